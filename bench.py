@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- hot-path benchmark (contract: see the task statement / DESIGN.md "Measurement").
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload train|eval]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload train|eval] [--full] [--dump-outputs DIR]
 
 One "step" is one pass of the hot path over one batch of synthetic input already resident in HBM:
   train: one CTLModel.training_step (ResNet50 256x128 bf16, P=16 x K=4 = 64 images, all four
@@ -9,6 +9,11 @@ One "step" is one pass of the hot path over one batch of synthetic input already
   eval : normalise + squared-L2 matrix + rank + CMC/mAP over 2228 x 17661 x 2048 fp32
          (DukeMTMC-shaped, BASELINE configs[4]) -> metric eval_dist_pairs_per_sec
 Rank 0 prints ONE JSON line.  For N>1 launch with torch.distributed.run (one rank per GPU, RCCL).
+
+A plain run sets up, warms up, times the K steps and prints the headline.  --full adds everything else the line used to
+carry: per-kernel and in-situ rooflines, counter passes, CPU baselines, the other precisions, batch sizes and shapes, the
+evaluation legs of a training run, the stock torch-ROCm yardstick.  --dump-outputs DIR writes what the timed path computed
+in its last step as DIR/<name>.npy (float32 / float64; the inputs are seeded, so two builds compare output for output).
 """
 from __future__ import annotations
 
@@ -215,10 +220,12 @@ def pmc_eval_insitu(timeout_s=75):
     return out
 
 
-def run_eval(args, rank, world, steps=None, warmup=None, shape=None, extras=True):
+def run_eval(args, rank, world, steps=None, warmup=None, shape=None, extras=True, full=True, outputs=None):
     """BASELINE configs[4]: normalise + squared-L2 + rank + CMC/mAP over 2228 x 17661 x 2048 fp32.  Timed twice:
     the METRIC-ONLY path the validation hook uses (streamed: the m x n matrix is never written; `value`) and the
-    materialised path (distance matrix + int64 ranked indices, what get_similar / the rank-index goldens need)."""
+    materialised path (distance matrix + int64 ranked indices, what get_similar / the rank-index goldens need).
+    full=False: the streamed path alone (no materialised run, first-call timing or per-kernel figures).  `outputs` (a dict,
+    rank 0): filled with the last timed step's (cmc, mAP, topk)."""
     from centroids_reid_amd import reid_metric as rm
     from centroids_reid_amd import parallel as par
     steps = steps or args.steps
@@ -269,25 +276,31 @@ def run_eval(args, rank, world, steps=None, warmup=None, shape=None, extras=True
     _quiet = open(os.devnull, "w")
     _so, sys.stdout = sys.stdout, _quiet                   # R1_mAP.compute mirrors the reference's banner print per call
     try:
-        dt_m, out_m = timed(step_materialised)
+        if full:
+            dt_m, out_m = timed(step_materialised)
         # the FIRST streamed evaluation of a label-set shape in a process reads the index statistics back mid-pipeline (8 bytes,
         # one extra host synchronisation); calls 2..N speculate on that capacity (reid_metric._CAP_HINT) and verify it in the
         # final read-back.  The timed steps below are all "call >= 2": the first call is timed separately, kernels warm.
-        step_streamed(); rm._CAP_HINT.clear()
-        barrier_sync(world)
-        t0 = time.perf_counter(); step_streamed(); barrier_sync(world)
-        first_call_ms = (time.perf_counter() - t0) * 1e3
+        step_streamed()
+        if full:
+            rm._CAP_HINT.clear()
+            barrier_sync(world)
+            t0 = time.perf_counter(); step_streamed(); barrier_sync(world)
+            first_call_ms = (time.perf_counter() - t0) * 1e3
         dt, out = timed(step_streamed)
     finally:
         sys.stdout = _so
         _quiet.close()
     pairs = float(nq) * ng * world * steps
     mAP = float(out[1].item())
-    assert abs(mAP - float(out_m[1].item())) < 1e-12, "streamed and materialised evaluation disagree"
+    if full:
+        assert abs(mAP - float(out_m[1].item())) < 1e-12, "streamed and materialised evaluation disagree"
+    if outputs is not None and rank == 0:
+        outputs.update(cmc=out[0], mAP=out[1].cpu().numpy(), topk=out[2])
 
     # ---- per-kernel roofline (rank 0): dominant kernel = the distance contraction (MFMA-bound)
     res = {}
-    if rank == 0:
+    if rank == 0 and full:
         fn, sq = rm.l2_normalize(feats, return_sqnorm=True)
         q, g = fn[:nq], fn[nq:]
         qq, gg = sq[:nq].contiguous(), sq[nq:].contiguous()
@@ -375,6 +388,7 @@ def run_eval(args, rank, world, steps=None, warmup=None, shape=None, extras=True
         if not extras:
             for k in ("f16_vs_f32", "roofline_hbm_stages"):
                 res.pop(k, None)
+    if rank == 0:
         res["mAP"] = mAP
     return {
         "metric": "eval_dist_pairs_per_sec", "value": pairs / dt, "unit": "pairs/s",
@@ -555,6 +569,22 @@ def vendor_yardstick(timeout_s=None):
         return {"error": f"{type(e).__name__}: {e}"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float64 where the value is float64 or integral, float32 otherwise."""
+    os.makedirs(path, exist_ok=True)
+    conv = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        conv[name] = a.astype(np.float64 if a.dtype == np.float64 or a.dtype.kind in "iub" else np.float32)
+    total = sum(a.nbytes for a in conv.values())
+    assert total <= DUMP_LIMIT_BYTES, f"outputs to dump are {total} bytes, over the {DUMP_LIMIT_BYTES} byte limit"
+    for name, a in conv.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 # ----------------------------------------------------------------------------- main
 _REAL_STDOUT = sys.stdout
 _REAL_FD = 1
@@ -575,10 +605,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--workload", choices=["train", "eval"], default=None)
     ap.add_argument("--no-cpu-baseline", action="store_true",
-                    help="skip the CPU leg (profiling runs; the default run always reports it)")
+                    help="skip the CPU leg of a --full run (a --full run reports it by default)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every side measurement (rooflines, counter passes, CPU baselines, other "
+                         "precisions / sizes / shapes, the evaluation legs of a training run, the stock torch-ROCm yardstick)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy")
     ap.add_argument("--inner-trace", action="store_true", help=argparse.SUPPRESS)   # child of bench_train.insitu_trace
     ap.add_argument("--inner-eval-trace", action="store_true", help=argparse.SUPPRESS)   # child of pmc_eval_insitu
     args = ap.parse_args()
+    if (args.steps is not None and args.steps < 1) or (args.warmup is not None and args.warmup < 0):
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.inner_eval_trace:
         inner_eval_trace()
         return
@@ -594,12 +631,13 @@ def main():
             workload = "train"
         except ImportError:
             workload = "eval"
+    outputs = {} if args.dump_outputs else None
     if workload == "train":
         from centroids_reid_amd import bench_train
-        args.steps = args.steps or 30
+        args.steps = args.steps if args.steps is not None else 30
         args.warmup = args.warmup if args.warmup is not None else 5
         out = bench_train.run(args, rank, world, barrier_sync, time_kernel,
-                              None if args.no_cpu_baseline else cpu_baseline_train)
+                              None if args.no_cpu_baseline else cpu_baseline_train, full=args.full, outputs=outputs)
         if rank == 0 and world == 1 and "embed" in out and not args.no_cpu_baseline:
             out["embed"]["cpu_baseline"] = cpu_baseline_embed()
         if rank == 0 and world == 1 and "embed" in out:
@@ -610,7 +648,7 @@ def main():
                 if "embed" in vy:
                     vy["embed"]["product_over_vendor"] = out["embed"]["value"] / vy["embed"]["images_per_s"]
                 out["extra"] = {"vendor_yardstick": vy}
-        if os.environ.get("CREID_BENCH_NO_EVAL", "0") != "1":
+        if args.full and os.environ.get("CREID_BENCH_NO_EVAL", "0") != "1":
             # the other half of BASELINE.metric (eval query x gallery dist-pairs/s) rides in the same line, timed by
             # the same invocation: 5 steps after 2 warm-up of the configs[4] workload
             ev = run_eval(args, rank, world, steps=5, warmup=2)
@@ -628,15 +666,17 @@ def main():
                     vy["eval"]["product_streamed_over_vendor"] = ev["value"] / vy["eval"]["pairs_per_s_to_ranked_indices"]
                 out["eval"] = ev
     else:
-        args.steps = args.steps or 5
+        args.steps = args.steps if args.steps is not None else 5
         args.warmup = args.warmup if args.warmup is not None else 2
-        out = run_eval(args, rank, world)
+        out = run_eval(args, rank, world, full=args.full, outputs=outputs)
         out.pop("steps", None)
     if rank == 0:
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
         line = {"metric": out.pop("metric"), "value": out.pop("value"), "unit": out.pop("unit"),
                 "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                 "ms_per_step": out.pop("ms_per_step"), "higher_is_better": True, "scaling": "weak",
-                "vs_baseline": None, "dtype": out.pop("dtype"), "data": "synthetic", **out}
+                "vs_baseline": None, "dtype": out.pop("dtype"), "data": "synthetic", "full": args.full, **out}
         os.write(_REAL_FD, (json.dumps(line) + "\n").encode())
     if dist.is_available() and dist.is_initialized():
         dist.destroy_process_group()

@@ -804,7 +804,26 @@ def fp32_mode_step(P, K, H, W, steps=6, warmup=2, dtype=torch.float32):
             "final_loss": loss, "note": "same step, exact-f32 MFMA parity mode (the mode the <=1e-4 golden comparisons run in)"}
 
 
-def run(args, rank, world, barrier_sync, time_kernel, cpu_baseline_fn=None, minimal=False):
+def step_outputs(model, out, n_sample=1 << 22, seed=0):
+    """What the timed training step computed, as host arrays (`bench.py --dump-outputs`): the returned loss and logged values,
+    and the state the step updated -- Adam's device step counter, the centers, every floating buffer (BatchNorm running
+    statistics) and a fixed seeded sample of the flat parameter vector (all of it would be > 100 MB)."""
+    res = {"loss": out["loss"].detach().double().reshape(1).cpu().numpy()}
+    for k, v in out.get("other", {}).items():
+        res[k] = v.detach().double().reshape(-1).cpu().numpy()
+    opt = model.optimizers()[0]
+    res["adam_step"] = opt.hyper[1:2].double().cpu().numpy()      # every applied step, the graph replays included
+    flat = opt.flat.detach()
+    idx = np.sort(np.random.default_rng(seed).integers(0, flat.numel(), min(n_sample, flat.numel())))
+    res["params_sample"] = flat[torch.as_tensor(idx, device=flat.device)].float().cpu().numpy()
+    res["centers"] = model.center_loss.centers.detach().float().cpu().numpy()
+    res["buffers"] = torch.cat([b.detach().float().reshape(-1) for b in model.buffers() if b.is_floating_point()]).cpu().numpy()
+    return res
+
+
+def run(args, rank, world, barrier_sync, time_kernel, cpu_baseline_fn=None, minimal=False, full=True, outputs=None):
+    """The training benchmark: set up, warm up, time args.steps steps.  full=False stops there (the headline and what the
+    timing itself yields); `outputs` (a dict, rank 0) is filled with step_outputs() of the last timed step."""
     P, K, H, W = 16, 4, 256, 128
     arch = os.environ.get("CREID_BENCH_ARCH", "resnet50")      # resnet50_ibn_a: side measurement, not the headline config
     if os.environ.get("CREID_BENCH_CONFIG3", "0") == "1":      # side line: the training half of BASELINE configs[3]
@@ -931,6 +950,9 @@ def run(args, rank, world, barrier_sync, time_kernel, cpu_baseline_fn=None, mini
         res["step_mfma_frac"] = tf_step / MFMA_BF16_TFLOPS     # all conv FLOPs / whole-step time (incl. HBM-bound BN etc.)
         from . import _lib as L
         res["plans"] = "tuned" if (L.lib() and L.N_PLANS > 0) else "rules"   # tuned_plans.json covers the configs[1] / [3] shapes only
+        if outputs is not None:
+            outputs.update(step_outputs(model, out))     # before the side measurements below train the model further
+    if rank == 0 and full:
         tf, ig_ms, slow, fast = igemm_roofline(P * K, H, W, time_kernel)
         headline = world == 1 and arch == "resnet50" and not f32 and not f16 and (H, W) == (256, 128) and P == 16
         insitu = insitu_trace() if headline else None
@@ -1036,7 +1058,7 @@ def run(args, rank, world, barrier_sync, time_kernel, cpu_baseline_fn=None, mini
                 "value": e5["value"], "unit": e5["unit"], "ms_per_step": e5["ms_per_step"], "batch": 512,
                 "vs_batch256": e5["value"] / res["embed"]["configs3_embedding_half"]["value"],
                 "note": "two loader batches per forward (inference.run_inference macro_batch)"}
-    if ddp and arch == "resnet50" and not f32 and not f16 and (H, W) == (256, 128) and os.environ.get("CREID_BENCH_NO_EVAL", "0") != "1":
+    if full and ddp and arch == "resnet50" and not f32 and not f16 and (H, W) == (256, 128) and os.environ.get("CREID_BENCH_NO_EVAL", "0") != "1":
         er = run_embed_ranks(world, barrier_sync)            # every rank takes part; rank 0 reports
         if rank == 0:
             res["embed_ranks" if "embed" in res else "embed"] = er

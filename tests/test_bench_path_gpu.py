@@ -133,3 +133,44 @@ def test_map_delta_of_bf16_backbone_on_clustered_identities():
     assert 0.3 < r["mAP_f32"] < 0.95, r
     assert abs(r["mAP_bf16_minus_f32"]) < 2e-2, r
     assert r["min_cosine"] > 0.99, r
+
+
+def test_plain_bench_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """`bench.py --gpus 1 --steps N --warmup 1 --dump-outputs DIR` (deterministic kernels): ONE stdout line with the headline
+    fields and none of the --full side measurements; the last timed step's outputs in DIR as float32 / float64 .npy files
+    (64 MB at most) whose loss is the line's final_loss; the same arguments dump the same arrays bit for bit (seeded inputs);
+    and --steps sets the number of timed steps: two more steps advance Adam's device step counter by exactly two."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env["CREID_DETERMINISTIC"] = "1"
+
+    def bench(steps, tag):
+        d = tmp_path / tag
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+                            "--dump-outputs", str(d)], cwd=root, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+        lines = [ln for ln in r.stdout.strip().splitlines() if ln.strip()]
+        assert len(lines) == 1, lines
+        return json.loads(lines[0]), {n[:-4]: np.load(d / n) for n in sorted(os.listdir(d))}
+
+    line, arrs = bench(3, "a")
+    assert line["metric"] == "train_images_per_sec" and line["unit"] == "images/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "bf16" and line["steps"] == 3 and line["warmup"] == 1 and line["full"] is False
+    assert line["value"] > 0 and line["ms_per_step"] > 0
+    assert not {"eval", "embed", "roofline", "roofline_hbm_stages", "cpu_baseline", "fp32_mode", "f16_train"} & set(line), line.keys()
+    assert {"loss", "adam_step", "centers", "params_sample", "buffers"} <= set(arrs), sorted(arrs)
+    for n, a in arrs.items():
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), n
+    assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+    assert float(arrs["loss"][0]) == line["final_loss"]
+    line_b, arrs_b = bench(3, "b")
+    assert sorted(arrs_b) == sorted(arrs)
+    for n in arrs:
+        assert np.array_equal(arrs_b[n], arrs[n]), f"{n} differs between two runs with the same arguments"
+    line_c, arrs_c = bench(5, "c")
+    assert line_c["steps"] == 5
+    assert arrs_c["adam_step"][0] - arrs["adam_step"][0] == 2.0, (arrs["adam_step"], arrs_c["adam_step"])

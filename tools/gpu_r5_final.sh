@@ -5,7 +5,7 @@ o=gpurun_out/r5f; mkdir -p $o
 python -m pytest tests -m gpu -q --maxfail=25 --durations=8 > $o/pytest.log 2>&1
 echo "pytest rc $?" >> $o/pytest.log; tail -14 $o/pytest.log
 python -c "import __graft_entry__ as g; g.smoke()" > $o/smoke.log 2>&1; tail -2 $o/smoke.log
-python bench.py > $o/bench.json 2> $o/bench.err; echo "bench rc $?"
+python bench.py --full > $o/bench.json 2> $o/bench.err; echo "bench rc $?"
 bash tools/prof_train.sh r5f > $o/train_step_anatomy.md 2>&1; head -22 $o/train_step_anatomy.md
 db=$(find gpurun_out/prof_r5f -name "*.db" | head -1)
 python tools/train_layers.py $db > $o/train_layers.md 2>&1; tail -14 $o/train_layers.md
@@ -13,7 +13,7 @@ cp gpurun_out/prof_r5f.md $o/train_kernel_stats.md 2>/dev/null
 bash tools/prof_embed.sh r5fe > $o/embed_anatomy.md 2>&1; tail -4 $o/embed_anatomy.md
 repo=$(pwd)
 (cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats -d $repo/gpurun_out/prof_r5fev -o ev -- \
-   python $repo/bench.py --workload eval --steps 5 --warmup 2 --no-cpu-baseline > $repo/gpurun_out/prof_r5fev.log 2>&1)
+   python $repo/bench.py --workload eval --steps 5 --warmup 2 --full --no-cpu-baseline > $repo/$o/prof_r5fev.log 2>&1)
 python tools/prof_summary.py $(find gpurun_out/prof_r5fev -name "*.db" | head -1) $o/eval_kernel_stats.md > /dev/null; head -14 $o/eval_kernel_stats.md
 rm -rf gpurun_out/prof_r5f gpurun_out/prof_r5fe gpurun_out/prof_r5fev
 # HBM-side traffic of the streamed evaluation's contraction on the configs[3] shard, old grid rule vs the shipped one

@@ -6,7 +6,7 @@ repo=$(pwd)
 python -m pytest tests -m gpu -q --maxfail=25 --durations=8 > $o/pytest.log 2>&1
 echo "pytest rc $?" >> $o/pytest.log; tail -14 $o/pytest.log
 python -c "import __graft_entry__ as g; g.smoke()" > $o/smoke.log 2>&1; tail -2 $o/smoke.log
-( time python bench.py > $o/bench.json 2> $o/bench.err ) 2> $o/bench.time; echo "bench rc $?"; tail -3 $o/bench.time
+( time python bench.py --full > $o/bench.json 2> $o/bench.err ) 2> $o/bench.time; echo "bench rc $?"; tail -3 $o/bench.time
 # what each round-6 schedule change is worth on THIS box (same process environment, two interleaved repeats)
 bash tools/ab.sh "CREID_HEADS_ONE_CALL=0 CREID_DS_REDUCE2=0 CREID_C3_AXF= CREID_HEADS_BNRED=0" "CREID_DS_REDUCE2=0 CREID_C3_AXF= CREID_HEADS_BNRED=0" \
   "CREID_C3_AXF= CREID_HEADS_BNRED=0" "CREID_C3_AXF=" "CREID_X=default" "CREID_WPREP_SIDE=1" > $o/switches_ab.txt 2>&1; cat $o/switches_ab.txt
@@ -17,7 +17,7 @@ python tools/step_sequence.py $db > $o/step_sequence.txt 2>&1
 cp gpurun_out/prof_r6f.md $o/train_kernel_stats.md 2>/dev/null
 bash tools/prof_embed.sh r6fe > $o/embed_anatomy.md 2>&1; tail -4 $o/embed_anatomy.md
 (cd /tmp && export TMPDIR=/tmp && CREID_BENCH_NO_PMC=1 rocprofv3 --kernel-trace --stats -d $repo/gpurun_out/prof_r6fev -o ev -- \
-   python $repo/bench.py --workload eval --steps 5 --warmup 2 --no-cpu-baseline > $repo/gpurun_out/prof_r6fev.log 2>&1)
+   python $repo/bench.py --workload eval --steps 5 --warmup 2 --full --no-cpu-baseline > $repo/$o/prof_r6fev.log 2>&1)
 python tools/prof_summary.py $(find gpurun_out/prof_r6fev -name "*.db" | head -1) $o/eval_kernel_stats.md > /dev/null; head -14 $o/eval_kernel_stats.md
 # the exact-f32 parity mode of the step: where its time goes
 (cd /tmp && export TMPDIR=/tmp && CREID_BENCH_DTYPE=f32 CREID_BENCH_NO_EVAL=1 CREID_BENCH_NO_INSITU=1 CREID_BENCH_NO_PMC=1 rocprofv3 --kernel-trace --stats -d $repo/gpurun_out/prof_r6f32 -o t -- \

@@ -4,7 +4,7 @@
 o=gpurun_out/r5b; mkdir -p $o
 timeout 700 python -m pytest tests -m gpu -q --maxfail=15 --durations=10 > $o/pytest.log 2>&1
 echo "pytest rc $?" >> $o/pytest.log; tail -25 $o/pytest.log
-python bench.py > $o/bench.json 2> $o/bench.err; echo "bench rc $?"
+python bench.py --full > $o/bench.json 2> $o/bench.err; echo "bench rc $?"
 bash tools/prof_train.sh r5b > $o/train_anatomy.md 2>&1
 db=$(find gpurun_out/prof_r5b -name "*.db" | head -1)
 python tools/train_layers.py $db > $o/train_layers.md 2>&1; tail -16 $o/train_layers.md

@@ -4,7 +4,7 @@ o=gpurun_out/r6s30; mkdir -p $o
 for rep in 1 2; do
   for lib in prev new; do
     if [ $lib = prev ]; then export CREID_LIB_PATH=$PWD/centroids-reid_amd/lib/libcreid_hip_prev.so; else unset CREID_LIB_PATH; fi
-    python bench.py --workload eval --steps 20 --warmup 5 --no-cpu-baseline > $o/eval_${lib}_$rep.json 2> $o/eval.err
+    python bench.py --workload eval --steps 20 --warmup 5 --full --no-cpu-baseline > $o/eval_${lib}_$rep.json 2> $o/eval.err
     python - <<PY
 import json
 d = json.load(open("$o/eval_${lib}_$rep.json"))

@@ -1,6 +1,6 @@
 #!/bin/bash
 o=gpurun_out/r6s36; mkdir -p $o
-( time python bench.py > $o/bench.json 2> $o/bench.err ) 2> $o/time.txt; echo "rc $?"; tail -3 $o/time.txt; tail -2 $o/bench.err
+( time python bench.py --full > $o/bench.json 2> $o/bench.err ) 2> $o/time.txt; echo "rc $?"; tail -3 $o/time.txt; tail -2 $o/bench.err
 python - <<'PY'
 import json
 d = json.load(open("gpurun_out/r6s36/bench.json"))
