@@ -39,6 +39,7 @@ SIGNATURES = {
     "creid_stream_finalize": (C.c_int, [_p, _p, _i64, _i32, _p, _p, _p, _p]),
     "creid_tune_set": (C.c_int, [_i32, _i64, _i64, _i64, _i64, _i32, _i32, _i32]),
     "creid_tune_clear": (C.c_int, []),
+    "creid_tune_count": (_i64, [_i32, _i64, _i64, _i64, _i64, _i32]),
     "creid_loo_centroids_fwd": (C.c_int, [_p, _p, _i64, _i64, _i64, _p, _p, _p]),
     "creid_loo_centroids_bwd": (C.c_int, [_p, _p, _i64, _i64, _i64, _p, _p]),
     "creid_loo_emb_fwd": (C.c_int, [_p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p]),

@@ -61,6 +61,24 @@ def conv_shapes(B, H, W, last_stride=1):
     return shapes
 
 
+# the workloads tuned_plans.json was measured for (its "_comment"): (H, W) -> batch sizes; each runs with last_stride 1 and 2
+PLAN_WORKLOADS = {(256, 128): (32, 64, 128, 192, 256, 384, 512), (320, 320): (56, 128, 256, 512)}
+
+
+def conv_plan_keys(B, H, W, last_stride=1):
+    """Per convolution of conv_shapes: (shape, keys), keys = the launch-plan keys (kind, M, N, K, mode) its launches look up in
+    the registry of tuned_plans.json, derived as conv_igemm.hip / conv_wgrad.hip derive them (mode = transposed | stride << 1,
+    | 8 for the folded eval-mode epilogue): forward, its eval-mode twin, data gradient, weight gradient."""
+    out = []
+    for cin, cout, k, s, h, w in conv_shapes(B, H, W, last_stride):
+        oh, ow = (h + 2 * (k // 2) - k) // s + 1, (w + 2 * (k // 2) - k) // s + 1
+        m_out, kk = B * oh * ow, cin * k * k
+        out.append(((cin, cout, k, s, h, w), {"fwd": (1, m_out, cout, kk, s << 1), "fwd_eval": (1, m_out, cout, kk, (s << 1) | 8),
+                                              "dgrad": (1, B * h * w, cin, cout * k * k, 1 | (s << 1)),
+                                              "wgrad": (0, m_out, cout, kk, s << 1)}))
+    return out
+
+
 def igemm_roofline(B, H, W, time_kernel, reps=5):
     """Live HIP-event timing of the dominant kernel family (igemm_bf16_kernel: conv forward + data gradient)
     over the real ResNet50 layer mix: achieved = sum(algorithmic FLOPs) / sum(avg launch duration)."""

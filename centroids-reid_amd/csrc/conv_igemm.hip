@@ -1254,14 +1254,22 @@ static int launch_igemm(const IGemmGeom& g_in, const void* src, const void* wgt,
   // (folded eval-mode launches -- epi_scale set -- look for a plan measured with THAT epilogue first: key bit 3; plans recorded
   // before the bit existed carry no mode and serve both)
   const int plan_d = g.transposed | (g.stride << 1);
-  const bool have_plan = creid_is16(dtype) && ((g.epi_scale && creid_tune_lookup(CREID_TUNE_IGEMM, g.M, g.N, g.K, plan_d | 8, tp)) ||
-                                                  creid_tune_lookup(CREID_TUNE_IGEMM, g.M, g.N, g.K, plan_d, tp));
+  const bool plan_eval = creid_is16(dtype) && g.epi_scale && creid_tune_lookup(CREID_TUNE_IGEMM, g.M, g.N, g.K, plan_d | 8, tp);
+  const bool have_plan = plan_eval || (creid_is16(dtype) && creid_tune_lookup(CREID_TUNE_IGEMM, g.M, g.N, g.K, plan_d, tp));
+  // the plan's kernel (tp.p2) once its word passed the checks below, else -1; `ran` records a launch that found a plan and took
+  // another kernel (creid_tune_count, what = 1).  Kernel ids: the plan kinds 0..5, 6 = the 3 x 3 c64 kernel, -2 = the rest.
+  int planned = -1;
+  auto ran = [&](int kernel) {
+    if (have_plan && kernel != planned) creid_tune_declined(CREID_TUNE_IGEMM, g.M, g.N, g.K, plan_eval ? (plan_d | 8) : plan_d);
+  };
   if (have_plan && dtype == CREID_F16 && tp.p2 == 2) {
     // (the first persistent 1x1 kernel of conv_stream.hip is bf16 only: f16 launches of those shapes take the built-in rule)
   } else if (have_plan && tp.p2 == 5) {
     tuned_pp = tp.p0;                                              // plan kind 5: all-waves-multiply persistent kernel, p0 = its variant word
+    planned = 5;
   } else if (have_plan && (tp.p0 == 64 || tp.p0 == 128) && g.N % tp.p0 == 0 && (tp.p1 == 2 || tp.p1 == 3 || tp.p1 == 4)) {
     bn = tp.p0; tuned_stages = tp.p1; tuned_dma = tp.p2 == 1; tuned_stream = tp.p2 == 2; tuned_bm256 = tp.p2 == 3; tuned_stream2 = tp.p2 == 4;
+    planned = (tp.p2 >= 1 && tp.p2 <= 4) ? tp.p2 : 0;            // (any other word: the producer/consumer kernel)
   }
   // layer1's 3 x 3, 64 -> 64 forward: halo tile in LDS, weights in registers (conv_stream.hip conv3x3_c64_kernel); CREID_C64_3X3=0:
   // the tile kernels
@@ -1272,7 +1280,7 @@ static int launch_igemm(const IGemmGeom& g_in, const void* src, const void* wgt,
         g.pad == 1 && g.pitch == 64 && g.check_bounds && !add_src && !bnred.x && !wred.ws && g.SH == g.OH && g.SW == g.OW &&
         !(bn_part && g.epi_scale)) {
       const int rc = launch_conv3x3_c64(g.M, g.OH, g.OW, src, wgt, out, bn_part, g.epi_scale, g.epi_shift, g.epi_relu, dtype, s);
-      if (rc != CREID_E_SHAPE) return rc;
+      if (rc != CREID_E_SHAPE) { ran(6); return rc; }
     }
   }
   // all-waves-multiply persistent kernel (conv_pipe.hip): plan kind 5, or CREID_IGEMM_PP = 0x1000 | variant for every launch it covers
@@ -1282,7 +1290,7 @@ static int launch_igemm(const IGemmGeom& g_in, const void* src, const void* wgt,
     const bool pp_off = pe && force_pp == 0;                              // CREID_IGEMM_PP=0: never, not even where a plan selects it
     if (creid_is16(dtype) && !bnred.x && !wred.ws && g.log2span >= 6 && !pp_off && (force_pp || tuned_pp >= 0)) {
       const int rc = launch_igemm_pp(g, src, wgt, out, add_src, bn_part, force_pp ? (force_pp & 0xfff) : tuned_pp, dtype, s);
-      if (rc != CREID_E_SHAPE) return rc;
+      if (rc != CREID_E_SHAPE) { ran(force_pp ? -2 : 5); return rc; }
     }
   }
   // persistent streaming kernel for the small-K 1x1 stride-1 forward convolutions (conv_stream.hip): plan kind 2, or
@@ -1294,7 +1302,7 @@ static int launch_igemm(const IGemmGeom& g_in, const void* src, const void* wgt,
                            g.kw == 1 && g.check_bounds && !add_src && !bnred.x && !wred.ws && g.pitch == g.K && !g.epi_scale;
     if (plain_1x1 && (force_stream || tuned_stream)) {
       const int rc = launch_stream1x1(g.M, g.K, g.N, src, wgt, out, bn_part, s);
-      if (rc != CREID_E_SHAPE) return rc;
+      if (rc != CREID_E_SHAPE) { ran(tuned_stream ? 2 : -2); return rc; }
     }
     // second form (plan kind 4 / CREID_STREAM2=1): also the folded eval-mode epilogue with the block's residual
     const char* f2 = CREID_KNOB_ENV("CREID_STREAM2");
@@ -1306,7 +1314,7 @@ static int launch_igemm(const IGemmGeom& g_in, const void* src, const void* wgt,
       // (plan: p1 = 2 -> widest column slab the LDS allows, 3 -> at most 128 columns, 4 -> 64)
       const int cap = tuned_stream2 ? (tuned_stages == 3 ? 128 : (tuned_stages == 4 ? 64 : 0)) : 0;
       const int rc = launch_stream2(g.M, g.K, g.N, src, wgt, out, bn_part, add_src, g.epi_scale, g.epi_shift, g.epi_relu, cap, dtype, s);
-      if (rc != CREID_E_SHAPE) return rc;
+      if (rc != CREID_E_SHAPE) { ran(tuned_stream2 ? 4 : -2); return rc; }
     }
   }
   if (g.N % bn != 0) return CREID_E_SHAPE;
@@ -1351,6 +1359,7 @@ static int launch_igemm(const IGemmGeom& g_in, const void* src, const void* wgt,
           if (dtype == CREID_F16) { if (st256 == 3) CREID_WS256_LAUNCH(3, F16T); else CREID_WS256_LAUNCH(2, F16T); }
           else { if (st256 == 3) CREID_WS256_LAUNCH(3, Bf16T); else CREID_WS256_LAUNCH(2, Bf16T); }
 #undef CREID_WS256_LAUNCH
+          ran(tuned_bm256 ? 3 : -2);
           return (int)hipGetLastError();
         }
       }
@@ -1366,6 +1375,7 @@ static int launch_igemm(const IGemmGeom& g_in, const void* src, const void* wgt,
       else { if (ws_stages == 4) CREID_WS_LAUNCH(64, 4); else if (ws_stages == 2) CREID_WS_LAUNCH(64, 2); else CREID_WS_LAUNCH(64, 3); }
 #undef CREID_WS_LAUNCH
 #undef CREID_WS_LAUNCH1
+      ran(0);
       return (int)hipGetLastError();
     }
     if (wred.ws) { const int rc = wgrad_reduce_job_launch(wred, s); if (rc) return rc; wred.ws = nullptr; }
@@ -1389,6 +1399,8 @@ static int launch_igemm(const IGemmGeom& g_in, const void* src, const void* wgt,
     }
 #undef CREID_DMA_LAUNCH
 #undef CREID_DMA_LAUNCH1
+    ran(1);
+    return (int)hipGetLastError();
   } else if (bnred.x || g.add_mask || (g.epi_scale && creid_is16(dtype)) || dtype == CREID_F16) {
     return CREID_E_DTYPE;          // the fused reduction / masked add / folded BatchNorm (and f16) exist only in the 16-bit LDS-DMA kernels
   } else if (wred.ws && wgrad_reduce_job_launch(wred, s) != 0) {
@@ -1412,6 +1424,7 @@ static int launch_igemm(const IGemmGeom& g_in, const void* src, const void* wgt,
   } else {
     return CREID_E_DTYPE;
   }
+  ran(-2);
   return (int)hipGetLastError();
 }
 

@@ -712,8 +712,10 @@ static WgradPlan plan_wgrad(int M, int NCO, int K, int dtype, int stride = 1) {
   WgradPlan p;
   p.stages = 0; p.ws = 0; p.kg = 0;
   TunePlan tp;
-  if (creid_is16(dtype) && creid_tune_lookup(CREID_TUNE_WGRAD, M, NCO, K, stride << 1, tp) && (tp.p0 == 64 || tp.p0 == 128) &&
-      (tp.p1 == 64 || tp.p1 == 128) && NCO % tp.p0 == 0 && K % tp.p1 == 0 && tp.p2 >= 1) {
+  const bool have_plan = creid_is16(dtype) && creid_tune_lookup(CREID_TUNE_WGRAD, M, NCO, K, stride << 1, tp);
+  if (have_plan && !((tp.p0 == 64 || tp.p0 == 128) && (tp.p1 == 64 || tp.p1 == 128) && NCO % tp.p0 == 0 && K % tp.p1 == 0 && tp.p2 >= 1))
+    creid_tune_declined(CREID_TUNE_WGRAD, M, NCO, K, stride << 1);      // a word this shape cannot run: the built-in rule below
+  else if (have_plan) {
     // measured plan for this shape: tile tp.p0 x tp.p1, tp.p2 = pixel splits | ring depth << 16 | producer/consumer << 20 |
     // two k-groups << 21
     p.tm = tp.p0; p.tn = tp.p1;

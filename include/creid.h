@@ -152,6 +152,11 @@ int creid_stream_finalize(const int32_t* npos, const uint32_t* hist, int64_t m, 
  * register before the first convolution (the Python binding does it at load time from tuned_plans.json). */
 int creid_tune_set(int32_t kind, int64_t a, int64_t b, int64_t c, int64_t d, int32_t p0, int32_t p1, int32_t p2);
 int creid_tune_clear(void);
+/* Host-side use counters of one registered plan: what = 0 -> lookups that returned it, what = 1 -> launches that found it but
+ * ran another kernel (a plan word the launch's validity checks reject, a planned kernel that refused the shape, a kernel that
+ * takes the shape ahead of every plan).  -1 when (kind, a, b, c, d) is not registered, -2 when `what` is neither 0 nor 1;
+ * creid_tune_clear drops the counts with the entries. */
+int64_t creid_tune_count(int32_t kind, int64_t a, int64_t b, int64_t c, int64_t d, int32_t what);
 
 /* ------------------------------------------------------------------ stage B: centroids */
 

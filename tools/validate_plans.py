@@ -39,13 +39,8 @@ plans = doc["plans"]
 
 def conv_ms(B, H, W):
     """(M, N, K) of every forward convolution at this size (and of its data gradient) -> which plans belong to the configuration."""
-    from centroids_reid_amd.bench_train import conv_shapes
-    out = set()
-    for cin, cout, k, s, h, w in conv_shapes(B, H, W):
-        oh, ow = (h + 2 * (k // 2) - k) // s + 1, (w + 2 * (k // 2) - k) // s + 1
-        out.add((B * oh * ow, cout, cin * k * k))
-        out.add((B * h * w, cin, cout * k * k))                  # data gradient
-    return out
+    from centroids_reid_amd.bench_train import conv_plan_keys
+    return {keys[what][1:4] for _, keys in conv_plan_keys(B, H, W) for what in ("fwd", "dgrad")}
 
 
 def write_tmp(entries):
