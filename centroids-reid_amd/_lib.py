@@ -15,6 +15,10 @@ LIB_PATH = os.environ.get("CREID_LIB_PATH") or os.path.join(_HERE, "lib", "libcr
 
 F32, BF16, F16 = 0, 1, 2
 _DT = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
+# convolution mode, not a storage type (include/creid.h): fp32 activations, weights split into two bf16 planes, three bf16 MFMAs
+# per product; accepted by the forward convolutions and the weight preparation only
+BF16X3 = 3
+EVAL_PRECISIONS = ("bf16x3",)
 
 _lib = None
 

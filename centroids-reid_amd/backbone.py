@@ -14,6 +14,7 @@ import contextlib
 import ctypes as C
 import math
 import os
+import weakref
 
 import torch
 from torch import nn
@@ -245,12 +246,26 @@ class _ConvUnit:
 
 
 class BackboneEngine:
-    """Explicit forward / backward schedule for one backbone instance."""
+    """Explicit forward / backward schedule for one backbone instance.
+
+    dtype: a torch dtype (the activation and MFMA input type), or the string "bf16x3" -- the eval-mode forward with fp32
+    activations whose convolutions run three bf16 MFMAs per product on split operands (fp32-grade embeddings on the bf16 matrix
+    pipe, csrc/conv_x3.hip).  That mode has no training forward / backward."""
 
     def __init__(self, net: ResNet, dtype=torch.bfloat16):
         self.net = net
+        self.mode = dtype if isinstance(dtype, str) else None
+        if self.mode is not None and self.mode not in L.EVAL_PRECISIONS:
+            raise ValueError(f"unknown compute mode {dtype!r} (a torch dtype or one of {L.EVAL_PRECISIONS})")
+        self.x3 = self.mode == "bf16x3"
+        if self.x3:
+            dtype = torch.float32          # activations and every non-convolution launch stay fp32
         self.dtype = dtype
         self.dt = L._DT[dtype]
+        self.conv_dt = L.BF16X3 if self.x3 else self.dt     # dtype code of the forward convolutions and their weight copies
+        # engines of the same network share a weight-change flag: an optimiser step announced to the training engine also
+        # makes an eval-mode engine (Baseline eval_precision) re-derive its copies
+        net.__dict__.setdefault("_creid_engines", weakref.WeakSet()).add(self)
         self.eval_ds_side = os.environ.get("CREID_EVAL_DS_SIDE", "0") == "1"   # eval forward: downsample conv on a side stream
         self.units = []
         self.stem = _ConvUnit(net.conv1, net.bn1)
@@ -330,6 +345,8 @@ class BackboneEngine:
                                "(the register-staged fallback kernels exist for bfloat16 and float32 only)")
         self.eval_fold = os.environ.get("CREID_EVAL_FOLD", "1") == "1" and \
             (dtype == torch.float32 or os.environ.get("CREID_IGEMM_DMA", "1") == "1")
+        if self.x3:
+            self.eval_fold = True          # (bf16x3 exists as the folded forward only: no statistics / apply schedule)
         self._fold_key = None
         # TIMING-ONLY ablation (results are WRONG): bit 0 skips the forward BatchNorm apply launches of bn1 / bn2 (no residual),
         # bit 1 their backward apply launches -- the upper bound of what fusing those passes into the consuming / producing
@@ -353,6 +370,17 @@ class BackboneEngine:
                   file=sys.stderr)
 
     # ---- helpers
+    @property
+    def weights_dirty(self):
+        return self._weights_dirty
+
+    @weights_dirty.setter
+    def weights_dirty(self, v):
+        self._weights_dirty = v
+        if v:
+            for e in list(self.net.__dict__.get("_creid_engines", ())):
+                e._weights_dirty = True
+
     @property
     def device(self):
         return self.net.conv1.weight.device
@@ -395,7 +423,9 @@ class BackboneEngine:
         lib, st = L.lib(), L.stream()
         units = [u for u in self.all_units() if u is not self.stem]
         for u in units:
-            if u.w_krsc is None:
+            if u.w_krsc is None and self.x3:
+                u.w_krsc = self._empty(2, u.cout, u.k, u.k, u.cin, dtype=torch.bfloat16)   # hi plane, lo plane; no dgrad copy
+            elif u.w_krsc is None:
                 u.w_krsc = self._empty(u.cout, u.k, u.k, u.cin)
                 u.w_crsk = self._empty(u.cin, u.k, u.k, u.cout)
         if self.stem.w_krsc is None:
@@ -407,7 +437,8 @@ class BackboneEngine:
             assert lib.creid_weight_prep_entry_bytes() == rec.dtype.itemsize == 48
             start, tiles, tstart = 0, 0, np.zeros(len(units), np.int32)
             for i, u in enumerate(units):
-                rec[i] = (u.conv.weight.data_ptr(), u.w_krsc.data_ptr(), u.w_crsk.data_ptr(), u.cout, u.cin, u.k, u.k, start)
+                rec[i] = (u.conv.weight.data_ptr(), u.w_krsc.data_ptr(), 0 if u.w_crsk is None else u.w_crsk.data_ptr(), u.cout,
+                          u.cin, u.k, u.k, start)
                 start += u.cout * u.cin * u.k * u.k
                 tstart[i] = tiles
                 tiles += ((u.cout + 31) // 32) * ((u.cin + 31) // 32)
@@ -424,10 +455,10 @@ class BackboneEngine:
             # signalling (tools/probes/anyorder_probe.hip) against ~45 us hidden.
             with self._fork_side():
                 L.check(lib.creid_weight_prep_multi(L.ptr(self._wprep_tab), L.ptr(self._wprep_tiles), len(units), self._wprep_total,
-                                                    self.dt, L.stream()), "weight_prep_multi")
+                                                    self.conv_dt, L.stream()), "weight_prep_multi")
         else:
             L.check(lib.creid_weight_prep_multi(L.ptr(self._wprep_tab), L.ptr(self._wprep_tiles), len(units), self._wprep_total,
-                                                self.dt, st), "weight_prep_multi")
+                                                self.conv_dt, st), "weight_prep_multi")
         self.weights_dirty = False
         self._wsig = self._weight_signature()
         return side
@@ -479,7 +510,7 @@ class BackboneEngine:
         d, oh, ow = _desc(B, H, W, u.cin, u.cout, u.k, u.stride, u.pad)
         a = self._empty(B * oh * ow, u.cout)
         L.check(lib.creid_conv2d_fwd_affine_nhwc(C.byref(d), L.ptr(a_in), L.ptr(u.w_krsc), L.ptr(a), L.ptr(u.fold),
-                                                 L.ptr(residual), 1 if relu else 0, self.dt, st), "conv2d_fwd_affine")
+                                                 L.ptr(residual), 1 if relu else 0, self.conv_dt, st), "conv2d_fwd_affine")
         return a, oh, ow
 
     def _stem_operand(self, x, B, H, W):
@@ -594,12 +625,12 @@ class BackboneEngine:
             part = None
             if (oh * ow) % 128 == 0:
                 part = self._empty(lib.creid_conv2d_bn_partial_rows(C.byref(d)) * 2, u.cout, dtype=torch.float32)
-            L.check(lib.creid_conv2d_fwd_nhwc(C.byref(d), L.ptr(a_in), L.ptr(u.w_krsc), L.ptr(x), L.ptr(part), self.dt, st),
+            L.check(lib.creid_conv2d_fwd_nhwc(C.byref(d), L.ptr(a_in), L.ptr(u.w_krsc), L.ptr(x), L.ptr(part), self.conv_dt, st),
                     "conv2d_fwd")
             return (x,) + self._ibn_tail(u, x, B, oh * ow, training, relu, part) + (oh, ow)
         rows = lib.creid_conv2d_bn_partial_rows(C.byref(d)) if training else 0
         part = self._empty(rows * 2, u.cout, dtype=torch.float32) if training else None
-        L.check(lib.creid_conv2d_fwd_nhwc(C.byref(d), L.ptr(a_in), L.ptr(u.w_krsc), L.ptr(x), L.ptr(part), self.dt, st),
+        L.check(lib.creid_conv2d_fwd_nhwc(C.byref(d), L.ptr(a_in), L.ptr(u.w_krsc), L.ptr(x), L.ptr(part), self.conv_dt, st),
                 "conv2d_fwd")
         return (x,) + self._bn_tail(u, x, part, rows, M, training, relu, residual, residual_ss, apply) + (oh, ow)
 
@@ -705,6 +736,9 @@ class BackboneEngine:
             assert x_nchw.dtype == torch.float32 and x_nchw.dim() == 4 and x_nchw.shape[1] == 3
         else:
             L.require_gpu(x_nchw.xpad)
+        if training and self.x3:
+            raise L.CreidError("compute mode bf16x3 is an eval-mode forward only (validation / inference): train with bfloat16, "
+                               "float16 or float32 and pass eval_precision='bf16x3' to Baseline / CTLModel")
         wprep_pending = False
         if self.weights_dirty or self._wsig != self._weight_signature():
             # training steps replayed from a hipGraph re-derive the 16-bit weight copies every step (the optimiser has just rewritten

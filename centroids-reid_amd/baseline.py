@@ -3,19 +3,23 @@
 `Baseline(cfg).forward(x) -> (base_out, global_feat)`; `self.base` holds the backbone parameters
 under the reference's names (state_dict keys `base.conv1.weight`, ...).  `compute_dtype` selects the
 activation / MFMA input type: torch.bfloat16 (throughput mode; the reference's AMP analogue when
-cfg.USE_MIXED_PRECISION) or torch.float32 (parity mode, exact-f32 MFMA)."""
+cfg.USE_MIXED_PRECISION) or torch.float32 (parity mode, exact-f32 MFMA).  `eval_precision="bf16x3"` runs the eval-mode forward
+(validation, inference) on a second engine over the same fp32 master weights: fp32 activations, convolutions as three bf16
+MFMAs per product on split operands -- fp32-grade embeddings at several times the fp32 mode's rate; training keeps
+`compute_dtype`."""
 from __future__ import annotations
 
 import torch
 from torch import nn
 
+from . import _lib as L
 from . import backbone as bb
 
 
 class Baseline(nn.Module):
     in_planes = 2048
 
-    def __init__(self, cfg, compute_dtype=None):
+    def __init__(self, cfg, compute_dtype=None, eval_precision=None):
         super().__init__()
         last_stride = cfg.MODEL.LAST_STRIDE
         model_name = cfg.MODEL.NAME
@@ -34,7 +38,11 @@ class Baseline(nn.Module):
         # train_ctl_model.py:44), switch it off and save the 67 MB layout pass per batch.  It is a detached copy: gradients flow
         # through global_feat only.
         self.return_base_out = True
+        if eval_precision is not None and eval_precision not in L.EVAL_PRECISIONS:
+            raise ValueError(f"eval_precision must be None or one of {L.EVAL_PRECISIONS}, got {eval_precision!r}")
+        self.eval_precision = eval_precision
         self._engine = None
+        self._eval_engine = None
         self.loss_scaler = None           # f16 training: solver.LossScaler (ModelBase.configure_optimizers attaches it)
 
     @property
@@ -44,13 +52,21 @@ class Baseline(nn.Module):
         self._engine.loss_scaler = self.loss_scaler
         return self._engine
 
+    def engine_for(self, training: bool):
+        """The engine a forward in this mode runs on: the eval_precision engine for eval-mode forwards when one is set."""
+        if training or self.eval_precision is None:
+            return self.engine
+        if self._eval_engine is None or self._eval_engine.mode != self.eval_precision:
+            self._eval_engine = bb.BackboneEngine(self.base, self.eval_precision)
+        return self._eval_engine
+
     def state_dict(self, *args, **kwargs):
         if self._engine is not None:
             self._engine.fold_counters()
         return super().state_dict(*args, **kwargs)
 
     def forward(self, x):
-        eng = self.engine
+        eng = self.engine_for(self.training)
         if isinstance(x, torch.Tensor):                 # (a transforms.StemOperand passes through: already the stem's layout)
             x = x.contiguous().float()
         if self.training and torch.is_grad_enabled():

@@ -81,7 +81,7 @@ def load_checkpoint_file(path, map_location="cpu"):
 
 
 class ModelBase(_Base):
-    def __init__(self, cfg=None, test_dataloader=None, compute_dtype=None, **kwargs):
+    def __init__(self, cfg=None, test_dataloader=None, compute_dtype=None, eval_precision=None, **kwargs):
         super().__init__()
         if cfg is None:
             hparams = {**kwargs}
@@ -99,7 +99,7 @@ class ModelBase(_Base):
         if test_dataloader is not None:
             self.test_dataloader = test_dataloader
 
-        self.backbone = Baseline(self.hparams, compute_dtype=compute_dtype)
+        self.backbone = Baseline(self.hparams, compute_dtype=compute_dtype, eval_precision=eval_precision)
         self.backbone.return_base_out = False            # this module only reads global_feat (modelling/bases.py:171)
         self.contrastive_loss = TripletLoss(self.hparams.SOLVER.MARGIN, self.hparams.SOLVER.DISTANCE_FUNC)
         d_model = self.hparams.MODEL.BACKBONE_EMB_SIZE

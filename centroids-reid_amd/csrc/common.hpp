@@ -118,3 +118,6 @@ struct F16T {
   }
 };
 static inline bool creid_is16(int dtype) { return dtype == CREID_BF16 || dtype == CREID_F16; }
+// the storage types: CREID_BF16X3 is a convolution mode (fp32 activations, split bf16 weights), accepted only by the forward
+// convolutions and the weight preparation
+static inline bool creid_is_storage(int dtype) { return dtype == CREID_F32 || creid_is16(dtype); }

@@ -46,6 +46,11 @@ struct IGemmGeom {
 #define CREID_ABL_ON(word, bits) 0
 #endif
 
+// bf16x3 forward convolution (conv_x3.hip): fp32 source / output, two-plane bf16 weights [2][N][K]; returns CREID_E_SHAPE for a
+// geometry it does not cover (data gradient, the pre-padded stem image)
+int launch_igemm_x3(const IGemmGeom& g, const void* src, const void* wgt, void* out, const void* add_src, float* bn_part,
+                    hipStream_t s);
+
 static inline void igemm_finish_geom(IGemmGeom& g) {
   g.inv_ohow = 1.0f / (float)(g.OH * g.OW);
   g.inv_ow = 1.0f / (float)g.OW;

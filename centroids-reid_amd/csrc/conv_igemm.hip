@@ -1237,6 +1237,7 @@ static int launch_igemm(const IGemmGeom& g_in, const void* src, const void* wgt,
 #else
   const int abl_env = 0;
 #endif
+  if (!creid_is_storage(dtype)) return CREID_E_DTYPE;     // (CREID_BF16X3 forward convolutions go to launch_igemm_x3)
   IGemmGeom g = g_in;
   g.abl = abl_env;
   WRedJob wred{};
@@ -1456,6 +1457,7 @@ int creid_conv2d_fwd_nhwc(const creid_conv_desc* d, const void* x, const void* w
   g.kw = d->kw; g.stride = d->stride; g.pad = d->pad; g.transposed = 0;
   g.K = (int)(d->kh * d->kw * d->in_c); g.N = (int)d->out_c; g.check_bounds = 1;
   igemm_finish_geom(g);
+  if (dtype == CREID_BF16X3) return launch_igemm_x3(g, x, w_krsc, y, nullptr, bn_partial, as_stream(stream));
   return launch_igemm(g, x, w_krsc, y, nullptr, bn_partial, dtype, as_stream(stream));
 }
 
@@ -1473,6 +1475,7 @@ int creid_conv2d_fwd_affine_nhwc(const creid_conv_desc* d, const void* x, const 
   g.K = (int)(d->kh * d->kw * d->in_c); g.N = (int)d->out_c; g.check_bounds = 1;
   igemm_finish_geom(g);
   g.epi_scale = scale_shift; g.epi_shift = scale_shift + d->out_c; g.epi_relu = relu ? 1 : 0;
+  if (dtype == CREID_BF16X3) return launch_igemm_x3(g, x, w_krsc, y, residual, nullptr, as_stream(stream));
   return launch_igemm(g, x, w_krsc, y, residual, nullptr, dtype, as_stream(stream));
 }
 
@@ -1528,6 +1531,7 @@ int creid_conv2d_dgrad_fused_nhwc(const creid_conv_desc* d, const void* dy, cons
                                   int wred_accumulate, const void* wred_ws, size_t wred_ws_bytes, int dtype, void* stream) {
   int rc = check_desc(d);
   if (rc) return rc;
+  if (!creid_is_storage(dtype)) return CREID_E_DTYPE;     // (before the piggy-backed weight-gradient reduction is planned)
   CREID_CHECK_ARG(dy && w_crsk && dx && bn_stat_image_rows >= 0);
   if (bn_x) CREID_CHECK_ARG(bn_mean && bn_invstd && bn_partial);
   if (bn_stat_image_rows % 128 != 0) return CREID_E_SHAPE;

@@ -955,6 +955,7 @@ int creid_bn2d_bwd_finalize_wred(const float* bn_partial, int64_t bn_rows, int64
                                  const void* wred_ws, size_t wred_ws_bytes, int dtype, void* stream) {
   CREID_CHECK_ARG(bn_partial && bn_mean && bn_invstd && bn_sums && bn_rows > 0 && bn_C > 0 && bn_count > 0 && wred_desc &&
                   wred_dw && wred_ws);
+  if (!creid_is_storage(dtype)) return CREID_E_DTYPE;
   BnBwdFinJob fin{bn_partial, (int)bn_rows, (int)bn_C, (float)(1.0 / (double)bn_count), bn_mean, bn_invstd, bn_gamma, bn_sums,
                   bn_dgamma, bn_dbeta, 0, 16};
   bn_bwd_fin_shape(fin);
@@ -973,6 +974,7 @@ int creid_bn2d_bwd_finalize_wred(const float* bn_partial, int64_t bn_rows, int64
 int creid_conv2d_wgrad_reduce_job(const creid_conv_desc* d, float* dw_oihw, int accumulate, const void* ws, size_t ws_bytes,
                                   int dtype, void* stream) {
   CREID_CHECK_ARG(d && dw_oihw && ws);
+  if (!creid_is_storage(dtype)) return CREID_E_DTYPE;
   WRedJob j{};
   if (!wgrad_make_reduce_job(d, dtype, ws, ws_bytes, dw_oihw, accumulate, j))
     return creid_conv2d_wgrad_reduce(d, dw_oihw, accumulate, ws, ws_bytes, dtype, stream);

@@ -1023,6 +1023,50 @@ __global__ __launch_bounds__(256) void weight_prep_multi_kernel(const WPrepEntry
   }
 }
 
+// CREID_BF16X3 weights (conv_x3.hip): OIHW fp32 -> two bf16 planes of [O][r][s][I], hi = bf16(w) then lo = bf16(w - hi)
+__device__ __forceinline__ void x3_split_bits(float v, unsigned short* hi, unsigned short* lo) {
+  const unsigned short h = f32_to_bf16_bits(v);
+  *hi = h;
+  *lo = f32_to_bf16_bits(v - bf16_bits_to_f32(h));
+}
+__global__ __launch_bounds__(256) void weight_prep_x3_kernel(const float* __restrict__ w, int O, int I, int kh, int kw,
+                                                             unsigned short* __restrict__ w2) {
+  const int64_t total = (int64_t)O * I * kh * kw;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int c = (int)(i % I);
+    int64_t t = i / I;
+    const int s = (int)(t % kw); t /= kw;
+    const int r = (int)(t % kh);
+    const int o = (int)(t / kh);
+    x3_split_bits(w[(((int64_t)o * I + c) * kh + r) * kw + s], w2 + i, w2 + total + i);
+  }
+}
+// the descriptor-table form: one workgroup per (entry, 32 x 32 (o, c) tile), every tap; crsk is not written
+__global__ __launch_bounds__(256) void weight_prep_multi_x3_kernel(const WPrepEntry* __restrict__ tab, int n_ent,
+                                                                   const int* __restrict__ tile_start) {
+  int lo = 0, hi = n_ent - 1;
+  const int bid = blockIdx.x;
+  while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (tile_start[mid] <= bid) lo = mid; else hi = mid - 1; }
+  const WPrepEntry e = tab[lo];
+  const int tiles_c = (e.I + 31) / 32;
+  const int tix = bid - tile_start[lo];
+  const int o0 = (tix / tiles_c) * 32, c0 = (tix % tiles_c) * 32;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;       // 32 x 8
+  const int taps = e.kh * e.kw;
+  const int64_t plane = (int64_t)e.O * taps * e.I;
+  unsigned short* out = reinterpret_cast<unsigned short*>(e.krsc);
+  for (int tap = 0; tap < taps; ++tap) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int o = o0 + ty + 8 * k, c = c0 + tx;
+      if (o < e.O && c < e.I) {
+        const int64_t d = ((int64_t)o * taps + tap) * e.I + c;
+        x3_split_bits(e.w[((int64_t)o * e.I + c) * taps + tap], out + d, out + plane + d);
+      }
+    }
+  }
+}
+
 // stem: OIHW [64,3,7,7] -> [64][8][32] with k = r*32 + s*4 + c (zero padded)
 template <typename T>
 __global__ __launch_bounds__(256) void stem_weight_prep_kernel(const float* __restrict__ w, T* __restrict__ out) {
@@ -1394,6 +1438,12 @@ int creid_weight_prep(const float* w_oihw, int64_t O, int64_t I, int64_t kh, int
   CREID_CHECK_ARG(w_oihw && w_krsc && O > 0 && I > 0 && kh > 0 && kw > 0);
   hipStream_t s = as_stream(stream);
   const int64_t total = O * I * kh * kw;
+  if (dtype == CREID_BF16X3) {
+    CREID_CHECK_ARG(!w_crsk);                                   // forward-only mode: no data-gradient copy
+    hipLaunchKernelGGL(weight_prep_x3_kernel, dim3(ew_blocks(total, 1)), dim3(256), 0, s, w_oihw, (int)O, (int)I, (int)kh,
+                       (int)kw, (unsigned short*)w_krsc);
+    CREID_LAUNCH_RET();
+  }
   DISPATCH_T(dtype,
              hipLaunchKernelGGL(weight_prep_kernel<float>, dim3(ew_blocks(total, 1)), dim3(256), 0, s, w_oihw, (int)O, (int)I,
                                 (int)kh, (int)kw, (float*)w_krsc, (float*)w_crsk),
@@ -1410,6 +1460,11 @@ int creid_weight_prep_multi(const void* table_dev, const int32_t* tile_start_dev
                             int dtype, void* stream) {
   CREID_CHECK_ARG(table_dev && tile_start_dev && n_entries > 0 && total_tiles > 0);
   hipStream_t s = as_stream(stream);
+  if (dtype == CREID_BF16X3) {
+    hipLaunchKernelGGL(weight_prep_multi_x3_kernel, dim3((unsigned)total_tiles), dim3(256), 0, s, (const WPrepEntry*)table_dev,
+                       (int)n_entries, tile_start_dev);
+    CREID_LAUNCH_RET();
+  }
   DISPATCH_T(dtype,
              hipLaunchKernelGGL(weight_prep_multi_kernel<float>, dim3((unsigned)total_tiles), dim3(256), 0, s,
                                 (const WPrepEntry*)table_dev, (int)n_entries, tile_start_dev),

@@ -33,7 +33,7 @@ def _inference(model, batch, use_cuda=True, normalize_with_bn=True, transform=No
                 transform = transform()                          # built on the first uint8 batch only (run_inference)
             # the device-side transform IS a GPU kernel: a uint8 batch goes to the device whatever `use_cuda` says (the flag only
             # keeps the reference's meaning for float batches, which a CPU-resident model could not run here anyway)
-            data = transform(data.cuda(), layout="stem", dtype=model.backbone.engine.dtype)
+            data = transform(data.cuda(), layout="stem", dtype=model.backbone.engine_for(False).dtype)   # (bf16x3: fp32)
         else:
             data = data.cuda() if use_cuda else data
         _, global_feat = model.backbone(data)

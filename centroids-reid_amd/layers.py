@@ -71,6 +71,46 @@ def conv2d_fwd_affine(x, w_krsc, stride, pad, scale_shift, residual=None, relu=T
     return y
 
 
+# ---- bf16x3 (fp32 activations, split bf16 weights, three MFMAs per product; forward only)
+def weight_prep_x3(w_oihw: torch.Tensor):
+    """fp32 OIHW -> bf16 [2, O, kh, kw, I]: hi = bf16(w) plane, then lo = bf16(w - hi) plane."""
+    O, I, kh, kw = w_oihw.shape
+    w2 = torch.empty((2, O, kh, kw, I), dtype=torch.bfloat16, device=w_oihw.device)
+    L.check(L.lib().creid_weight_prep(L.ptr(w_oihw.contiguous()), O, I, kh, kw, L.BF16X3, L.ptr(w2), None, L.stream()),
+            "weight_prep")
+    return w2
+
+
+def conv2d_fwd_x3(x, w2, stride, pad, with_stats=False):
+    """fp32 x [B,H,W,Cin], w2 from weight_prep_x3 -> fp32 y [B,OH,OW,Cout] (+ partial [rows,2,Cout])."""
+    L.require_gpu(x, w2)
+    assert x.dtype == torch.float32 and w2.dtype == torch.bfloat16 and w2.dim() == 5
+    B, H, W, cin = x.shape
+    cout, k = w2.shape[1], w2.shape[2]
+    d, oh, ow = conv_desc(B, H, W, cin, cout, k, stride, pad)
+    y = torch.empty((B, oh, ow, cout), dtype=torch.float32, device=x.device)
+    part = None
+    if with_stats:
+        rows = L.lib().creid_conv2d_bn_partial_rows(C.byref(d))
+        part = torch.empty((rows, 2, cout), dtype=torch.float32, device=x.device)
+    L.check(L.lib().creid_conv2d_fwd_nhwc(C.byref(d), L.ptr(x), L.ptr(w2), L.ptr(y), L.ptr(part), L.BF16X3, L.stream()),
+            "conv2d_fwd")
+    return (y, part) if with_stats else y
+
+
+def conv2d_fwd_affine_x3(x, w2, stride, pad, scale_shift, residual=None, relu=True):
+    """bf16x3 eval-mode conv -> BatchNorm(scale_shift [2, Cout]) -> (+fp32 residual) -> (ReLU) in one launch."""
+    L.require_gpu(x, w2, scale_shift, residual)
+    assert x.dtype == torch.float32 and w2.dtype == torch.bfloat16 and w2.dim() == 5
+    B, H, W, cin = x.shape
+    cout, k = w2.shape[1], w2.shape[2]
+    d, oh, ow = conv_desc(B, H, W, cin, cout, k, stride, pad)
+    y = torch.empty((B, oh, ow, cout), dtype=torch.float32, device=x.device)
+    L.check(L.lib().creid_conv2d_fwd_affine_nhwc(C.byref(d), L.ptr(x), L.ptr(w2), L.ptr(y), L.ptr(scale_shift),
+                                                 L.ptr(residual), 1 if relu else 0, L.BF16X3, L.stream()), "conv2d_fwd_affine")
+    return y
+
+
 def conv2d_dgrad(dy, w_crsk, in_hw, stride, pad, add_src=None):
     L.require_gpu(dy, w_crsk)
     B, oh, ow, cout = dy.shape

@@ -31,7 +31,12 @@ extern "C" {
 
 #define CREID_ABI_VERSION 1
 
-enum { CREID_F32 = 0, CREID_BF16 = 1, CREID_F16 = 2 };
+/* CREID_BF16X3 is a convolution mode, not a storage type: fp32 activations in and out, weights pre-split into two bf16 planes
+ * (hi = bf16(w), lo = bf16(w - hi)), and every product expanded into three bf16 MFMAs (lo*hi + hi*lo + hi*hi, fp32
+ * accumulation) -- fp32-grade results from the bf16 matrix pipe, for the eval-mode forward.  It is accepted ONLY by
+ * creid_conv2d_fwd_nhwc, creid_conv2d_fwd_affine_nhwc, creid_weight_prep and creid_weight_prep_multi; every other entry point
+ * that takes a dtype returns CREID_E_DTYPE for it (the rest of the eval forward runs with CREID_F32 on the fp32 activations). */
+enum { CREID_F32 = 0, CREID_BF16 = 1, CREID_F16 = 2, CREID_BF16X3 = 3 };
 enum { CREID_E_ARG = -1, CREID_E_DTYPE = -2, CREID_E_WS = -3, CREID_E_SHAPE = -4 };
 
 int creid_abi_version(void);
@@ -434,7 +439,10 @@ int creid_conv2d_fwd_nhwc(const creid_conv_desc* d, const void* x, const void* w
  * beta - mean * scale} (creid_bn2d_fold_multi), applied to the fp32 accumulators in the epilogue:
  * y = act(conv(x) * scale + shift (+ residual)), act = ReLU when relu != 0; residual (nullable) has y's shape and dtype.
  * Same arithmetic as creid_conv2d_fwd_nhwc + creid_bn2d_finalize(training = 0) + creid_bn2d_apply, without the two extra
- * passes (fp32 mode: bit-identical; bf16 mode: the conv output is rounded once, after the affine, instead of twice). */
+ * passes (fp32 mode: bit-identical; bf16 mode: the conv output is rounded once, after the affine, instead of twice).
+ * dtype CREID_BF16X3 (this call and creid_conv2d_fwd_nhwc, bn_partial included): x, y and residual fp32, w_krsc the two-plane
+ * bf16 buffer [2][out_c][kh][kw][in_c] of creid_weight_prep; the k order of every output element is fixed by the shape alone
+ * (identical bits whatever the batch size). */
 int creid_conv2d_fwd_affine_nhwc(const creid_conv_desc* d, const void* x, const void* w_krsc, void* y,
                                  const float* scale_shift, const void* residual, int relu, int dtype, void* stream);
 /* Training forward of a 1 x 1 stride-1 convolution whose INPUT is still the raw output of the previous convolution: that layer's
@@ -558,7 +566,9 @@ int creid_image_to_nhwc4_pad(const float* x_nchw, int64_t B, int64_t H, int64_t 
 int creid_augment_u8(const uint8_t* src_hwc, const int32_t* params, int64_t B, int64_t H, int64_t W, int64_t pad,
                      float mean0, float mean1, float mean2, float std0, float std1, float std2, float erase0, float erase1,
                      float erase2, int32_t layout, int32_t dtype, void* out, void* stream);
-/* fp32 OIHW master weights -> compute-dtype [O][r][s][I] (forward) and [I][r][s][O] (dgrad, nullable). */
+/* fp32 OIHW master weights -> compute-dtype [O][r][s][I] (forward) and [I][r][s][O] (dgrad, nullable).
+ * CREID_BF16X3: w_krsc = bf16 [2][O][r][s][I], hi plane then lo plane; w_crsk must be NULL (no data gradient in that mode),
+ * else CREID_E_ARG.  creid_weight_prep_multi with CREID_BF16X3 writes the same two planes and ignores the crsk fields. */
 int creid_weight_prep(const float* w_oihw, int64_t O, int64_t I, int64_t kh, int64_t kw, int dtype,
                       void* w_krsc, void* w_crsk, void* stream);
 int creid_stem_weight_prep(const float* w_oihw, int dtype, void* w_stem, void* stream);
