@@ -16,9 +16,10 @@ LIB_PATH = os.environ.get("CREID_LIB_PATH") or os.path.join(_HERE, "lib", "libcr
 F32, BF16, F16 = 0, 1, 2
 _DT = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
 # convolution mode, not a storage type (include/creid.h): fp32 activations, weights split into two bf16 planes, three bf16 MFMAs
-# per product; accepted by the forward convolutions and the weight preparation only
+# per product; accepted by the forward convolutions and the weight preparation (training: the *_x3 entry points)
 BF16X3 = 3
 EVAL_PRECISIONS = ("bf16x3",)
+TRAIN_PRECISIONS = ("bf16x3",)       # string compute modes Baseline / ModelBase / CTLModel(compute_dtype=...) train in
 
 _lib = None
 
@@ -103,6 +104,11 @@ SIGNATURES = {
     "creid_conv2d_wgrad_reduce": (C.c_int, [_p, _p, C.c_int, _p, _sz, C.c_int, _p]),
     "creid_bn2d_bwd_finalize_wred": (C.c_int, [_p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, C.c_int, _p, _sz, C.c_int, _p]),
     "creid_conv2d_wgrad_reduce_job": (C.c_int, [_p, _p, C.c_int, _p, _sz, C.c_int, _p]),
+    "creid_conv2d_dgrad_x3_nhwc": (C.c_int, [_p, _p, _p, _p, _p, _p]),
+    "creid_conv2d_wgrad_x3_workspace_bytes": (_sz, [_p]),
+    "creid_conv2d_wgrad_x3_nhwc": (C.c_int, [_p, _p, _p, _p, C.c_int, _p, _sz, _p]),
+    "creid_conv2d_wgrad_x3_partials": (C.c_int, [_p, _p, _p, _p, _sz, _p]),
+    "creid_weight_prep_x3_train_multi": (C.c_int, [_p, _p, _i64, _i64, _p]),
     "creid_stem_conv_fwd": (C.c_int, [_i64, _i64, _i64, _p, _p, _p, _p, C.c_int, _p]),
     "creid_stem_conv_wgrad_workspace_bytes": (_sz, [_i64, _i64, _i64, C.c_int]),
     "creid_stem_conv_wgrad": (C.c_int, [_i64, _i64, _i64, _p, _p, _p, C.c_int, _p, _sz, C.c_int, _p]),

@@ -250,14 +250,22 @@ class BackboneEngine:
 
     dtype: a torch dtype (the activation and MFMA input type), or the string "bf16x3" -- the eval-mode forward with fp32
     activations whose convolutions run three bf16 MFMAs per product on split operands (fp32-grade embeddings on the bf16 matrix
-    pipe, csrc/conv_x3.hip).  That mode has no training forward / backward."""
+    pipe, csrc/conv_x3.hip).  By default that mode has no training forward / backward; trainable=True adds them: the fp32
+    engine's training schedule with the forward, data-gradient and weight-gradient launches of the 52 non-stem convolutions
+    on the bf16x3 entry points (every activation, BatchNorm, IBN and the stem stay exact fp32)."""
 
-    def __init__(self, net: ResNet, dtype=torch.bfloat16):
+    def __init__(self, net: ResNet, dtype=torch.bfloat16, trainable=False):
         self.net = net
         self.mode = dtype if isinstance(dtype, str) else None
         if self.mode is not None and self.mode not in L.EVAL_PRECISIONS:
             raise ValueError(f"unknown compute mode {dtype!r} (a torch dtype or one of {L.EVAL_PRECISIONS})")
         self.x3 = self.mode == "bf16x3"
+        if trainable and not self.x3:
+            raise ValueError("trainable=True selects the training form of a string compute mode; torch dtypes always train")
+        self.x3_train = self.x3 and trainable
+        if self.x3_train and isinstance(net.layer1[0], BasicBlock):
+            raise L.CreidError(f"compute mode bf16x3 trains the Bottleneck networks only ({getattr(net, 'arch', 'resnet18/34')} is a "
+                               "BasicBlock network): train it with bfloat16, float16 or float32")
         if self.x3:
             dtype = torch.float32          # activations and every non-convolution launch stay fp32
         self.dtype = dtype
@@ -298,8 +306,12 @@ class BackboneEngine:
         self._ws2 = [None, None]
         # weight-gradient split reductions ride in the first workgroups of the NEXT data-gradient launch
         # (creid_conv2d_dgrad_fused_nhwc) instead of 53 stand-alone 5-25 us launches; CREID_WRED_PIGGYBACK=0: round-1 path
+        if self.x3_train:
+            # bf16x3 weight gradients: partial tiles + the fp32 split reduction in one call (creid_conv2d_wgrad_x3_nhwc), on the
+            # main stream -- the carried and side-stream reduction forms are fp32 / 16-bit schedules
+            self.wgrad_stream = self.reduce_stream = False
         self.wred_piggyback = os.environ.get("CREID_WRED_PIGGYBACK", "1") == "1" and not self.wgrad_stream \
-            and not self.reduce_stream
+            and not self.reduce_stream and not self.x3_train
         # BatchNorm-backward finalizes ride in the first workgroups of a weight-gradient launch issued between the data
         # gradient that produced their column sums and the apply that needs them (CREID_BNFIN_PIGGYBACK=0: own launches)
         # CREID_FIN_CARRIER: "wgrad" (above) | "wred" (finalize and the pending split reduction share one launch between the data
@@ -424,7 +436,9 @@ class BackboneEngine:
         units = [u for u in self.all_units() if u is not self.stem]
         for u in units:
             if u.w_krsc is None and self.x3:
-                u.w_krsc = self._empty(2, u.cout, u.k, u.k, u.cin, dtype=torch.bfloat16)   # hi plane, lo plane; no dgrad copy
+                u.w_krsc = self._empty(2, u.cout, u.k, u.k, u.cin, dtype=torch.bfloat16)   # hi plane, lo plane
+                if self.x3_train:                                                          # the data gradient's copy
+                    u.w_crsk = self._empty(2, u.cin, u.k, u.k, u.cout, dtype=torch.bfloat16)
             elif u.w_krsc is None:
                 u.w_krsc = self._empty(u.cout, u.k, u.k, u.cin)
                 u.w_crsk = self._empty(u.cin, u.k, u.k, u.cout)
@@ -448,17 +462,22 @@ class BackboneEngine:
             self._wprep_key = key
         L.check(lib.creid_stem_weight_prep(L.ptr(self.stem.conv.weight), self.dt, L.ptr(self.stem.w_krsc), st),
                 "stem_weight_prep")
+        def multi(stream):
+            if self.x3_train:              # both two-plane copies (forward and data gradient) in one launch
+                L.check(lib.creid_weight_prep_x3_train_multi(L.ptr(self._wprep_tab), L.ptr(self._wprep_tiles), len(units),
+                                                             self._wprep_total, stream), "weight_prep_x3_train_multi")
+            else:
+                L.check(lib.creid_weight_prep_multi(L.ptr(self._wprep_tab), L.ptr(self._wprep_tiles), len(units), self._wprep_total,
+                                                    self.conv_dt, stream), "weight_prep_multi")
         if side:
             # the 52 non-stem copies (~50 us at ResNet50 size) are needed by layer1 only: inside a captured graph they run as a
             # parallel branch beside the stem (image layout pass, 7 x 7 convolution, BatchNorm, max-pool: ~95 us that depend on the
             # stem copy alone); forward() joins the branch in front of the first bottleneck.  One fork / join costs ~6 us of graph
             # signalling (tools/probes/anyorder_probe.hip) against ~45 us hidden.
             with self._fork_side():
-                L.check(lib.creid_weight_prep_multi(L.ptr(self._wprep_tab), L.ptr(self._wprep_tiles), len(units), self._wprep_total,
-                                                    self.conv_dt, L.stream()), "weight_prep_multi")
+                multi(L.stream())
         else:
-            L.check(lib.creid_weight_prep_multi(L.ptr(self._wprep_tab), L.ptr(self._wprep_tiles), len(units), self._wprep_total,
-                                                self.conv_dt, st), "weight_prep_multi")
+            multi(st)
         self.weights_dirty = False
         self._wsig = self._weight_signature()
         return side
@@ -736,9 +755,10 @@ class BackboneEngine:
             assert x_nchw.dtype == torch.float32 and x_nchw.dim() == 4 and x_nchw.shape[1] == 3
         else:
             L.require_gpu(x_nchw.xpad)
-        if training and self.x3:
+        if training and self.x3 and not self.x3_train:
             raise L.CreidError("compute mode bf16x3 is an eval-mode forward only (validation / inference): train with bfloat16, "
-                               "float16 or float32 and pass eval_precision='bf16x3' to Baseline / CTLModel")
+                               "float16 or float32 and pass eval_precision='bf16x3' to Baseline / CTLModel, or train in the mode "
+                               "with compute_dtype='bf16x3' (BackboneEngine(net, 'bf16x3', trainable=True))")
         wprep_pending = False
         if self.weights_dirty or self._wsig != self._weight_signature():
             # training steps replayed from a hipGraph re-derive the 16-bit weight copies every step (the optimiser has just rewritten
@@ -910,6 +930,12 @@ class BackboneEngine:
     def _wgrad_launch(self, u, a_in, dy, B, H, W, fin=None):
         lib, st = L.lib(), L.stream()
         d, _, _ = _desc(B, H, W, u.cin, u.cout, u.k, u.stride, u.pad)
+        if self.x3_train:
+            nbytes = lib.creid_conv2d_wgrad_x3_workspace_bytes(C.byref(d))
+            ws = self._workspace(nbytes)
+            L.check(lib.creid_conv2d_wgrad_x3_nhwc(C.byref(d), L.ptr(a_in), L.ptr(dy), L.ptr(self._grad_of(u.conv.weight)), 1,
+                                                   L.ptr(ws), nbytes, st), "conv2d_wgrad_x3")
+            return
         nbytes = lib.creid_conv2d_wgrad_workspace_bytes(C.byref(d), self.dt)
         gw = self._grad_of(u.conv.weight)
         if self.wred_piggyback:
@@ -968,6 +994,11 @@ class BackboneEngine:
         d, _, _ = _desc(B, H, W, u.cin, u.cout, u.k, u.stride, u.pad)
         M = B * H * W
         dx = self._empty(M, u.cin)
+        if self.x3_train:                  # (the fp32 schedule: no fused BatchNorm reduction, no mask, stride-1 add_src)
+            assert add_src_stride == 1 and add_mask is None
+            L.check(lib.creid_conv2d_dgrad_x3_nhwc(C.byref(d), L.ptr(dy), L.ptr(u.w_crsk), L.ptr(dx), L.ptr(add_src), st),
+                    "conv2d_dgrad_x3")
+            return dx, None
         fuse_bn = bnred is not None and self.fuse_bn_reduce
         carry = len(self._wred_pending) >= (2 if self.fin_with_wred else 1)     # "wred" mode keeps one job for the finalize launch
         if carry or fuse_bn or add_mask is not None:

@@ -6,7 +6,8 @@ activation / MFMA input type: torch.bfloat16 (throughput mode; the reference's A
 cfg.USE_MIXED_PRECISION) or torch.float32 (parity mode, exact-f32 MFMA).  `eval_precision="bf16x3"` runs the eval-mode forward
 (validation, inference) on a second engine over the same fp32 master weights: fp32 activations, convolutions as three bf16
 MFMAs per product on split operands -- fp32-grade embeddings at several times the fp32 mode's rate; training keeps
-`compute_dtype`."""
+`compute_dtype`.  `compute_dtype="bf16x3"` trains in that mode too: the fp32 mode's schedule with every non-stem convolution
+(forward, data gradient, weight gradient) on the split-operand bf16 path; its eval-mode forward is the bf16x3 one."""
 from __future__ import annotations
 
 import torch
@@ -33,6 +34,8 @@ class Baseline(nn.Module):
             self.base.load_param(cfg.MODEL.PRETRAIN_PATH)      # modelling/baseline.py:84-87
             print("Loading pretrained ImageNet model......")
         self.compute_dtype = compute_dtype or (torch.bfloat16 if cfg.USE_MIXED_PRECISION else torch.float32)
+        if isinstance(self.compute_dtype, str) and self.compute_dtype not in L.TRAIN_PRECISIONS:
+            raise ValueError(f"compute_dtype must be a torch dtype or one of {L.TRAIN_PRECISIONS}, got {self.compute_dtype!r}")
         # base_out = the reference's NCHW fp32 feature map (modelling/baseline.py:91-96).  A stand-alone Baseline returns it like the
         # reference does; ModelBase / CTLModel, which never consume it (`_, features = self.backbone(x)`, modelling/bases.py:171,
         # train_ctl_model.py:44), switch it off and save the 67 MB layout pass per batch.  It is a detached copy: gradients flow
@@ -45,16 +48,25 @@ class Baseline(nn.Module):
         self._eval_engine = None
         self.loss_scaler = None           # f16 training: solver.LossScaler (ModelBase.configure_optimizers attaches it)
 
+    def _engine_matches(self, eng):
+        cd = self.compute_dtype
+        if isinstance(cd, str):           # a string mode's engine computes in fp32: match on the mode, not on .dtype
+            return eng.mode == cd and eng.x3_train
+        return eng.mode is None and eng.dtype == cd
+
     @property
     def engine(self):
-        if self._engine is None or self._engine.dtype != self.compute_dtype:
-            self._engine = bb.BackboneEngine(self.base, self.compute_dtype)
+        if self._engine is None or not self._engine_matches(self._engine):
+            if isinstance(self.compute_dtype, str):
+                self._engine = bb.BackboneEngine(self.base, self.compute_dtype, trainable=True)
+            else:
+                self._engine = bb.BackboneEngine(self.base, self.compute_dtype)
         self._engine.loss_scaler = self.loss_scaler
         return self._engine
 
     def engine_for(self, training: bool):
         """The engine a forward in this mode runs on: the eval_precision engine for eval-mode forwards when one is set."""
-        if training or self.eval_precision is None:
+        if training or self.eval_precision is None or self.eval_precision == self.compute_dtype:
             return self.engine
         if self._eval_engine is None or self._eval_engine.mode != self.eval_precision:
             self._eval_engine = bb.BackboneEngine(self.base, self.eval_precision)

@@ -46,10 +46,15 @@ struct IGemmGeom {
 #define CREID_ABL_ON(word, bits) 0
 #endif
 
-// bf16x3 forward convolution (conv_x3.hip): fp32 source / output, two-plane bf16 weights [2][N][K]; returns CREID_E_SHAPE for a
-// geometry it does not cover (data gradient, the pre-padded stem image)
+// bf16x3 convolution (conv_x3.hip): fp32 source / output, two-plane bf16 weights [2][N][K]; forward or data gradient
+// (g.transposed), epilogue "+ add_src" at full resolution; returns CREID_E_SHAPE for a geometry it does not cover (the
+// pre-padded stem image, compact or masked add_src, parity-ordered rows)
 int launch_igemm_x3(const IGemmGeom& g, const void* src, const void* wgt, void* out, const void* add_src, float* bn_part,
                     hipStream_t s);
+
+// the descriptor checks of every convolution entry point (conv_igemm.hip): CREID_E_ARG for a null or non-positive descriptor,
+// CREID_E_SHAPE for a geometry outside the kernels' cover, 0 otherwise
+int conv_check_desc(const creid_conv_desc* d);
 
 static inline void igemm_finish_geom(IGemmGeom& g) {
   g.inv_ohow = 1.0f / (float)(g.OH * g.OW);

@@ -1439,6 +1439,8 @@ static int check_desc(const creid_conv_desc* d) {
   return 0;
 }
 
+int conv_check_desc(const creid_conv_desc* d) { return check_desc(d); }
+
 extern "C" {
 
 int64_t creid_conv2d_bn_partial_rows(const creid_conv_desc* d) {
@@ -1491,6 +1493,21 @@ int creid_conv2d_dgrad_nhwc(const creid_conv_desc* d, const void* dy, const void
   g.K = (int)(d->kh * d->kw * d->out_c); g.N = (int)d->in_c; g.check_bounds = 1;
   igemm_finish_geom(g);
   return launch_igemm(g, dy, w_crsk, dx, add_src, nullptr, dtype, as_stream(stream));
+}
+
+/* bf16x3 data gradient (conv_x3.hip): fp32 dy / dx / add_src, w2_crsk = the two-plane transposed copy. */
+int creid_conv2d_dgrad_x3_nhwc(const creid_conv_desc* d, const void* dy, const void* w2_crsk, void* dx, const void* add_src,
+                               void* stream) {
+  int rc = check_desc(d);
+  if (rc) return rc;
+  CREID_CHECK_ARG(dy && w2_crsk && dx);
+  IGemmGeom g;
+  g.M = (int)(d->batch * d->in_h * d->in_w); g.OH = (int)d->in_h; g.OW = (int)d->in_w;
+  g.SH = (int)d->out_h; g.SW = (int)d->out_w; g.pitch = (int)d->out_c; g.log2span = ilog2_exact(d->out_c);
+  g.kw = d->kw; g.stride = d->stride; g.pad = d->pad; g.transposed = 1;
+  g.K = (int)(d->kh * d->kw * d->out_c); g.N = (int)d->in_c; g.check_bounds = 1;
+  igemm_finish_geom(g);
+  return launch_igemm_x3(g, dy, w2_crsk, dx, add_src, nullptr, as_stream(stream));
 }
 
 /* dgrad with the NEXT BatchNorm-backward's column reduction fused into the epilogue (bf16 only). */

@@ -607,6 +607,144 @@ __global__ __launch_bounds__(256) void wgrad_f32_kernel(IGemmGeom g, const float
       }
 }
 
+// ------------------------------------------------------------------------------------ bf16x3
+// fp32-grade weight gradient on the bf16 matrix pipe (CREID_BF16X3, see conv_x3.hip).  Both fp32 operands are split into
+// (hi, lo) bf16 planes while a 32-pixel k-tile is written to LDS pixel-major -- the layout of wgrad_bf16_kernel, so the
+// fragments (8 consecutive pixels of one channel per lane) come out of the same transposing reads -- and every product is
+// lo*hi + hi*lo + hi*hi with fp32 accumulation.  Grid, pixel splits and the [split][NCO][K] fp32 partial tiles are exactly
+// those of wgrad_f32_kernel under plan_wgrad(..., CREID_F32): the CREID_F32 reduce paths sum them.  The k order of every
+// partial is fixed by the shape (pixel order inside one split, then the three terms), so results are deterministic.
+constexpr int WKX = 32;   // pixels per k-step (bf16x3)
+
+template <int TM, int TN>
+__global__ __launch_bounds__(256) void wgrad_x3_kernel(IGemmGeom g, const float* __restrict__ dy, const float* __restrict__ x,
+                                                       int NCO, float* __restrict__ ws, int tiles_k, int m_per_split) {
+  constexpr int PA = TM + 32, PB = TN + 32;                 // LDS row pitches (elements), as wgrad_bf16_kernel
+  constexpr int IM = TM / 64, JN = TN / 64;                 // MFMA tiles per wave
+  constexpr int CA = TM / 4, CB = TN / 4;                   // float4 chunks per row
+  constexpr int RA = 256 / CA, RB = 256 / CB;               // rows per load pass
+  constexpr int NA = WKX / RA, NBL = WKX / RB;              // load passes
+  // [pixel][channel] bf16, hi and lo planes of both operands
+  __shared__ __attribute__((aligned(16))) unsigned short Ah[WKX * PA], Al[WKX * PA], Bh[WKX * PB], Bl[WKX * PB];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int tile = blockIdx.x, split = blockIdx.y;
+  const int tile_co = tile / tiles_k, tile_k = tile - tile_co * tiles_k;
+  const int co0 = tile_co * TM, k0 = tile_k * TN;
+  const int m_begin = split * m_per_split, m_end = min(g.M, m_begin + m_per_split);
+  const int span_mask = (1 << g.log2span) - 1;
+  const int a_ch = tid % CA, a_row = tid / CA;
+  const int b_ch = tid % CB, b_row = tid / CB;
+  const int kcol = k0 + 4 * b_ch;                           // a 4-channel chunk never straddles two taps (span >= 64)
+  const int tap = kcol >> g.log2span, cc = kcol & span_mask;
+  const int tr = tap / g.kw, ts = tap - tr * g.kw;
+  float4 ra[NA], rb[NBL];
+  auto gload = [&](int mb) {                                // rows past the split or outside the image stage zeros
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+      const int m = mb + a_row + RA * i;
+      ra[i] = (m < m_end) ? *reinterpret_cast<const float4*>(dy + (int64_t)m * NCO + co0 + 4 * a_ch) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int i = 0; i < NBL; ++i) {
+      const int m = mb + b_row + RB * i;
+      rb[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (m < m_end) {
+        int b, rem, oy, ox, iy, ix;
+        fast_divmod(m, g.OH * g.OW, g.inv_ohow, b, rem);
+        fast_divmod(rem, g.OW, g.inv_ow, oy, ox);
+        if (igemm_src_pixel(g, oy, ox, tr, ts, iy, ix))
+          rb[i] = *reinterpret_cast<const float4*>(x + (int64_t)((b * g.SH + iy) * g.SW + ix) * g.pitch + cc);
+      }
+    }
+  };
+  auto split4 = [](const float4& v, unsigned short* hp, unsigned short* lp) {
+    const unsigned h0 = f32x2_to_bf16x2_bits(v.x, v.y), h1 = f32x2_to_bf16x2_bits(v.z, v.w);
+    const unsigned l0 = f32x2_to_bf16x2_bits(v.x - __uint_as_float(h0 << 16), v.y - __uint_as_float(h0 & 0xffff0000u));
+    const unsigned l1 = f32x2_to_bf16x2_bits(v.z - __uint_as_float(h1 << 16), v.w - __uint_as_float(h1 & 0xffff0000u));
+    *reinterpret_cast<uint2*>(hp) = make_uint2(h0, h1);
+    *reinterpret_cast<uint2*>(lp) = make_uint2(l0, l1);
+  };
+  auto lstore = [&]() {
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+      const int o = (a_row + RA * i) * PA + 4 * a_ch;
+      split4(ra[i], &Ah[o], &Al[o]);
+    }
+#pragma unroll
+    for (int i = 0; i < NBL; ++i) {
+      const int o = (b_row + RB * i) * PB + 4 * b_ch;
+      split4(rb[i], &Bh[o], &Bl[o]);
+    }
+  };
+  f32x16 acc[IM][JN];
+#pragma unroll
+  for (int i = 0; i < IM; ++i)
+#pragma unroll
+    for (int j = 0; j < JN; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  // transposing-read lane map of wgrad_bf16_kernel
+  const int li = lane & 15;
+  const int t_row = 8 * (lane >> 5) + (li >> 2), t_col = 16 * ((lane >> 4) & 1) + 4 * (li & 3);
+  gload(m_begin);
+  for (int mb = m_begin; mb < m_end; mb += WKX) {
+    __syncthreads();            // previous step's fragment reads are done
+    lstore();
+    __syncthreads();
+    if (mb + WKX < m_end) gload(mb + WKX);
+#pragma unroll
+    for (int kk = 0; kk < WKX / 16; ++kk) {
+      // [fragment 0 | 1] x [pixels 0..3 | 4..7] of each plane
+      s16x4 ah0[2], ah1[2], bh0[2], bh1[2], al0[2], al1[2], bl0[2], bl1[2];
+      const int ao = (kk * 16 + t_row) * PA + wm * (TM / 2) + t_col, bo = (kk * 16 + t_row) * PB + wn * (TN / 2) + t_col;
+      tr_load4<4 * PA * 2>(&Ah[ao], ah0[0], ah1[0], ah0[1], ah1[1]);
+      tr_load4<4 * PB * 2>(&Bh[bo], bh0[0], bh1[0], bh0[1], bh1[1]);
+      tr_load4<4 * PA * 2>(&Al[ao], al0[0], al1[0], al0[1], al1[1]);
+      tr_load4<4 * PB * 2>(&Bl[bo], bl0[0], bl1[0], bl0[1], bl1[1]);
+      tr_wait8(ah0[0], ah1[0], ah0[1], ah1[1], bh0[0], bh1[0], bh0[1], bh1[1]);
+      tr_wait8(al0[0], al1[0], al0[1], al1[1], bl0[0], bl1[0], bl0[1], bl1[1]);
+      __builtin_amdgcn_sched_barrier(0);
+      s16x8 ah[IM], al[IM], bh[JN], bl[JN];
+#pragma unroll
+      for (int i = 0; i < IM; ++i) {
+        ah[i] = __builtin_shufflevector(ah0[i], ah1[i], 0, 1, 2, 3, 4, 5, 6, 7);
+        al[i] = __builtin_shufflevector(al0[i], al1[i], 0, 1, 2, 3, 4, 5, 6, 7);
+      }
+#pragma unroll
+      for (int j = 0; j < JN; ++j) {
+        bh[j] = __builtin_shufflevector(bh0[j], bh1[j], 0, 1, 2, 3, 4, 5, 6, 7);
+        bl[j] = __builtin_shufflevector(bl0[j], bl1[j], 0, 1, 2, 3, 4, 5, 6, 7);
+      }
+      // small terms first, interleaved over the wave's fragments (conv_x3.hip)
+#pragma unroll
+      for (int i = 0; i < IM; ++i)
+#pragma unroll
+        for (int j = 0; j < JN; ++j) acc[i][j] = Bf16T::mfma(al[i], bh[j], acc[i][j]);
+#pragma unroll
+      for (int i = 0; i < IM; ++i)
+#pragma unroll
+        for (int j = 0; j < JN; ++j) acc[i][j] = Bf16T::mfma(ah[i], bl[j], acc[i][j]);
+#pragma unroll
+      for (int i = 0; i < IM; ++i)
+#pragma unroll
+        for (int j = 0; j < JN; ++j) acc[i][j] = Bf16T::mfma(ah[i], bh[j], acc[i][j]);
+    }
+  }
+  const int l31 = lane & 31, kh = lane >> 5;
+  float* wsp = ws + (int64_t)split * NCO * g.K;
+#pragma unroll
+  for (int i = 0; i < IM; ++i)
+#pragma unroll
+    for (int j = 0; j < JN; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int co = co0 + wm * (TM / 2) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
+        const int kc = k0 + wn * (TN / 2) + j * 32 + l31;
+        wsp[(int64_t)co * g.K + kc] = acc[i][j][r];
+      }
+}
+
 // sum over splits and scatter [NCO][K = (tap, within)] -> OIHW fp32 gradient (accumulating).
 // r = tap / kw_taps; s = tap % kw_taps + within / cpitch; c = within % cpitch.
 // Workgroup = (256/SL) float4 element groups x SL split lanes: every thread streams its 16-byte column slice
@@ -994,6 +1132,49 @@ static int conv_wgrad_phases(const creid_conv_desc* d, const void* x, const void
   igemm_finish_geom(g);
   return run_wgrad(g, dy, x, (int)d->out_c, dw_oihw, d->kw, (int)d->in_c, (int)d->in_c, d->kh, d->kw, accumulate, ws,
                    ws_bytes, dtype, as_stream(stream), phases, fin);
+}
+
+// ---- bf16x3: partial tiles by wgrad_x3_kernel in the CREID_F32 workspace layout, summed by the CREID_F32 split reduction
+size_t creid_conv2d_wgrad_x3_workspace_bytes(const creid_conv_desc* d) {
+  if (!d || conv_check_desc(d)) return 0;
+  return creid_conv2d_wgrad_workspace_bytes(d, CREID_F32);
+}
+
+int creid_conv2d_wgrad_x3_partials(const creid_conv_desc* d, const void* x, const void* dy, void* ws, size_t ws_bytes,
+                                   void* stream) {
+  const int rc = conv_check_desc(d);
+  if (rc) return rc;
+  CREID_CHECK_ARG(x && dy && ws);
+  IGemmGeom g;
+  g.M = (int)(d->batch * d->out_h * d->out_w); g.OH = (int)d->out_h; g.OW = (int)d->out_w;
+  g.SH = (int)d->in_h; g.SW = (int)d->in_w; g.pitch = (int)d->in_c; g.log2span = ilog2x(d->in_c);
+  g.kw = d->kw; g.stride = d->stride; g.pad = d->pad; g.transposed = 0;
+  g.K = (int)(d->kh * d->kw * d->in_c); g.N = (int)d->out_c; g.check_bounds = 1;
+  igemm_finish_geom(g);
+  const int NCO = (int)d->out_c;
+  const WgradPlan p = plan_wgrad(g.M, NCO, g.K, CREID_F32, g.stride);
+  if (ws_bytes < (size_t)p.splits * NCO * g.K * sizeof(float)) return CREID_E_WS;
+  const dim3 grid((unsigned)p.tiles, (unsigned)p.splits), block(256);
+  hipStream_t s = as_stream(stream);
+#define CREID_WX3(TM_, TN_)                                                                                          \
+  hipLaunchKernelGGL((wgrad_x3_kernel<TM_, TN_>), grid, block, 0, s, g, (const float*)dy, (const float*)x, NCO, (float*)ws, \
+                     p.tiles_k, p.m_per_split)
+  if (p.tm == 128 && p.tn == 128) CREID_WX3(128, 128);
+  else if (p.tm == 128 && p.tn == 64) CREID_WX3(128, 64);
+  else if (p.tm == 64 && p.tn == 128) CREID_WX3(64, 128);
+  else CREID_WX3(64, 64);
+#undef CREID_WX3
+  CREID_LAUNCH_RET();
+}
+
+int creid_conv2d_wgrad_x3_nhwc(const creid_conv_desc* d, const void* x, const void* dy, float* dw_oihw, int accumulate,
+                               void* ws, size_t ws_bytes, void* stream) {
+  const int rc = conv_check_desc(d);
+  if (rc) return rc;
+  CREID_CHECK_ARG(x && dy && dw_oihw && ws);
+  const int r1 = creid_conv2d_wgrad_x3_partials(d, x, dy, ws, ws_bytes, stream);
+  if (r1) return r1;
+  return creid_conv2d_wgrad_reduce_job(d, dw_oihw, accumulate, ws, ws_bytes, CREID_F32, stream);
 }
 
 size_t creid_stem_conv_wgrad_workspace_bytes(int64_t batch, int64_t H, int64_t W, int dtype) {

@@ -7,7 +7,10 @@
 //
 //   activations  fp32 NHWC in and out (every other kernel of the eval-mode forward keeps its CREID_F32 path);
 //   weights      split once at weight-prep time: [2][O][r][s][I] bf16, the hi plane then the lo plane (creid_weight_prep
-//                with dtype CREID_BF16X3);
+//                with dtype CREID_BF16X3); the data gradient reads the transposed copy [2][I][r][s][O]
+//                (creid_weight_prep_x3_train_multi);
+//   dgrad        the same kernel with the transposed geometry (igemm_src_pixel): source dY, output dX, every tap visited in
+//                the fixed order (absent taps of a stride-2 layer stage zeros), epilogue "+ add_src";
 //   activation   split when the k-tile lands in LDS: one cooperative pass per tile, so a row that feeds both wave columns of
 //                the tile is split once; the LDS image holds the hi and lo planes (the same bytes as the fp32 tile);
 //   k order      the whole reduction of an output element runs in one workgroup, k-step by k-step, and inside a step always
@@ -207,8 +210,9 @@ __global__ __launch_bounds__(256, 2) void igemm_x3_kernel(IGemmGeom g, const flo
 
 int launch_igemm_x3(const IGemmGeom& g, const void* src, const void* wgt, void* out, const void* add_src, float* bn_part,
                     hipStream_t s) {
-  // forward, NHWC source with in_c a power of two >= 64 (check_desc): every k-tile lies inside one tap
-  if (g.transposed || !g.check_bounds || g.log2span < 5 || g.K % X3_BK != 0 || g.N % 64 != 0) return CREID_E_SHAPE;
+  // NHWC source whose channels (in_c forward, out_c data gradient) are a power of two >= 64 (check_desc): every k-tile lies
+  // inside one tap
+  if (!g.check_bounds || g.add_compact || g.add_mask || g.parity || g.log2span < 5 || g.K % X3_BK != 0 || g.N % 64 != 0) return CREID_E_SHAPE;
   const int tiles_m = (g.M + 127) / 128;
   const int bn = (g.N % 128 == 0 && (int64_t)tiles_m * (g.N / 128) >= 512) ? 128 : 64;
   const int tiles_n = g.N / bn;

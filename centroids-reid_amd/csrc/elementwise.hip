@@ -1066,6 +1066,46 @@ __global__ __launch_bounds__(256) void weight_prep_multi_x3_kernel(const WPrepEn
     }
   }
 }
+// the training form: both two-plane copies, krsc [2][O][r][s][I] and crsk [2][I][r][s][O] (the bf16x3 data gradient's
+// operand), per tap through an LDS transpose so each copy leaves coalesced along its innermost index
+__global__ __launch_bounds__(256) void weight_prep_multi_x3_train_kernel(const WPrepEntry* __restrict__ tab, int n_ent,
+                                                                         const int* __restrict__ tile_start) {
+  __shared__ float tl[32][33];
+  int lo = 0, hi = n_ent - 1;
+  const int bid = blockIdx.x;
+  while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (tile_start[mid] <= bid) lo = mid; else hi = mid - 1; }
+  const WPrepEntry e = tab[lo];
+  const int tiles_c = (e.I + 31) / 32;
+  const int tix = bid - tile_start[lo];
+  const int o0 = (tix / tiles_c) * 32, c0 = (tix % tiles_c) * 32;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;       // 32 x 8
+  const int taps = e.kh * e.kw;
+  const int64_t plane = (int64_t)e.O * taps * e.I;
+  unsigned short* krsc = reinterpret_cast<unsigned short*>(e.krsc);
+  unsigned short* crsk = reinterpret_cast<unsigned short*>(e.crsk);
+  for (int tap = 0; tap < taps; ++tap) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int o = o0 + ty + 8 * k, c = c0 + tx;
+      tl[ty + 8 * k][tx] = (o < e.O && c < e.I) ? e.w[((int64_t)o * e.I + c) * taps + tap] : 0.f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int o = o0 + ty + 8 * k, c = c0 + tx;
+      if (o < e.O && c < e.I) {
+        const int64_t d = ((int64_t)o * taps + tap) * e.I + c;
+        x3_split_bits(tl[ty + 8 * k][tx], krsc + d, krsc + plane + d);
+      }
+      const int c2 = c0 + ty + 8 * k, o2 = o0 + tx;
+      if (c2 < e.I && o2 < e.O) {
+        const int64_t d = ((int64_t)c2 * taps + tap) * e.O + o2;
+        x3_split_bits(tl[tx][ty + 8 * k], crsk + d, crsk + plane + d);
+      }
+    }
+    __syncthreads();
+  }
+}
 
 // stem: OIHW [64,3,7,7] -> [64][8][32] with k = r*32 + s*4 + c (zero padded)
 template <typename T>
@@ -1472,6 +1512,14 @@ int creid_weight_prep_multi(const void* table_dev, const int32_t* tile_start_dev
                                 (const WPrepEntry*)table_dev, (int)n_entries, tile_start_dev),
              hipLaunchKernelGGL(weight_prep_multi_kernel<_Float16>, dim3((unsigned)total_tiles), dim3(256), 0, s,
                                 (const WPrepEntry*)table_dev, (int)n_entries, tile_start_dev));
+  CREID_LAUNCH_RET();
+}
+
+int creid_weight_prep_x3_train_multi(const void* table_dev, const int32_t* tile_start_dev, int64_t n_entries,
+                                     int64_t total_tiles, void* stream) {
+  CREID_CHECK_ARG(table_dev && tile_start_dev && n_entries > 0 && total_tiles > 0);
+  hipLaunchKernelGGL(weight_prep_multi_x3_train_kernel, dim3((unsigned)total_tiles), dim3(256), 0, as_stream(stream),
+                     (const WPrepEntry*)table_dev, (int)n_entries, tile_start_dev);
   CREID_LAUNCH_RET();
 }
 

@@ -111,6 +111,65 @@ def conv2d_fwd_affine_x3(x, w2, stride, pad, scale_shift, residual=None, relu=Tr
     return y
 
 
+# ---- bf16x3 training (data gradient, weight gradient, both weight copies)
+def weight_prep_x3_train(w_oihw: torch.Tensor):
+    """fp32 OIHW -> (bf16 [2, O, kh, kw, I], bf16 [2, I, kh, kw, O]): the forward's and the data gradient's two-plane copies,
+    written by one creid_weight_prep_x3_train_multi launch over a one-entry table."""
+    import numpy as np
+    L.require_gpu(w_oihw)
+    w = w_oihw.contiguous()
+    O, I, kh, kw = w.shape
+    krsc = torch.empty((2, O, kh, kw, I), dtype=torch.bfloat16, device=w.device)
+    crsk = torch.empty((2, I, kh, kw, O), dtype=torch.bfloat16, device=w.device)
+    rec = np.zeros(1, dtype=np.dtype([("w", "<u8"), ("krsc", "<u8"), ("crsk", "<u8"), ("O", "<i4"), ("I", "<i4"), ("kh", "<i4"),
+                                      ("kw", "<i4"), ("start", "<i8")]))
+    rec[0] = (w.data_ptr(), krsc.data_ptr(), crsk.data_ptr(), O, I, kh, kw, 0)
+    tab = torch.from_numpy(rec.view(np.uint8).copy()).to(w.device)
+    tiles = ((O + 31) // 32) * ((I + 31) // 32)
+    start = torch.zeros(1, dtype=torch.int32, device=w.device)
+    L.check(L.lib().creid_weight_prep_x3_train_multi(L.ptr(tab), L.ptr(start), 1, tiles, L.stream()), "weight_prep_x3_train_multi")
+    torch.cuda.current_stream().synchronize()            # (tab / start are freed on return)
+    return krsc, crsk
+
+
+def conv2d_dgrad_x3(dy, w2_crsk, in_hw, stride, pad, add_src=None):
+    """fp32 dy [B,OH,OW,Cout], w2_crsk bf16 [2,Cin,k,k,Cout] -> fp32 dx [B,H,W,Cin] (+ fp32 add_src of dx's shape)."""
+    L.require_gpu(dy, w2_crsk, add_src)
+    assert dy.dtype == torch.float32 and w2_crsk.dtype == torch.bfloat16 and w2_crsk.dim() == 5
+    B, oh, ow, cout = dy.shape
+    cin, k = w2_crsk.shape[1], w2_crsk.shape[2]
+    H, W = in_hw
+    d, oh2, ow2 = conv_desc(B, H, W, cin, cout, k, stride, pad)
+    assert (oh2, ow2) == (oh, ow)
+    dx = torch.empty((B, H, W, cin), dtype=torch.float32, device=dy.device)
+    L.check(L.lib().creid_conv2d_dgrad_x3_nhwc(C.byref(d), L.ptr(dy), L.ptr(w2_crsk), L.ptr(dx), L.ptr(add_src), L.stream()),
+            "conv2d_dgrad_x3")
+    return dx
+
+
+def conv2d_wgrad_x3(x, dy, k, stride, pad, dw=None, accumulate=False, partials_only=False):
+    """fp32 x [B,H,W,Cin], dy [B,OH,OW,Cout] -> fp32 OIHW dW (into / onto `dw` when given).  partials_only: returns
+    (workspace, desc) holding the fp32 partial tiles instead -- summed by creid_conv2d_wgrad_reduce_job(..., CREID_F32)."""
+    L.require_gpu(x, dy, dw)
+    assert x.dtype == torch.float32 and dy.dtype == torch.float32
+    B, H, W, cin = x.shape
+    cout = dy.shape[3]
+    d, oh, ow = conv_desc(B, H, W, cin, cout, k, stride, pad)
+    assert tuple(dy.shape) == (B, oh, ow, cout)
+    lib = L.lib()
+    nbytes = lib.creid_conv2d_wgrad_x3_workspace_bytes(C.byref(d))
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x.device)
+    if partials_only:
+        L.check(lib.creid_conv2d_wgrad_x3_partials(C.byref(d), L.ptr(x), L.ptr(dy), L.ptr(ws), nbytes, L.stream()),
+                "conv2d_wgrad_x3_partials")
+        return ws, d
+    if dw is None:
+        dw = torch.zeros((cout, cin, k, k), dtype=torch.float32, device=x.device)
+    L.check(lib.creid_conv2d_wgrad_x3_nhwc(C.byref(d), L.ptr(x), L.ptr(dy), L.ptr(dw), 1 if accumulate else 0, L.ptr(ws), nbytes,
+                                           L.stream()), "conv2d_wgrad_x3")
+    return dw
+
+
 def conv2d_dgrad(dy, w_crsk, in_hw, stride, pad, add_src=None):
     L.require_gpu(dy, w_crsk)
     B, oh, ow, cout = dy.shape

@@ -33,9 +33,11 @@ extern "C" {
 
 /* CREID_BF16X3 is a convolution mode, not a storage type: fp32 activations in and out, weights pre-split into two bf16 planes
  * (hi = bf16(w), lo = bf16(w - hi)), and every product expanded into three bf16 MFMAs (lo*hi + hi*lo + hi*hi, fp32
- * accumulation) -- fp32-grade results from the bf16 matrix pipe, for the eval-mode forward.  It is accepted ONLY by
- * creid_conv2d_fwd_nhwc, creid_conv2d_fwd_affine_nhwc, creid_weight_prep and creid_weight_prep_multi; every other entry point
- * that takes a dtype returns CREID_E_DTYPE for it (the rest of the eval forward runs with CREID_F32 on the fp32 activations). */
+ * accumulation) -- fp32-grade results from the bf16 matrix pipe.  It is accepted ONLY by creid_conv2d_fwd_nhwc,
+ * creid_conv2d_fwd_affine_nhwc, creid_weight_prep and creid_weight_prep_multi; every other entry point that takes a dtype
+ * returns CREID_E_DTYPE for it (the rest of the eval forward runs with CREID_F32 on the fp32 activations).  Training in the mode
+ * uses entry points of its own, which take no dtype: creid_conv2d_dgrad_x3_nhwc, creid_conv2d_wgrad_x3_nhwc / _partials and
+ * creid_weight_prep_x3_train_multi (every other launch of a training step runs with CREID_F32). */
 enum { CREID_F32 = 0, CREID_BF16 = 1, CREID_F16 = 2, CREID_BF16X3 = 3 };
 enum { CREID_E_ARG = -1, CREID_E_DTYPE = -2, CREID_E_WS = -3, CREID_E_SHAPE = -4 };
 
@@ -461,6 +463,14 @@ int creid_bn2d_fold_multi(const void* table_dev, int64_t n_entries, void* stream
 /* data gradient: dx = conv_transpose(dy, w) (+ add_src if non-NULL); w_crsk is [in_c][kh][kw][out_c]. */
 int creid_conv2d_dgrad_nhwc(const creid_conv_desc* d, const void* dy, const void* w_crsk, void* dx,
                             const void* add_src, int dtype, void* stream);
+/* bf16x3 data gradient (CREID_BF16X3 arithmetic, three bf16 MFMAs per product): dx = conv_transpose(dy, w) (+ add_src if
+ * non-NULL).  dy, dx and add_src fp32 NHWC ([batch, out_h, out_w, out_c] in, [batch, in_h, in_w, in_c] out and add_src);
+ * w2_crsk = bf16 [2][in_c][kh][kw][out_c], hi plane then lo plane (creid_weight_prep_x3_train_multi).  The k order of every
+ * element is fixed by the shape (every tap of the kernel, absent taps of a stride-2 layer contributing zeros).
+ * Returns CREID_E_ARG for a null pointer, CREID_E_SHAPE for a descriptor outside the convolution kernels' cover (in_c and
+ * out_c powers of two >= 64, 1 x 1 or 3 x 3, stride 1 or 2), before anything is launched. */
+int creid_conv2d_dgrad_x3_nhwc(const creid_conv_desc* d, const void* dy, const void* w2_crsk, void* dx, const void* add_src,
+                               void* stream);
 /* The same data gradient with the column reduction of the NEXT BatchNorm backward fused into the epilogue
  * (bf16 only): dx is g = dL/da of the layer whose raw conv output is bn_x and post-ReLU activation bn_act
  * (nullable); bn_partial[ceil(M/128)][2][in_c] receives (sum dy, sum dy*xhat), dy = g*[bn_act > 0].
@@ -510,6 +520,21 @@ int creid_bn2d_bwd_finalize_wred(const float* bn_partial, int64_t bn_rows, int64
  * last workgroups): a reduction that finds no carrier gives bit-identical gradients to one that did. */
 int creid_conv2d_wgrad_reduce_job(const creid_conv_desc* d, float* dw_oihw, int accumulate, const void* ws,
                                   size_t ws_bytes, int dtype, void* stream);
+/* bf16x3 weight gradient: dW[o][c][r][s] = sum over pixels of dy * x with both fp32 operands split into (hi, lo) bf16 and
+ * three bf16 MFMAs per product (fp32 accumulation).  x fp32 [batch, in_h, in_w, in_c], dy fp32 [batch, out_h, out_w, out_c].
+ * The partial tiles use exactly the workspace of the fp32 weight gradient: layout [split][out_c][kh*kw*in_c] fp32 with the
+ * split count of creid_conv2d_wgrad_workspace_bytes(d, CREID_F32), which is what creid_conv2d_wgrad_x3_workspace_bytes
+ * returns (0 for a descriptor outside the cover).  creid_conv2d_wgrad_x3_partials writes the partial tiles only; they are
+ * summed with dtype CREID_F32 by creid_conv2d_wgrad_reduce_job (or creid_conv2d_wgrad_reduce, or carried by
+ * creid_bn2d_bwd_finalize_wred / creid_conv2d_dgrad_fused_nhwc with CREID_F32), deterministically.
+ * creid_conv2d_wgrad_x3_nhwc = partials + creid_conv2d_wgrad_reduce_job(CREID_F32): bit-identical to the two-call form.
+ * dw_oihw fp32 OIHW, accumulate as in creid_conv2d_wgrad_nhwc.  Returns CREID_E_ARG for a null pointer, CREID_E_SHAPE for a
+ * descriptor outside the cover, CREID_E_WS for a short workspace -- all before anything is launched. */
+size_t creid_conv2d_wgrad_x3_workspace_bytes(const creid_conv_desc* d);
+int creid_conv2d_wgrad_x3_nhwc(const creid_conv_desc* d, const void* x, const void* dy, float* dw_oihw, int accumulate,
+                               void* ws, size_t ws_bytes, void* stream);
+int creid_conv2d_wgrad_x3_partials(const creid_conv_desc* d, const void* x, const void* dy, void* ws, size_t ws_bytes,
+                                   void* stream);
 /* creid_conv2d_wgrad_partials whose launch also carries a BatchNorm-backward FINALIZE in its first workgroups: the weight
  * gradient is independent of the chain dgrad -> finalize -> apply -> dgrad, so issued between a data gradient and the next
  * BatchNorm's apply it hides that 4-128-workgroup, latency-bound step (bn_*: the arguments creid_bn2d_bwd's finalize
@@ -579,6 +604,12 @@ int creid_stem_weight_prep(const float* w_oihw, int dtype, void* w_stem, void* s
 int64_t creid_weight_prep_entry_bytes(void);
 int creid_weight_prep_multi(const void* table_dev, const int32_t* tile_start_dev, int64_t n_entries,
                             int64_t total_tiles, int dtype, void* stream);
+/* bf16x3 training copies, one launch over the same table (every w_crsk non-NULL): w_krsc = bf16 [2][O][r][s][I] (the forward's
+ * operand, as creid_weight_prep_multi with CREID_BF16X3) and w_crsk = bf16 [2][I][r][s][O] (the data gradient's), each the hi
+ * plane hi = bf16(w) then the lo plane lo = bf16(w - hi), round to nearest even.  CREID_E_ARG for a null pointer or an empty
+ * table. */
+int creid_weight_prep_x3_train_multi(const void* table_dev, const int32_t* tile_start_dev, int64_t n_entries,
+                                     int64_t total_tiles, void* stream);
 
 /* nn.BatchNorm2d (resnet.py:57-62,96,111; momentum 0.1, eps 1e-5) split in three steps:
  * finalize: partial (sum,sumsq) rows -> mean / invstd (+ running-stat update, unbiased variance) when
