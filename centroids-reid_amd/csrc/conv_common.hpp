@@ -56,6 +56,12 @@ int launch_igemm_x3(const IGemmGeom& g, const void* src, const void* wgt, void* 
 // CREID_E_SHAPE for a geometry outside the kernels' cover, 0 otherwise
 int conv_check_desc(const creid_conv_desc* d);
 
+static inline int igemm_ilog2(int64_t v) {      // log2 of a power of two, -1 otherwise
+  int l = 0;
+  while ((1LL << l) < v) ++l;
+  return ((1LL << l) == v) ? l : -1;
+}
+
 static inline void igemm_finish_geom(IGemmGeom& g) {
   g.inv_ohow = 1.0f / (float)(g.OH * g.OW);
   g.inv_ow = 1.0f / (float)g.OW;
@@ -66,6 +72,36 @@ static inline void igemm_finish_geom(IGemmGeom& g) {
   g.epi_shift = nullptr;
   g.epi_relu = 0;
   g.abl = 0;
+}
+
+// Forward convolution of descriptor d: GEMM rows = output pixels, A gathered from the input, K = taps x in_c.
+static inline IGemmGeom fwd_geom(const creid_conv_desc* d) {
+  IGemmGeom g;
+  g.M = (int)(d->batch * d->out_h * d->out_w); g.OH = (int)d->out_h; g.OW = (int)d->out_w;
+  g.SH = (int)d->in_h; g.SW = (int)d->in_w; g.pitch = (int)d->in_c; g.log2span = igemm_ilog2(d->in_c);
+  g.kw = d->kw; g.stride = d->stride; g.pad = d->pad; g.transposed = 0;
+  g.K = (int)(d->kh * d->kw * d->in_c); g.N = (int)d->out_c; g.check_bounds = 1;
+  igemm_finish_geom(g);
+  return g;
+}
+// Its data gradient: GEMM rows = input pixels, A gathered from dY (transposed gather), K = taps x out_c.
+static inline IGemmGeom dgrad_geom(const creid_conv_desc* d) {
+  IGemmGeom g;
+  g.M = (int)(d->batch * d->in_h * d->in_w); g.OH = (int)d->in_h; g.OW = (int)d->in_w;
+  g.SH = (int)d->out_h; g.SW = (int)d->out_w; g.pitch = (int)d->out_c; g.log2span = igemm_ilog2(d->out_c);
+  g.kw = d->kw; g.stride = d->stride; g.pad = d->pad; g.transposed = 1;
+  g.K = (int)(d->kh * d->kw * d->out_c); g.N = (int)d->in_c; g.check_bounds = 1;
+  igemm_finish_geom(g);
+  return g;
+}
+// The stem (7x7 s2 on the pre-padded NHWC4 image [B, H + 8, W + 6, 4]): a "tap" is one kernel row of 8 pixels x 4 channels.
+static inline IGemmGeom stem_geom(int64_t B, int64_t H, int64_t W) {
+  IGemmGeom g;
+  g.M = (int)(B * (H / 2) * (W / 2)); g.OH = (int)(H / 2); g.OW = (int)(W / 2);
+  g.SH = (int)(H + 8); g.SW = (int)(W + 6); g.pitch = 4; g.log2span = 5;
+  g.kw = 1; g.stride = 2; g.pad = 0; g.transposed = 0; g.K = 256; g.N = 64; g.check_bounds = 0;
+  igemm_finish_geom(g);
+  return g;
 }
 
 // Source pixel of output row (oy, ox) under tap (r, s); returns false when it falls outside.
@@ -105,7 +141,6 @@ struct BnRedArgs {
   const float* mean;
   const float* invstd;
   float* partial;
-  int prefetch;          // fetch x / act before the C tile is staged (A/B knob CREID_BNRED_PREFETCH, default 1)
   int tiles_per_image;   // 0: mean/invstd are per channel [N]; > 0: per (image, channel) [B][N] (IBN), this many
                          // 128-row tiles per image
   const unsigned char* mask;   // nullable: ReLU mask as bits (creid_bn2d_apply_mask), one byte per 8 channels; replaces `act`

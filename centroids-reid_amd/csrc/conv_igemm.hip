@@ -4,17 +4,19 @@
 //
 // bf16: 128 x BN x 64 tile (2x2 waves, 64 x BN/2 per wave) on v_mfma_f32_32x32x16_bf16, fp32 accumulate; LDS
 //       row-major [row][64] with the 16-B chunk index XOR-swizzled by (row>>1)&7 (conflict-free ds_read_b128).
-//       Three kernels share that tiling and the epilogue:
-//         igemm_bf16_dma_kernel  global->LDS DMA gather (the A rows come from different image rows / taps),
-//                                NS-stage ring, 256 threads -- the default for every 1x1 / 3x3 layer;
-//         igemm_bf16_ws_kernel   512 threads, producer waves issue the DMA, consumer waves multiply -- long-k
-//                                128 x 64 tiles;
-//         igemm_bf16_kernel      register-staged gather -- the stem (32-element taps).
+//       Three kernels share that tiling:
+//         igemm_bf16_ws_kernel   512 threads, producer waves issue the global->LDS DMA gather (the A rows come from
+//                                different image rows / taps) into an NS-stage ring, consumer waves multiply -- the
+//                                default for every 1x1 / 3x3 layer;
+//         igemm_bf16_dma_kernel  256 threads, every wave issues its DMA pieces and multiplies -- the stem (32-element
+//                                taps, two per k-tile), CREID_IGEMM_WS=0 and the plans that name it;
+//         igemm_bf16_kernel      register-staged gather -- the fallback under CREID_IGEMM_DMA=0 / CREID_STEM_DMA=0.
+//       The two DMA kernels share one epilogue (igemm_tile_epilogue below, built from conv_epilogue.hpp).
 // f32 : 128 x BN x 16 tile on v_mfma_f32_32x32x2_f32 (exact f32; parity mode), K-major LDS.
 // Epilogue (both): optional "+ add_src" (residual-gradient accumulation in dgrad), store in the
 // activation dtype, and optional per-tile per-channel (sum, sum of squares) partials of the fp32
 // accumulators for the training-mode BatchNorm that follows every convolution.
-#include "conv_common.hpp"
+#include "conv_epilogue.hpp"
 #include <type_traits>
 #include "wgrad_reduce.hpp"
 #include "tune.hpp"
@@ -270,9 +272,168 @@ __global__ __launch_bounds__(256, BN == 128 ? 1 : 2) void igemm_bf16_kernel(IGem
     }
   }
 }
+// ------------------------------------------------------------------------------------ 16-bit C-tile epilogue
+// The epilogue of the two LDS-DMA tile kernels (primitives: conv_epilogue.hpp), entered behind the __syncthreads() that ends
+// the k-loop.  NT = 256 (igemm_bf16_dma_kernel): every wave holds a 64 x BN/2 accumulator sub-tile; NT = 512
+// (igemm_bf16_ws_kernel): waves 0-3 hold BM/2 x BN/2 sub-tiles, all eight waves copy out.  `smem` is the kernel's whole LDS
+// array: first the staged C tile ([BN columns][BM + 4 rows]), then the scratch of the two reductions.  pixel_of maps a GEMM
+// row to the raster pixel of the output tensor.  Per chunk: "+ add_src" (full resolution, optionally bit-masked, or the
+// stride-2 compact tensor), store, and the fused BatchNorm-backward column reduction (bnred.x; 128-row tiles only), whose
+// operand chunks (x, act or its mask bits) are fetched BEFORE the staging so the loads fly while the accumulators go through
+// LDS.  bn_part: per-channel (sum, sum of squares) of the fp32 accumulators, one row pair per 128 rows.
+template <typename ET, int BM, int BN, int NT, typename PixelOf>
+__device__ __forceinline__ void igemm_tile_epilogue(const IGemmGeom& g, unsigned short* smem, const f32x16 (&acc)[BM / 64][BN / 64],
+                                                    unsigned short* __restrict__ out, const unsigned short* __restrict__ add_src,
+                                                    float* __restrict__ bn_part, const BnRedArgs& bnred, int tile_m, int row0,
+                                                    int col0, PixelOf pixel_of) {
+  constexpr int MI = BM / 64, TNW = BN / 64, WS = NT / 64;
+  constexpr int CPT = BM + 4;                                    // staging pitch (elements)
+  constexpr int CPR = BN / 8, NIT = (BM * CPR) / NT;             // 16-byte chunks per tile row; chunks per thread
+  constexpr int NRG = NT / CPR;                                  // row groups among the threads sharing a column octet
+  constexpr int NPRE = BM == 128 ? NIT : 1;
+  constexpr int UNR = NT == 512 ? 8 : NRG;                       // unroll of the octet sums (64 terms at NT = 512, BN = 64)
+  static_assert(16 % CPR == 0, "copy-out map: 8 or 16 column octets per tile row");
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const bool holds_acc = NT == 256 || wave < 4;
+  const int wm = (wave & 3) >> 1, wn = wave & 1;
+  const int l31 = lane & 31, kh = lane >> 5;
+  const unsigned short* bx = BM == 128 ? reinterpret_cast<const unsigned short*>(bnred.x) : nullptr;
+  const unsigned short* bact = reinterpret_cast<const unsigned short*>(bnred.act);
+
+  uint4 pre_x[NPRE], pre_a[NPRE];
+  unsigned pre_m[NPRE];                                          // ReLU mask bits of the chunk (bnred.mask) instead of pre_a
+  if (bx) {
+#pragma unroll
+    for (int i = 0; i < NPRE; ++i) {
+      int rl, ch;
+      copy_unit<WS, CPR>(lane, wave, i, rl, ch);
+      const int rr = row0 + rl;
+      pre_x[i] = make_uint4(0u, 0u, 0u, 0u);
+      pre_a[i] = make_uint4(ET::ONE2, ET::ONE2, ET::ONE2, ET::ONE2);
+      pre_m[i] = 0xffu;
+      if (rr < g.M) {
+        const int64_t off = (int64_t)pixel_of(rr) * g.N + col0 + ch * 8;
+        pre_x[i] = *reinterpret_cast<const uint4*>(bx + off);
+        if (bnred.mask) pre_m[i] = bnred.mask[off >> 3];
+        else if (bact) pre_a[i] = *reinterpret_cast<const uint4*>(bact + off);
+      }
+    }
+  }
+  float s1v[TNW], s2v[TNW];
+  if (holds_acc && g.epi_scale) {
+    // eval-mode BatchNorm folded into the convolution: ReLU here unless the block's residual is still to be added in the copy-out
+    const bool relu_now = g.epi_relu && !add_src;
+#pragma unroll
+    for (int j = 0; j < TNW; ++j) {
+      const int cl = wn * (BN / 2) + j * 32 + l31;
+      const float sc = g.epi_scale[col0 + cl], sh = g.epi_shift[col0 + cl];
+      s1v[j] = 0.f; s2v[j] = 0.f;
+#pragma unroll
+      for (int i = 0; i < MI; ++i)
+        stage_block<ET>(&smem[cl * CPT + wm * (BM / 2) + i * 32 + 4 * kh], acc[i][j], true, sc, sh, relu_now);
+    }
+  } else if (holds_acc) {
+#pragma unroll
+    for (int j = 0; j < TNW; ++j) {
+      const int cl = wn * (BN / 2) + j * 32 + l31;
+      float s1 = 0.f, s2 = 0.f;                                  // rows >= M were zero-filled -> contribute 0
+#pragma unroll
+      for (int i = 0; i < MI; ++i) {
+        colsum_block(acc[i][j], s1, s2);
+        stage_block<ET>(&smem[cl * CPT + wm * (BM / 2) + i * 32 + 4 * kh], acc[i][j]);
+      }
+      colsum_lane_halves(s1, s2);
+      s1v[j] = s1; s2v[j] = s2;
+    }
+  }
+  __syncthreads();
+  float rs1[8], rs2[8], rmu[8], ris[8];
+  if (bx) {
+    int rl0, ch0;
+    copy_unit<WS, CPR>(lane, wave, 0, rl0, ch0);                 // this thread's column octet is the same in every pass
+    const int c0 = col0 + ch0 * 8;
+    const int64_t so = bnred.tiles_per_image ? (int64_t)(tile_m / bnred.tiles_per_image) * g.N : 0;   // per-image statistics (IBN)
+#pragma unroll
+    for (int k = 0; k < 8; k += 4) {
+      const float4 a = *reinterpret_cast<const float4*>(bnred.mean + so + c0 + k);
+      const float4 b = *reinterpret_cast<const float4*>(bnred.invstd + so + c0 + k);
+      rmu[k] = a.x; rmu[k + 1] = a.y; rmu[k + 2] = a.z; rmu[k + 3] = a.w;
+      ris[k] = b.x; ris[k + 1] = b.y; ris[k + 2] = b.z; ris[k + 3] = b.w;
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { rs1[k] = 0.f; rs2[k] = 0.f; }
+  }
+  uint4 cv[NIT];
+  read_back_chunks<NIT, WS, CPR, CPT>(smem, lane, wave, cv);
+#pragma unroll
+  for (int i = 0; i < NIT; ++i) {
+    int rl, ch;
+    copy_unit<WS, CPR>(lane, wave, i, rl, ch);
+    const int rr = row0 + rl;
+    if (rr < g.M) {
+      uint4 v = cv[i];
+      const int prow = pixel_of(rr);
+      const int64_t off = (int64_t)prow * g.N + col0 + ch * 8;
+      if (add_src) {
+        int64_t aoff = off;
+        bool has = true;
+        if (g.add_compact) {                                     // the stride-2 downsample branch's gradient, compact
+          int ab, arem, ay, ax;
+          fast_divmod(prow, g.OH * g.OW, g.inv_ohow, ab, arem);
+          fast_divmod(arem, g.OW, g.inv_ow, ay, ax);
+          has = ((ay | ax) & 1) == 0;
+          aoff = (int64_t)((ab * (g.OH >> 1) + (ay >> 1)) * (g.OW >> 1) + (ax >> 1)) * g.N + col0 + ch * 8;
+        }
+        if (has) {
+          const uint4 a = *reinterpret_cast<const uint4*>(add_src + aoff);
+          add_chunk<ET>(v, a, g.epi_relu, g.add_mask ? (unsigned)g.add_mask[aoff >> 3] : 0xffu);
+        }
+      }
+      if (!CREID_ABL_ON(g.abl, 8)) *reinterpret_cast<uint4*>(out + off) = v;
+      if (bx) bnred_chunk<ET>(v, pre_x[i % NPRE], pre_a[i % NPRE], pre_m[i % NPRE], rmu, ris, rs1, rs2);   // (NPRE == NIT whenever bx can be non-null)
+    }
+  }
+  if (bx) {
+    __syncthreads();                                             // staged C tile no longer needed
+    float* red2 = reinterpret_cast<float*>(smem);                // [NRG][2][BN]
+    const int cidx = lane >> 2;                                  // unit of the pass; lane & 3 = row of its quad
+    const int rg = (wave * 4 + (lane & 3)) * (16 / CPR) + cidx / CPR, cb = (cidx % CPR) * 8;   // threads that share an octet
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { red2[(rg * 2 + 0) * BN + cb + k] = rs1[k]; red2[(rg * 2 + 1) * BN + cb + k] = rs2[k]; }
+    __syncthreads();
+    for (int i = tid; i < 2 * BN; i += NT) {
+      const int which = i / BN, cl = i - which * BN;
+      float a = 0.f;
+#pragma unroll UNR
+      for (int q = 0; q < NRG; ++q) a += red2[(q * 2 + which) * BN + cl];
+      bnred.partial[((int64_t)tile_m * 2 + which) * g.N + col0 + cl] = a;
+    }
+  }
+  if (bn_part) {
+    __syncthreads();
+    float* red = reinterpret_cast<float*>(smem);                 // [2 (wm)][2 (s1, s2)][BN]
+    if (holds_acc) {
+#pragma unroll
+      for (int j = 0; j < TNW; ++j) {
+        const int cl = wn * (BN / 2) + j * 32 + l31;
+        if (kh == 0) { red[(wm * 2 + 0) * BN + cl] = s1v[j]; red[(wm * 2 + 1) * BN + cl] = s2v[j]; }
+      }
+    }
+    __syncthreads();
+    for (int i = tid; i < 2 * BN; i += NT) {
+      const int which = i / BN, cl = i - which * BN;
+      if constexpr (BM == 128) {
+        bn_part[((int64_t)tile_m * 2 + which) * g.N + col0 + cl] = red[(0 * 2 + which) * BN + cl] + red[(1 * 2 + which) * BN + cl];
+      } else {                                                   // partial rows stay per 128 rows: one per consumer-wave row half
+        bn_part[((int64_t)(tile_m * 2 + 0) * 2 + which) * g.N + col0 + cl] = red[(0 * 2 + which) * BN + cl];
+        if (row0 + 128 < g.M) bn_part[((int64_t)(tile_m * 2 + 1) * 2 + which) * g.N + col0 + cl] = red[(1 * 2 + which) * BN + cl];
+      }
+    }
+  }
+}
 
 // ------------------------------------------------------------------------------------ bf16, LDS-DMA
-// Same tiling / epilogue as igemm_bf16_kernel, but both operand tiles are fetched with gfx950's
+// Same tiling as igemm_bf16_kernel, but both operand tiles are fetched with gfx950's
 // global->LDS DMA (`global_load_lds_dwordx4`: LDS[wave base + lane*16] <- that lane's 16 global bytes): no
 // staging VGPRs, no ds_write pass, ~16 address VALU per k-tile.  The LDS image is linear (8 rows x 128 B per
 // wave-instruction); the conflict-free XOR swizzle is applied on the SOURCE side (lane holding LDS chunk c'
@@ -281,8 +442,6 @@ __global__ __launch_bounds__(256, BN == 128 ? 1 : 2) void igemm_bf16_kernel(IGem
 // is multiplied; `s_waitcnt vmcnt(n)` with n = the DMA instructions of the younger tiles still in flight; one
 // bare s_barrier per k-tile.  Measured (r01, profiles/r01_igemm_stage_sweep.md): NS = 2 wins on every ResNet50
 // layer -- the loop is not DMA-latency bound, and 3+ stages cost a workgroup per CU.
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
 template <int BN, int NS, typename ET = Bf16T>
 __global__ __launch_bounds__(256, (NS * (128 + BN) * 128 <= 80 * 1024) ? 2 : 1) void igemm_bf16_dma_kernel(IGemmGeom g, const unsigned short* __restrict__ src,
                                                                  const unsigned short* __restrict__ wgt,
@@ -291,7 +450,7 @@ __global__ __launch_bounds__(256, (NS * (128 + BN) * 128 <= 80 * 1024) ? 2 : 1) 
                                                                  float* __restrict__ bn_part, int tiles_n,
                                                                  BnRedArgs bnred) {
   constexpr int BK = 64, TNW = BN / 64, NBI = BN / 32;          // NBI = B-tile DMA instructions per wave
-  constexpr int CPT = 128 + 4;                                   // transposed C staging (see igemm_bf16_ws_kernel)
+  constexpr int CPT = 128 + 4;                                   // C staging pitch (igemm_tile_epilogue)
   constexpr int TILE_A = 128 * BK, TILE_B = BN * BK, STAGE = TILE_A + TILE_B;
   constexpr int LDS_ELEMS = (NS * STAGE) > (BN * CPT) ? (NS * STAGE) : (BN * CPT);
   constexpr int LPT = 4 + NBI;                                   // DMA instructions per wave per k-tile
@@ -434,203 +593,7 @@ __global__ __launch_bounds__(256, (NS * (128 + BN) * 128 <= 80 * 1024) ? 2 : 1) 
   }
   __syncthreads();
 
-  // ---- epilogue (identical to igemm_bf16_kernel)
-  // fused BN-backward reduction: its two operand tiles (x, act) are fetched NOW, so the loads fly while the
-  // accumulators are staged through LDS (they used to start only after the C tile had been stored)
-  constexpr int NPRE = (128 * (BN / 8)) / 256;
-  constexpr int CPR = BN / 8;
-  static_assert(16 % CPR == 0, "copy-out map: 8 or 16 column octets per tile row");
-  const int t4 = lane & 3, q4 = (lane >> 2) & 3, g4 = lane >> 4;
-  auto unit_of = [&](int i, int& rl, int& ch) {                  // copy-out map of igemm_bf16_ws_kernel, 4 waves
-    const int Q = (wave + 4 * i) * 16 + g4 * 4 + q4;
-    ch = Q % CPR;
-    rl = 4 * (Q / CPR) + t4;
-  };
-  uint4 pre_x[NPRE], pre_a[NPRE];
-  unsigned pre_m[NPRE];                                          // ReLU mask bits of the chunk (bnred.mask) instead of pre_a
-  if (bnred.x && bnred.prefetch) {
-    const unsigned short* bx0 = reinterpret_cast<const unsigned short*>(bnred.x);
-    const unsigned short* ba0 = reinterpret_cast<const unsigned short*>(bnred.act);
-#pragma unroll
-    for (int i = 0; i < NPRE; ++i) {
-      int rl, ch;
-      unit_of(i, rl, ch);
-      const int rr = row0 + rl;
-      pre_x[i] = make_uint4(0u, 0u, 0u, 0u);
-      pre_a[i] = make_uint4(ET::ONE2, ET::ONE2, ET::ONE2, ET::ONE2);
-      pre_m[i] = 0xffu;
-      if (rr < g.M) {
-        const int64_t off = (int64_t)rr * g.N + col0 + ch * 8;
-        pre_x[i] = *reinterpret_cast<const uint4*>(bx0 + off);
-        if (bnred.mask) pre_m[i] = bnred.mask[off >> 3];
-        else if (ba0) pre_a[i] = *reinterpret_cast<const uint4*>(ba0 + off);
-      }
-    }
-  }
-  float s1v[TNW], s2v[TNW];
-  if (g.epi_scale) {
-    // eval-mode BatchNorm folded into the convolution: y = acc * scale[c] + shift[c] on the fp32 accumulators (a lane's
-    // column is fixed per j), ReLU here unless the block's residual is still to be added in the copy-out
-    const bool relu_now = g.epi_relu && !add_src;
-#pragma unroll
-    for (int j = 0; j < TNW; ++j) {
-      const int cl = wn * (BN / 2) + j * 32 + l31;
-      const float sc = g.epi_scale[col0 + cl], sh = g.epi_shift[col0 + cl];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int rl = wm * 64 + i * 32 + 8 * q + 4 * kh;
-          float v0 = fmaf(acc[i][j][4 * q], sc, sh), v1 = fmaf(acc[i][j][4 * q + 1], sc, sh);
-          float v2 = fmaf(acc[i][j][4 * q + 2], sc, sh), v3 = fmaf(acc[i][j][4 * q + 3], sc, sh);
-          if (relu_now) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); v2 = fmaxf(v2, 0.f); v3 = fmaxf(v3, 0.f); }
-          *reinterpret_cast<uint2*>(&smem[cl * CPT + rl]) = make_uint2(ET::pack2(v0, v1), ET::pack2(v2, v3));
-        }
-      }
-      s1v[j] = 0.f; s2v[j] = 0.f;
-    }
-  } else {
-#pragma unroll
-  for (int j = 0; j < TNW; ++j) {
-    const int cl = wn * (BN / 2) + j * 32 + l31;
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int rl = wm * 64 + i * 32 + 8 * q + 4 * kh;
-        const float v0 = acc[i][j][4 * q], v1 = acc[i][j][4 * q + 1], v2 = acc[i][j][4 * q + 2], v3 = acc[i][j][4 * q + 3];
-        s1 += v0; s2 = fmaf(v0, v0, s2);
-        s1 += v1; s2 = fmaf(v1, v1, s2);
-        s1 += v2; s2 = fmaf(v2, v2, s2);
-        s1 += v3; s2 = fmaf(v3, v3, s2);
-        *reinterpret_cast<uint2*>(&smem[cl * CPT + rl]) = make_uint2(ET::pack2(v0, v1), ET::pack2(v2, v3));
-      }
-    }
-    s1 += __shfl_xor(s1, 32, 64); s2 += __shfl_xor(s2, 32, 64);
-    s1v[j] = s1; s2v[j] = s2;
-  }
-  }
-  __syncthreads();
-  constexpr int NIT = (128 * CPR) / 256;
-  u32x2 trlo[NIT], trhi[NIT];
-  {
-    const int sq = lane & 3, sj = (lane >> 2) & 3;
-#pragma unroll
-    for (int i = 0; i < NIT; ++i) {
-      const int Qs = (wave + 4 * i) * 16 + g4 * 4 + sq;
-      const unsigned addr = (unsigned)(uintptr_t)&smem[((Qs % CPR) * 8 + sj) * CPT + 4 * (Qs / CPR)];
-      asm volatile("ds_read_b64_tr_b16 %0, %2\n\tds_read_b64_tr_b16 %1, %2 offset:%3"
-                   : "=&v"(trlo[i]), "=&v"(trhi[i]) : "v"(addr), "i"(4 * CPT * 2) : "memory");
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-    for (int i = 0; i < NIT; ++i) asm volatile("" : "+v"(trlo[i]), "+v"(trhi[i]));
-  }
-  constexpr int NRG = 256 / CPR;                               // row groups among the threads sharing a chunk column
-  const unsigned short* bx = reinterpret_cast<const unsigned short*>(bnred.x);
-  const unsigned short* bact = reinterpret_cast<const unsigned short*>(bnred.act);
-  float rs1[8], rs2[8], rmu[8], ris[8];
-  if (bx) {
-    const int c0 = col0 + ((g4 * 4 + q4) % CPR) * 8;
-#pragma unroll
-    for (int k = 0; k < 8; k += 4) {
-      const int64_t so = bnred.tiles_per_image ? (int64_t)(tile_m / bnred.tiles_per_image) * g.N : 0;   // per-image statistics (IBN)
-      const float4 a = *reinterpret_cast<const float4*>(bnred.mean + so + c0 + k);
-      const float4 b = *reinterpret_cast<const float4*>(bnred.invstd + so + c0 + k);
-      rmu[k] = a.x; rmu[k + 1] = a.y; rmu[k + 2] = a.z; rmu[k + 3] = a.w;
-      ris[k] = b.x; ris[k + 1] = b.y; ris[k + 2] = b.z; ris[k + 3] = b.w;
-    }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { rs1[k] = 0.f; rs2[k] = 0.f; }
-  }
-#pragma unroll
-  for (int i = 0; i < NIT; ++i) {
-    int rl, ch;
-    unit_of(i, rl, ch);
-    const int rr = row0 + rl;
-    if (rr < g.M) {
-      uint4 v = make_uint4(trlo[i].x, trlo[i].y, trhi[i].x, trhi[i].y);
-      const int64_t off = (int64_t)rr * g.N + col0 + ch * 8;
-      if (add_src) {
-        int64_t aoff = off;
-        bool has = true;
-        if (g.add_compact) {                                     // the stride-2 downsample branch's gradient, compact
-          int ab, arem, ay, ax;
-          fast_divmod(rr, g.OH * g.OW, g.inv_ohow, ab, arem);
-          fast_divmod(arem, g.OW, g.inv_ow, ay, ax);
-          has = ((ay | ax) & 1) == 0;
-          aoff = (int64_t)((ab * (g.OH >> 1) + (ay >> 1)) * (g.OW >> 1) + (ax >> 1)) * g.N + col0 + ch * 8;
-        }
-        if (has) {
-          const uint4 a = *reinterpret_cast<const uint4*>(add_src + aoff);
-          const unsigned am = g.add_mask ? (unsigned)g.add_mask[aoff >> 3] : 0xffu;
-          unsigned* vw = &v.x; const unsigned* aw = &a.x;
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const float alo = ((am >> (2 * q)) & 1u) ? ET::lo(aw[q]) : 0.f;
-            const float ahi = ((am >> (2 * q + 1)) & 1u) ? ET::hi(aw[q]) : 0.f;
-            float lo = ET::lo(vw[q]) + alo;
-            float hi = ET::hi(vw[q]) + ahi;
-            if (g.epi_relu) { lo = fmaxf(lo, 0.f); hi = fmaxf(hi, 0.f); }     // folded BatchNorm + residual: ReLU after the add
-            vw[q] = ET::pack2(lo, hi);
-          }
-        }
-      }
-      *reinterpret_cast<uint4*>(out + off) = v;
-      if (bx) {                                                // fused BN-backward column reduction
-        uint4 xv = pre_x[i], av = pre_a[i];
-        unsigned mb = pre_m[i];
-        if (!bnred.prefetch) {
-          xv = *reinterpret_cast<const uint4*>(bx + off);
-          av = make_uint4(ET::ONE2, ET::ONE2, ET::ONE2, ET::ONE2);
-          if (bnred.mask) mb = bnred.mask[off >> 3];
-          else if (bact) av = *reinterpret_cast<const uint4*>(bact + off);
-        }
-        const unsigned* vw = &v.x; const unsigned* xw = &xv.x; const unsigned* aw = &av.x;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          float g0 = ET::lo(vw[q]), g1 = ET::hi(vw[q]);
-          const float a0 = ET::lo(aw[q]), a1 = ET::hi(aw[q]);
-          const float x0 = ET::lo(xw[q]), x1 = ET::hi(xw[q]);
-          g0 = (a0 > 0.f && ((mb >> (2 * q)) & 1u)) ? g0 : 0.f; g1 = (a1 > 0.f && ((mb >> (2 * q + 1)) & 1u)) ? g1 : 0.f;
-          rs1[2 * q] += g0; rs1[2 * q + 1] += g1;
-          rs2[2 * q] = fmaf(g0, (x0 - rmu[2 * q]) * ris[2 * q], rs2[2 * q]);
-          rs2[2 * q + 1] = fmaf(g1, (x1 - rmu[2 * q + 1]) * ris[2 * q + 1], rs2[2 * q + 1]);
-        }
-      }
-    }
-  }
-  if (bx) {
-    __syncthreads();                                           // staged C tile no longer needed
-    float* red2 = reinterpret_cast<float*>(smem);              // [NRG][2][BN]
-    const int cidx = g4 * 4 + q4;
-    const int rg = (wave * 4 + t4) * (16 / CPR) + cidx / CPR, cb = (cidx % CPR) * 8;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { red2[(rg * 2 + 0) * BN + cb + k] = rs1[k]; red2[(rg * 2 + 1) * BN + cb + k] = rs2[k]; }
-    __syncthreads();
-    for (int i = tid; i < 2 * BN; i += 256) {
-      const int which = i / BN, cl = i - which * BN;
-      float a = 0.f;
-#pragma unroll
-      for (int q = 0; q < NRG; ++q) a += red2[(q * 2 + which) * BN + cl];
-      bnred.partial[((int64_t)tile_m * 2 + which) * g.N + col0 + cl] = a;
-    }
-  }
-  if (bn_part) {
-    __syncthreads();
-    float* red = reinterpret_cast<float*>(smem);
-#pragma unroll
-    for (int j = 0; j < TNW; ++j) {
-      const int cl = wn * (BN / 2) + j * 32 + l31;
-      if (kh == 0) { red[(wm * 2 + 0) * BN + cl] = s1v[j]; red[(wm * 2 + 1) * BN + cl] = s2v[j]; }
-    }
-    __syncthreads();
-    for (int i = tid; i < 2 * BN; i += 256) {
-      const int which = i / BN, cl = i - which * BN;
-      bn_part[((int64_t)tile_m * 2 + which) * g.N + col0 + cl] = red[(0 * 2 + which) * BN + cl] + red[(1 * 2 + which) * BN + cl];
-    }
-  }
+  igemm_tile_epilogue<ET, 128, BN, 256>(g, smem, acc, out, add_src, bn_part, bnred, tile_m, row0, col0, [](int rr) { return rr; });
 }
 
 // ------------------------------------------------------------------------------------ bf16, warp-specialised
@@ -642,7 +605,7 @@ __global__ __launch_bounds__(256, (NS * (128 + BN) * 128 <= 80 * 1024) ? 2 : 1) 
 // into an NS-deep LDS ring.  One s_barrier per k-tile couples them:
 //   barrier B_t  <=  producers: their pieces of tile t have landed (vmcnt);  consumers: done reading tile t-1
 //   after B_t    :   producers issue tile t+NS-1 into slot (t-1)%NS, consumers multiply tile t.
-// Tiling, swizzle, zero page and the epilogue maths are those of igemm_bf16_dma_kernel (512 threads copy out).
+// Tiling, swizzle, zero page and the epilogue are those of igemm_bf16_dma_kernel (all 512 threads copy out).
 // BM = 128: the consumer waves hold 64 x BN/2 sub-tiles (two workgroups per CU where the ring allows it; THREE for the
 // 128 x 64 tile with a 2-deep ring: 48 KB of LDS, and the register allocator is held to 80 VGPRs (it needs 76) -- measured
 // -0.06 ms per step on the rule-selected schedule, round 3).  BM = 256: 128 x BN/2
@@ -759,7 +722,7 @@ __global__ __launch_bounds__(512, (BN == 64 && NS == 2 && BM == 128) ? 6 : ((NS 
 #pragma unroll
       for (int i = 0; i < NAI; ++i) {
         __builtin_amdgcn_global_load_lds((gptr_t)aptr[i], (lptr_t)(la + i * 2048), 16, 0, 0);
-        aptr[i] += amul[i] ? BK : 0;                             // running pointers (see igemm_bf16_dma_kernel)
+        aptr[i] += amul[i] ? BK : 0;                             // running pointers
       }
 #pragma unroll
       for (int i = 0; i < NBI; ++i) {
@@ -832,217 +795,7 @@ __global__ __launch_bounds__(512, (BN == 64 && NS == 2 && BM == 128) ? 6 : ((NS 
   }
   __syncthreads();
 
-  // ---- epilogue: consumers stage the C tile (bf16) in LDS, all 512 threads copy it out
-  // fused BN-backward reduction: its two operand tiles (x, act) are fetched NOW, so the loads fly while the
-  // accumulators are staged through LDS (they used to start only after the C tile had been stored)
-  // copy-out map (see below): a 16-lane group owns 4 rows x 4 column octets; lane = 16*g4 + 4*q4 + t4 stores row t4 of the
-  // row quad, octet g4*4 + q4 of the wave's 16-octet strip
-  constexpr int NPRE = BM == 128 ? (128 * (BN / 8)) / 512 : 1;   // (the fused BN reduction exists for 128-row tiles only)
-  const int t4 = lane & 3, q4 = (lane >> 2) & 3, g4 = lane >> 4;
-  auto unit_of = [&](int i, int& rl, int& ch) {
-    const int Q = (wave + 8 * i) * 16 + g4 * 4 + q4;
-    ch = Q % CPR;
-    rl = 4 * (Q / CPR) + t4;
-  };
-  uint4 pre_x[NPRE], pre_a[NPRE];
-  unsigned pre_m[NPRE];                                          // ReLU mask bits of the chunk (bnred.mask) instead of pre_a
-  if (BM == 128 && bnred.x && bnred.prefetch) {
-    const unsigned short* bx0 = reinterpret_cast<const unsigned short*>(bnred.x);
-    const unsigned short* ba0 = reinterpret_cast<const unsigned short*>(bnred.act);
-#pragma unroll
-    for (int i = 0; i < NPRE; ++i) {
-      int rl, ch;
-      unit_of(i, rl, ch);
-      const int rr = row0 + rl;
-      pre_x[i] = make_uint4(0u, 0u, 0u, 0u);
-      pre_a[i] = make_uint4(ET::ONE2, ET::ONE2, ET::ONE2, ET::ONE2);
-      pre_m[i] = 0xffu;
-      if (rr < g.M) {
-        const int64_t off = (int64_t)pixel_of(rr) * g.N + col0 + ch * 8;
-        pre_x[i] = *reinterpret_cast<const uint4*>(bx0 + off);
-        if (bnred.mask) pre_m[i] = bnred.mask[off >> 3];
-        else if (ba0) pre_a[i] = *reinterpret_cast<const uint4*>(ba0 + off);
-      }
-    }
-  }
-  // The C tile is staged COLUMN-major: a lane's four consecutive accumulator rows of one column are one packed 8-byte
-  // LDS store (2 v_cvt_pk_bf16_f32 + 1 ds_write_b64 per 4 values; the row-major image took a 2-byte store per value),
-  // and the copy-out gets its row-major 16-byte chunks back through the transposing LDS read.  Column pitch 264 B:
-  // 16 consecutive columns start 2 banks apart (conflict-free b64 stores), the 4 x 4 units of a transposing read too.
-  float s1v[TNW], s2v[TNW];
-  if (!producer && g.epi_scale) {
-    // eval-mode BatchNorm folded into the convolution (see igemm_bf16_dma_kernel)
-    const bool relu_now = g.epi_relu && !add_src;
-#pragma unroll
-    for (int j = 0; j < TNW; ++j) {
-      const int cl = wn * (BN / 2) + j * 32 + l31;
-      const float sc = g.epi_scale[col0 + cl], sh = g.epi_shift[col0 + cl];
-#pragma unroll
-      for (int i = 0; i < MI; ++i) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int rl = wm * (BM / 2) + i * 32 + 8 * q + 4 * kh;
-          float v0 = fmaf(acc[i][j][4 * q], sc, sh), v1 = fmaf(acc[i][j][4 * q + 1], sc, sh);
-          float v2 = fmaf(acc[i][j][4 * q + 2], sc, sh), v3 = fmaf(acc[i][j][4 * q + 3], sc, sh);
-          if (relu_now) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); v2 = fmaxf(v2, 0.f); v3 = fmaxf(v3, 0.f); }
-          *reinterpret_cast<uint2*>(&smem[cl * CPT + rl]) = make_uint2(ET::pack2(v0, v1), ET::pack2(v2, v3));
-        }
-      }
-      s1v[j] = 0.f; s2v[j] = 0.f;
-    }
-  } else if (!producer) {
-#pragma unroll
-    for (int j = 0; j < TNW; ++j) {
-      const int cl = wn * (BN / 2) + j * 32 + l31;
-      float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-      for (int i = 0; i < MI; ++i) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int rl = wm * (BM / 2) + i * 32 + 8 * q + 4 * kh;
-          const float v0 = acc[i][j][4 * q], v1 = acc[i][j][4 * q + 1], v2 = acc[i][j][4 * q + 2], v3 = acc[i][j][4 * q + 3];
-          s1 += v0; s2 = fmaf(v0, v0, s2);
-          s1 += v1; s2 = fmaf(v1, v1, s2);
-          s1 += v2; s2 = fmaf(v2, v2, s2);
-          s1 += v3; s2 = fmaf(v3, v3, s2);
-          *reinterpret_cast<uint2*>(&smem[cl * CPT + rl]) = make_uint2(ET::pack2(v0, v1), ET::pack2(v2, v3));
-        }
-      }
-      s1 += __shfl_xor(s1, 32, 64); s2 += __shfl_xor(s2, 32, 64);
-      s1v[j] = s1; s2v[j] = s2;
-    }
-  }
-  __syncthreads();
-  // transposing reads: in a 16-lane group lane s supplies the 8-byte unit (column 8 * octet(s & 3) + (s >> 2), the row quad)
-  // and lane l receives (row l & 3, columns 8 * octet(l >> 2) + 0..3); a second read 4 columns on completes the 16-byte chunk.
-  // Every lane takes part (the data crosses lanes), only the global store is predicated.
-  constexpr int NIT = (BM * CPR) / NT;
-  static_assert(16 % CPR == 0, "copy-out map: 8 or 16 column octets per tile row");
-  u32x2 trlo[NIT], trhi[NIT];
-  {
-    const int sq = lane & 3, sj = (lane >> 2) & 3;
-#pragma unroll
-    for (int i = 0; i < NIT; ++i) {
-      const int Qs = (wave + 8 * i) * 16 + g4 * 4 + sq;
-      const unsigned addr = (unsigned)(uintptr_t)&smem[((Qs % CPR) * 8 + sj) * CPT + 4 * (Qs / CPR)];
-      asm volatile("ds_read_b64_tr_b16 %0, %2\n\tds_read_b64_tr_b16 %1, %2 offset:%3"
-                   : "=&v"(trlo[i]), "=&v"(trhi[i]) : "v"(addr), "i"(4 * CPT * 2) : "memory");
-    }
-  }
-  const unsigned short* bx = BM == 128 ? reinterpret_cast<const unsigned short*>(bnred.x) : nullptr;
-  const unsigned short* bact = reinterpret_cast<const unsigned short*>(bnred.act);
-  float rs1[8], rs2[8], rmu[8], ris[8];
-  if (bx) {
-    const int c0 = col0 + ((g4 * 4 + q4) % CPR) * 8;            // this thread's column octet is the same in every pass
-#pragma unroll
-    for (int k = 0; k < 8; k += 4) {
-      const int64_t so = bnred.tiles_per_image ? (int64_t)(tile_m / bnred.tiles_per_image) * g.N : 0;   // per-image statistics (IBN)
-      const float4 a = *reinterpret_cast<const float4*>(bnred.mean + so + c0 + k);
-      const float4 b = *reinterpret_cast<const float4*>(bnred.invstd + so + c0 + k);
-      rmu[k] = a.x; rmu[k + 1] = a.y; rmu[k + 2] = a.z; rmu[k + 3] = a.w;
-      ris[k] = b.x; ris[k + 1] = b.y; ris[k + 2] = b.z; ris[k + 3] = b.w;
-    }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { rs1[k] = 0.f; rs2[k] = 0.f; }
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-  for (int i = 0; i < NIT; ++i) asm volatile("" : "+v"(trlo[i]), "+v"(trhi[i]));
-#pragma unroll
-  for (int i = 0; i < NIT; ++i) {
-    int rl, ch;
-    unit_of(i, rl, ch);
-    const int rr = row0 + rl;
-    if (rr < g.M) {
-      uint4 v = make_uint4(trlo[i].x, trlo[i].y, trhi[i].x, trhi[i].y);
-      const int prow = pixel_of(rr);
-      const int64_t off = (int64_t)prow * g.N + col0 + ch * 8;
-      if (add_src) {
-        int64_t aoff = off;
-        bool has = true;
-        if (g.add_compact) {                                     // the stride-2 downsample branch's gradient, compact
-          int ab, arem, ay, ax;
-          fast_divmod(prow, g.OH * g.OW, g.inv_ohow, ab, arem);
-          fast_divmod(arem, g.OW, g.inv_ow, ay, ax);
-          has = ((ay | ax) & 1) == 0;
-          aoff = (int64_t)((ab * (g.OH >> 1) + (ay >> 1)) * (g.OW >> 1) + (ax >> 1)) * g.N + col0 + ch * 8;
-        }
-        if (has) {
-          const uint4 a = *reinterpret_cast<const uint4*>(add_src + aoff);
-          const unsigned am = g.add_mask ? (unsigned)g.add_mask[aoff >> 3] : 0xffu;
-          unsigned* vw = &v.x; const unsigned* aw = &a.x;
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const float alo = ((am >> (2 * q)) & 1u) ? ET::lo(aw[q]) : 0.f;
-            const float ahi = ((am >> (2 * q + 1)) & 1u) ? ET::hi(aw[q]) : 0.f;
-            float lo = ET::lo(vw[q]) + alo;
-            float hi = ET::hi(vw[q]) + ahi;
-            if (g.epi_relu) { lo = fmaxf(lo, 0.f); hi = fmaxf(hi, 0.f); }     // folded BatchNorm + residual: ReLU after the add
-            vw[q] = ET::pack2(lo, hi);
-          }
-        }
-      }
-      if (!CREID_ABL_ON(g.abl, 8)) *reinterpret_cast<uint4*>(out + off) = v;
-      if (bx) {
-        uint4 xv = pre_x[i % NPRE], av = pre_a[i % NPRE];        // (NPRE == NIT whenever bx can be non-null)
-        unsigned mb = pre_m[i % NPRE];
-        if (!bnred.prefetch) {
-          xv = *reinterpret_cast<const uint4*>(bx + off);
-          av = make_uint4(ET::ONE2, ET::ONE2, ET::ONE2, ET::ONE2);
-          if (bnred.mask) mb = bnred.mask[off >> 3];
-          else if (bact) av = *reinterpret_cast<const uint4*>(bact + off);
-        }
-        const unsigned* vw = &v.x; const unsigned* xw = &xv.x; const unsigned* aw = &av.x;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          float g0 = ET::lo(vw[q]), g1 = ET::hi(vw[q]);
-          const float a0 = ET::lo(aw[q]), a1 = ET::hi(aw[q]);
-          const float x0 = ET::lo(xw[q]), x1 = ET::hi(xw[q]);
-          g0 = (a0 > 0.f && ((mb >> (2 * q)) & 1u)) ? g0 : 0.f; g1 = (a1 > 0.f && ((mb >> (2 * q + 1)) & 1u)) ? g1 : 0.f;
-          rs1[2 * q] += g0; rs1[2 * q + 1] += g1;
-          rs2[2 * q] = fmaf(g0, (x0 - rmu[2 * q]) * ris[2 * q], rs2[2 * q]);
-          rs2[2 * q + 1] = fmaf(g1, (x1 - rmu[2 * q + 1]) * ris[2 * q + 1], rs2[2 * q + 1]);
-        }
-      }
-    }
-  }
-  if (bx) {
-    __syncthreads();
-    float* red2 = reinterpret_cast<float*>(smem);                // [NRG][2][BN]
-    const int cidx = g4 * 4 + q4;
-    const int rg = (wave * 4 + t4) * (16 / CPR) + cidx / CPR, cb = (cidx % CPR) * 8;   // threads that share an octet
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { red2[(rg * 2 + 0) * BN + cb + k] = rs1[k]; red2[(rg * 2 + 1) * BN + cb + k] = rs2[k]; }
-    __syncthreads();
-    for (int i = tid; i < 2 * BN; i += NT) {
-      const int which = i / BN, cl = i - which * BN;
-      float a = 0.f;
-#pragma unroll 8
-      for (int q = 0; q < NRG; ++q) a += red2[(q * 2 + which) * BN + cl];
-      bnred.partial[((int64_t)tile_m * 2 + which) * g.N + col0 + cl] = a;
-    }
-  }
-  if (bn_part) {
-    __syncthreads();
-    float* red = reinterpret_cast<float*>(smem);
-    if (!producer) {
-#pragma unroll
-      for (int j = 0; j < TNW; ++j) {
-        const int cl = wn * (BN / 2) + j * 32 + l31;
-        if (kh == 0) { red[(wm * 2 + 0) * BN + cl] = s1v[j]; red[(wm * 2 + 1) * BN + cl] = s2v[j]; }
-      }
-    }
-    __syncthreads();
-    for (int i = tid; i < 2 * BN; i += NT) {
-      const int which = i / BN, cl = i - which * BN;
-      if constexpr (BM == 128) {
-        bn_part[((int64_t)tile_m * 2 + which) * g.N + col0 + cl] = red[(0 * 2 + which) * BN + cl] + red[(1 * 2 + which) * BN + cl];
-      } else {                                                   // partial rows stay per 128 rows: one per consumer-wave row half
-        bn_part[((int64_t)(tile_m * 2 + 0) * 2 + which) * g.N + col0 + cl] = red[(0 * 2 + which) * BN + cl];
-        if (row0 + 128 < g.M) bn_part[((int64_t)(tile_m * 2 + 1) * 2 + which) * g.N + col0 + cl] = red[(1 * 2 + which) * BN + cl];
-      }
-    }
-  }
+  igemm_tile_epilogue<ET, BM, BN, NT>(g, smem, acc, out, add_src, bn_part, bnred, tile_m, row0, col0, pixel_of);
 }
 
 // ------------------------------------------------------------------------------------ f32
@@ -1216,10 +969,9 @@ __global__ __launch_bounds__(256) void igemm_f32_kernel(IGemmGeom g, const float
 }
 
 // ------------------------------------------------------------------------------------ host
-static int ilog2_exact(int64_t v) {
-  int l = 0;
-  while ((1LL << l) < v) ++l;
-  return ((1LL << l) == v) ? l : -1;
+static int use_dma_env() {
+  static const int v = [] { const char* e = getenv("CREID_IGEMM_DMA"); return e ? atoi(e) : 1; }();
+  return v;
 }
 
 static int ws_stages_env() {
@@ -1228,7 +980,7 @@ static int ws_stages_env() {
 }
 
 static int launch_igemm(const IGemmGeom& g_in, const void* src, const void* wgt, void* out, const void* add_src,
-                        float* bn_part, int dtype, hipStream_t s, BnRedArgs bnred = BnRedArgs{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0},
+                        float* bn_part, int dtype, hipStream_t s, BnRedArgs bnred = BnRedArgs{},
                         const WRedJob* wred_in = nullptr) {
 #ifdef CREID_ABL_BUILD
   const char* abl_e = CREID_KNOB_ENV("CREID_IGEMM_ABL");                  // per call: the probes sweep it inside one process
@@ -1321,7 +1073,7 @@ static int launch_igemm(const IGemmGeom& g_in, const void* src, const void* wgt,
   if (g.N % bn != 0) return CREID_E_SHAPE;
   const int tiles_n = g.N / bn;
   const dim3 grid((unsigned)(tiles_m * tiles_n)), block(256);
-  static const int use_dma = [] { const char* e = getenv("CREID_IGEMM_DMA"); return e ? atoi(e) : 1; }();
+  const int use_dma = use_dma_env();
   const bool stem_geom = g.log2span == 5 && !g.transposed && !g.check_bounds && g.kw == 1 && g.stride == 2 && g.pad == 0;
   static const int stem_dma = [] { const char* e = getenv("CREID_STEM_DMA"); return e ? atoi(e) : 1; }();
   if (creid_is16(dtype) && use_dma && (g.log2span >= 6 || (stem_geom && stem_dma))) {
@@ -1432,7 +1184,7 @@ static int launch_igemm(const IGemmGeom& g_in, const void* src, const void* wgt,
 static int check_desc(const creid_conv_desc* d) {
   if (!d || d->batch <= 0 || d->in_h <= 0 || d->in_w <= 0 || d->in_c <= 0 || d->out_c <= 0) return CREID_E_ARG;
   if (d->kh != d->kw || (d->kh != 1 && d->kh != 3) || d->stride < 1 || d->stride > 2) return CREID_E_SHAPE;
-  if (ilog2_exact(d->in_c) < 0 || ilog2_exact(d->out_c) < 0 || d->in_c < 64 || d->out_c < 64) return CREID_E_SHAPE;
+  if (igemm_ilog2(d->in_c) < 0 || igemm_ilog2(d->out_c) < 0 || d->in_c < 64 || d->out_c < 64) return CREID_E_SHAPE;
   if (d->out_h != (d->in_h + 2 * d->pad - d->kh) / d->stride + 1) return CREID_E_SHAPE;
   if (d->out_w != (d->in_w + 2 * d->pad - d->kw) / d->stride + 1) return CREID_E_SHAPE;
   if (d->batch * d->in_h * d->in_w >= (1LL << 24) || d->batch * d->out_h * d->out_w >= (1LL << 24) || d->batch * d->in_h * d->in_w * d->in_c > (1LL << 40)) return CREID_E_SHAPE;
@@ -1453,12 +1205,7 @@ int creid_conv2d_fwd_nhwc(const creid_conv_desc* d, const void* x, const void* w
   int rc = check_desc(d);
   if (rc) return rc;
   CREID_CHECK_ARG(x && w_krsc && y);
-  IGemmGeom g;
-  g.M = (int)(d->batch * d->out_h * d->out_w); g.OH = (int)d->out_h; g.OW = (int)d->out_w;
-  g.SH = (int)d->in_h; g.SW = (int)d->in_w; g.pitch = (int)d->in_c; g.log2span = ilog2_exact(d->in_c);
-  g.kw = d->kw; g.stride = d->stride; g.pad = d->pad; g.transposed = 0;
-  g.K = (int)(d->kh * d->kw * d->in_c); g.N = (int)d->out_c; g.check_bounds = 1;
-  igemm_finish_geom(g);
+  IGemmGeom g = fwd_geom(d);
   if (dtype == CREID_BF16X3) return launch_igemm_x3(g, x, w_krsc, y, nullptr, bn_partial, as_stream(stream));
   return launch_igemm(g, x, w_krsc, y, nullptr, bn_partial, dtype, as_stream(stream));
 }
@@ -1470,12 +1217,7 @@ int creid_conv2d_fwd_affine_nhwc(const creid_conv_desc* d, const void* x, const 
   int rc = check_desc(d);
   if (rc) return rc;
   CREID_CHECK_ARG(x && w_krsc && y && scale_shift);
-  IGemmGeom g;
-  g.M = (int)(d->batch * d->out_h * d->out_w); g.OH = (int)d->out_h; g.OW = (int)d->out_w;
-  g.SH = (int)d->in_h; g.SW = (int)d->in_w; g.pitch = (int)d->in_c; g.log2span = ilog2_exact(d->in_c);
-  g.kw = d->kw; g.stride = d->stride; g.pad = d->pad; g.transposed = 0;
-  g.K = (int)(d->kh * d->kw * d->in_c); g.N = (int)d->out_c; g.check_bounds = 1;
-  igemm_finish_geom(g);
+  IGemmGeom g = fwd_geom(d);
   g.epi_scale = scale_shift; g.epi_shift = scale_shift + d->out_c; g.epi_relu = relu ? 1 : 0;
   if (dtype == CREID_BF16X3) return launch_igemm_x3(g, x, w_krsc, y, residual, nullptr, as_stream(stream));
   return launch_igemm(g, x, w_krsc, y, residual, nullptr, dtype, as_stream(stream));
@@ -1486,12 +1228,7 @@ int creid_conv2d_dgrad_nhwc(const creid_conv_desc* d, const void* dy, const void
   int rc = check_desc(d);
   if (rc) return rc;
   CREID_CHECK_ARG(dy && w_crsk && dx);
-  IGemmGeom g;
-  g.M = (int)(d->batch * d->in_h * d->in_w); g.OH = (int)d->in_h; g.OW = (int)d->in_w;
-  g.SH = (int)d->out_h; g.SW = (int)d->out_w; g.pitch = (int)d->out_c; g.log2span = ilog2_exact(d->out_c);
-  g.kw = d->kw; g.stride = d->stride; g.pad = d->pad; g.transposed = 1;
-  g.K = (int)(d->kh * d->kw * d->out_c); g.N = (int)d->in_c; g.check_bounds = 1;
-  igemm_finish_geom(g);
+  IGemmGeom g = dgrad_geom(d);
   return launch_igemm(g, dy, w_crsk, dx, add_src, nullptr, dtype, as_stream(stream));
 }
 
@@ -1501,12 +1238,7 @@ int creid_conv2d_dgrad_x3_nhwc(const creid_conv_desc* d, const void* dy, const v
   int rc = check_desc(d);
   if (rc) return rc;
   CREID_CHECK_ARG(dy && w2_crsk && dx);
-  IGemmGeom g;
-  g.M = (int)(d->batch * d->in_h * d->in_w); g.OH = (int)d->in_h; g.OW = (int)d->in_w;
-  g.SH = (int)d->out_h; g.SW = (int)d->out_w; g.pitch = (int)d->out_c; g.log2span = ilog2_exact(d->out_c);
-  g.kw = d->kw; g.stride = d->stride; g.pad = d->pad; g.transposed = 1;
-  g.K = (int)(d->kh * d->kw * d->out_c); g.N = (int)d->in_c; g.check_bounds = 1;
-  igemm_finish_geom(g);
+  IGemmGeom g = dgrad_geom(d);
   return launch_igemm_x3(g, dy, w2_crsk, dx, add_src, nullptr, as_stream(stream));
 }
 
@@ -1517,22 +1249,9 @@ int creid_conv2d_dgrad_bnred_nhwc(const creid_conv_desc* d, const void* dy, cons
                                   int add_src_stride, int dtype, void* stream) {
   int rc = check_desc(d);
   if (rc) return rc;
-  CREID_CHECK_ARG(dy && w_crsk && dx && bn_x && bn_mean && bn_invstd && bn_partial && bn_stat_image_rows >= 0);
-  if (bn_stat_image_rows % 128 != 0) return CREID_E_SHAPE;
-  if (add_src_stride != 1 && add_src_stride != 2) return CREID_E_ARG;
-  if (add_src_stride == 2 && (!add_src || d->in_h % 2 || d->in_w % 2)) return CREID_E_SHAPE;
-  static const int use_dma = [] { const char* e = getenv("CREID_IGEMM_DMA"); return e ? atoi(e) : 1; }();
-  if (!creid_is16(dtype) || !use_dma) return CREID_E_DTYPE;
-  IGemmGeom g;
-  g.M = (int)(d->batch * d->in_h * d->in_w); g.OH = (int)d->in_h; g.OW = (int)d->in_w;
-  g.SH = (int)d->out_h; g.SW = (int)d->out_w; g.pitch = (int)d->out_c; g.log2span = ilog2_exact(d->out_c);
-  g.kw = d->kw; g.stride = d->stride; g.pad = d->pad; g.transposed = 1;
-  g.K = (int)(d->kh * d->kw * d->out_c); g.N = (int)d->in_c; g.check_bounds = 1;
-  igemm_finish_geom(g);
-  static const int prefetch = [] { const char* e = getenv("CREID_BNRED_PREFETCH"); return e ? atoi(e) : 1; }();
-  g.add_compact = add_src_stride == 2;
-  BnRedArgs br{bn_x, bn_act, bn_mean, bn_invstd, bn_partial, prefetch, (int)(bn_stat_image_rows / 128)};
-  return launch_igemm(g, dy, w_crsk, dx, add_src, nullptr, dtype, as_stream(stream), br);
+  CREID_CHECK_ARG(dy && w_crsk && dx && bn_x && bn_mean && bn_invstd && bn_partial && bn_stat_image_rows >= 0);   // (here bn_x is required)
+  return creid_conv2d_dgrad_fused_nhwc(d, dy, w_crsk, dx, add_src, add_src_stride, nullptr, bn_x, bn_act, nullptr, bn_mean, bn_invstd,
+                                       bn_partial, bn_stat_image_rows, nullptr, nullptr, 0, nullptr, 0, dtype, stream);
 }
 
 /* Data gradient with everything that can ride in the same launch: "+ add_src" (full or stride-2 compact), the NEXT
@@ -1554,7 +1273,7 @@ int creid_conv2d_dgrad_fused_nhwc(const creid_conv_desc* d, const void* dy, cons
   if (bn_stat_image_rows % 128 != 0) return CREID_E_SHAPE;
   if (add_src_stride != 1 && add_src_stride != 2) return CREID_E_ARG;
   if (add_src_stride == 2 && (!add_src || d->in_h % 2 || d->in_w % 2)) return CREID_E_SHAPE;
-  static const int use_dma = [] { const char* e = getenv("CREID_IGEMM_DMA"); return e ? atoi(e) : 1; }();
+  const int use_dma = use_dma_env();
   if (bn_x && (!creid_is16(dtype) || !use_dma)) return CREID_E_DTYPE;
   if (add_mask && (!add_src || add_src_stride != 1 || !creid_is16(dtype) || !use_dma)) return CREID_E_ARG;
   WRedJob job{};
@@ -1564,17 +1283,11 @@ int creid_conv2d_dgrad_fused_nhwc(const creid_conv_desc* d, const void* dy, cons
     if (!wgrad_make_reduce_job(wred_desc, dtype, wred_ws, wred_ws_bytes, wred_dw, wred_accumulate, job)) return CREID_E_SHAPE;
     have_job = true;
   }
-  IGemmGeom g;
-  g.M = (int)(d->batch * d->in_h * d->in_w); g.OH = (int)d->in_h; g.OW = (int)d->in_w;
-  g.SH = (int)d->out_h; g.SW = (int)d->out_w; g.pitch = (int)d->out_c; g.log2span = ilog2_exact(d->out_c);
-  g.kw = d->kw; g.stride = d->stride; g.pad = d->pad; g.transposed = 1;
-  g.K = (int)(d->kh * d->kw * d->out_c); g.N = (int)d->in_c; g.check_bounds = 1;
-  igemm_finish_geom(g);
-  static const int prefetch = [] { const char* e = getenv("CREID_BNRED_PREFETCH"); return e ? atoi(e) : 1; }();
+  IGemmGeom g = dgrad_geom(d);
   g.add_compact = add_src_stride == 2;
   g.add_mask = add_mask;
-  BnRedArgs br{bn_x, bn_mask ? nullptr : bn_act, bn_mean, bn_invstd, bn_partial, prefetch, (int)(bn_stat_image_rows / 128), bn_mask};
-  if (!bn_x) br = BnRedArgs{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr};
+  BnRedArgs br{};
+  if (bn_x) br = BnRedArgs{bn_x, bn_mask ? nullptr : bn_act, bn_mean, bn_invstd, bn_partial, (int)(bn_stat_image_rows / 128), bn_mask};
   return launch_igemm(g, dy, w_crsk, dx, add_src, nullptr, dtype, as_stream(stream), br, have_job ? &job : nullptr);
 }
 
@@ -1585,11 +1298,7 @@ int creid_stem_conv_fwd(int64_t batch, int64_t H, int64_t W, const void* xpad, c
                         float* bn_partial, int dtype, void* stream) {
   CREID_CHECK_ARG(xpad && w_stem && y && batch > 0 && H > 0 && W > 0);
   if (H % 2 || W % 2) return CREID_E_SHAPE;
-  IGemmGeom g;
-  g.M = (int)(batch * (H / 2) * (W / 2)); g.OH = (int)(H / 2); g.OW = (int)(W / 2);
-  g.SH = (int)(H + 8); g.SW = (int)(W + 6); g.pitch = 4; g.log2span = 5;
-  g.kw = 1; g.stride = 2; g.pad = 0; g.transposed = 0; g.K = 256; g.N = 64; g.check_bounds = 0;
-  igemm_finish_geom(g);
+  IGemmGeom g = stem_geom(batch, H, W);
   return launch_igemm(g, xpad, w_stem, y, nullptr, bn_partial, dtype, as_stream(stream));
 }
 
@@ -1598,11 +1307,7 @@ int creid_stem_conv_fwd_affine(int64_t batch, int64_t H, int64_t W, const void* 
                                const float* scale_shift, int relu, int dtype, void* stream) {
   CREID_CHECK_ARG(xpad && w_stem && y && scale_shift && batch > 0 && H > 0 && W > 0);
   if (H % 2 || W % 2) return CREID_E_SHAPE;
-  IGemmGeom g;
-  g.M = (int)(batch * (H / 2) * (W / 2)); g.OH = (int)(H / 2); g.OW = (int)(W / 2);
-  g.SH = (int)(H + 8); g.SW = (int)(W + 6); g.pitch = 4; g.log2span = 5;
-  g.kw = 1; g.stride = 2; g.pad = 0; g.transposed = 0; g.K = 256; g.N = 64; g.check_bounds = 0;
-  igemm_finish_geom(g);
+  IGemmGeom g = stem_geom(batch, H, W);
   g.epi_scale = scale_shift; g.epi_shift = scale_shift + 64; g.epi_relu = relu ? 1 : 0;
   return launch_igemm(g, xpad, w_stem, y, nullptr, nullptr, dtype, as_stream(stream));
 }

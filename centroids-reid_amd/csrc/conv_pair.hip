@@ -10,7 +10,7 @@
 // registers a tile ahead, stores a tile late, column-major packed staging read back through the transposing LDS read -- and the
 // second multiply runs in the k order of the tile kernels (four 64-deep chunks, 16-wide slices inside): both outputs are
 // bit-identical to the two launches (tests/test_eval_fold_gpu.py::test_block_boundary_one_launch_equals_two_launches).
-#include "conv_common.hpp"
+#include "conv_epilogue.hpp"
 #include <stdlib.h>
 
 namespace creid_pair {
@@ -83,6 +83,8 @@ __global__ __launch_bounds__(512, 1) void c3_c1_kernel(const unsigned short* __r
       *reinterpret_cast<uint4*>(slot + r * 64 + ((lcp ^ ((r >> 1) & 7)) << 3)) = areg[u];
     }
   };
+  // copy_unit<8, cpr>() of conv_epilogue.hpp with the lane's share computed once, here: recomputed at each use the STATS
+  // instantiation needs 258 registers (two spills)
   const int t4 = lane & 3, q4 = (lane >> 2) & 3, g4 = lane >> 4;
   auto unit_of = [&](int i, int cpr, int& rl, int& ch) {
     const int Q = (wave + 8 * i) * 16 + g4 * 4 + q4;
@@ -188,32 +190,12 @@ __global__ __launch_bounds__(512, 1) void c3_c1_kernel(const unsigned short* __r
         }
       }
       __syncthreads();                                            // the half is staged
-      u32x2 trlo[NIT], trhi[NIT];
-      {
-        const int sq = lane & 3, sj = (lane >> 2) & 3;
-#pragma unroll
-        for (int i = 0; i < NIT; ++i) {
-          const int Qs = (wave + 8 * i) * 16 + g4 * 4 + sq;
-          const unsigned addr = (unsigned)(uintptr_t)&stage[((Qs % CPR) * 8 + sj) * CPT + 4 * (Qs / CPR)];
-          asm volatile("ds_read_b64_tr_b16 %0, %2\n\tds_read_b64_tr_b16 %1, %2 offset:%3"
-                       : "=&v"(trlo[i]), "=&v"(trhi[i]) : "v"(addr), "i"(4 * CPT * 2) : "memory");
-        }
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-      for (int i = 0; i < NIT; ++i) asm volatile("" : "+v"(trlo[i]), "+v"(trhi[i]));
+      uint4 cv[NIT];
+      read_back_chunks<NIT, 8, CPR, CPT>(stage, lane, wave, cv);
 #pragma unroll
       for (int i = 0; i < NIT; ++i) {
-        uint4 v = make_uint4(trlo[i].x, trlo[i].y, trhi[i].x, trhi[i].y);
-        const uint4 a = resc[h][i];
-        unsigned* vw = &v.x; const unsigned* aw = &a.x;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          float lo = ET::lo(vw[q]) + ET::lo(aw[q]);
-          float hi = ET::hi(vw[q]) + ET::hi(aw[q]);
-          lo = fmaxf(lo, 0.f); hi = fmaxf(hi, 0.f);
-          vw[q] = ET::pack2(lo, hi);
-        }
+        uint4 v = cv[i];
+        add_chunk<ET>(v, resc[h][i], true);
         outv[h][i] = v;
         // the same chunk as an operand of the second multiply: row rl, channels h * 128 + ch * 8 ..
         int rl, ch;
@@ -241,7 +223,7 @@ __global__ __launch_bounds__(512, 1) void c3_c1_kernel(const unsigned short* __r
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { const float v = acc2[r]; s1 += v; s2 = fmaf(v, v, s2); }
-        s1 += __shfl_xor(s1, 32, 64); s2 += __shfl_xor(s2, 32, 64);
+        colsum_lane_halves(s1, s2);
         if (kh == 0) { red[(wr * 2 + 0) * 64 + cl] = s1; red[(wr * 2 + 1) * 64 + cl] = s2; }
       }
 #pragma unroll
@@ -264,22 +246,7 @@ __global__ __launch_bounds__(512, 1) void c3_c1_kernel(const unsigned short* __r
             (red[(0 * 2 + which) * 64 + cl] + red[(1 * 2 + which) * 64 + cl]) + (red[(2 * 2 + which) * 64 + cl] + red[(3 * 2 + which) * 64 + cl]);
       }
     }
-    {
-      u32x2 trlo[NIT2], trhi[NIT2];
-      const int sq = lane & 3, sj = (lane >> 2) & 3;
-#pragma unroll
-      for (int i = 0; i < NIT2; ++i) {
-        const int Qs = (wave + 8 * i) * 16 + g4 * 4 + sq;
-        const unsigned addr = (unsigned)(uintptr_t)&stage[((Qs % CPR2) * 8 + sj) * CPT + 4 * (Qs / CPR2)];
-        asm volatile("ds_read_b64_tr_b16 %0, %2\n\tds_read_b64_tr_b16 %1, %2 offset:%3"
-                     : "=&v"(trlo[i]), "=&v"(trhi[i]) : "v"(addr), "i"(4 * CPT * 2) : "memory");
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-      for (int i = 0; i < NIT2; ++i) asm volatile("" : "+v"(trlo[i]), "+v"(trhi[i]));
-#pragma unroll
-      for (int i = 0; i < NIT2; ++i) out1v[i] = make_uint4(trlo[i].x, trlo[i].y, trhi[i].x, trhi[i].y);
-    }
+    read_back_chunks<NIT2, 8, CPR2, CPT>(stage, lane, wave, out1v);
   }
   store_out(n_iter - 1);
 }

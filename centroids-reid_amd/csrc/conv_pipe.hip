@@ -18,7 +18,7 @@
 //     pieces through a staging area OUTSIDE the operand ring, so its stores drain under the next tile's loads.
 // Arithmetic per output element is that of the tile kernels (same k order inside v_mfma_f32_32x32x16_bf16, same epilogue
 // operations): outputs are bit-identical (tests/test_conv_pipe_gpu.py).
-#include "conv_common.hpp"
+#include "conv_epilogue.hpp"
 #include "tune.hpp"
 #include <type_traits>
 #include <stdlib.h>
@@ -28,7 +28,6 @@ namespace creid_pp {   // (a NAMED namespace: rocprofv3 prints `(anonymous names
 
 __device__ __attribute__((aligned(128))) unsigned g_zero_page_pp[32];
 
-template <int N> __device__ __forceinline__ void pp_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 __device__ __forceinline__ void pp_barrier() {
   __builtin_amdgcn_sched_barrier(0);
   asm volatile("s_barrier" ::: "memory");
@@ -45,7 +44,7 @@ __device__ __forceinline__ void pp_lds_barrier() {
 // One LDS-DMA piece: LDS[lds_addr + lane * 16] <- the lane's 16 global bytes.  Written as inline asm ON PURPOSE: hipcc models a
 // global_load_lds builtin as a FLAT access that may touch LDS, and from then on every wait it inserts for a fragment read is
 // a full `s_waitcnt lgkmcnt(0)` (pending-flat state), which exposes the latency of the reads issued just before it.  The asm
-// form is invisible to that bookkeeping; its completion is counted by hand (pp_wait_vm).  M0 is not used by anything else here.
+// form is invisible to that bookkeeping; its completion is counted by hand (wait_vm).  M0 is not used by anything else here.
 __device__ __forceinline__ void pp_glds16(const unsigned short* gsrc, unsigned lds_addr) {
   asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(gsrc), "s"(lds_addr) : "memory");
 }
@@ -209,11 +208,11 @@ __global__ __launch_bounds__(512, (BM * BN <= 128 * 128) ? 4 : 2) void igemm_bf1
       // free-running modes: the whole of k-tile 1 goes out NOW (ring slot 1 doubled as the copy-out staging area until the
       // barrier that ended the previous tile).  vmcnt(NP) then means "k-tile 0 has landed" whatever the previous tile's stores
       // do: loads return in order among themselves, so as long as one k-tile-0 piece is pending so are the NP younger ones.
-      if (NS == 3 && nk > 2) { issue(1, 1, 0, NP); issue(2, 2, 0, NP); pp_wait_vm<2 * NP>(); }
-      else if (nk > 1) { issue(1, 1, 0, NP); pp_wait_vm<NP>(); }
-      else pp_wait_vm<0>();
+      if (NS == 3 && nk > 2) { issue(1, 1, 0, NP); issue(2, 2, 0, NP); wait_vm<2 * NP>(); }
+      else if (nk > 1) { issue(1, 1, 0, NP); wait_vm<NP>(); }
+      else wait_vm<0>();
     } else {
-      pp_wait_vm<0>();                                           // k-tile 0 of this tile (and the previous tile's stores)
+      wait_vm<0>();                                              // k-tile 0 of this tile (and the previous tile's stores)
     }
     pp_barrier();
     PP_STAMP();
@@ -324,7 +323,7 @@ __global__ __launch_bounds__(512, (BM * BN <= 128 * 128) ? 4 : 2) void igemm_bf1
         if (ph == NPH - 1 && grp == 1) {
           // group 1 reaches the barrier that frees slot t & 1 for the DMA of k-tile t + 2 and opens k-tile t + 1 for group 0:
           // its reads of slot t & 1 must have returned and its pieces of k-tile t + 1 must have landed
-          if (more) pp_wait_vm<0>();
+          if (more) wait_vm<0>();
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         }
         pp_barrier();
@@ -340,7 +339,7 @@ __global__ __launch_bounds__(512, (BM * BN <= 128 * 128) ? 4 : 2) void igemm_bf1
             for (int j = 0; j < NJ; ++j)
               acc[i][j] = ET::mfma(a[kq][i], b[kq][j], acc[i][j]);
         __builtin_amdgcn_s_setprio(0);
-        if (ph == NPH - 1 && grp == 0 && more) pp_wait_vm<0>();   // group 0's pieces of k-tile t + 1
+        if (ph == NPH - 1 && grp == 0 && more) wait_vm<0>();      // group 0's pieces of k-tile t + 1
         pp_barrier();
         PP_STAMP();
       }
@@ -352,9 +351,8 @@ __global__ __launch_bounds__(512, (BM * BN <= 128 * 128) ? 4 : 2) void igemm_bf1
     const int next = tile + (int)gridDim.x;
     if (next < ntiles) { tile_setup(next); issue(0, 0, 0, NP); }
 
-    // ---- epilogue: 32-row blocks of every wave row, staged column-major (packed bf16, one ds_write_b64 per 4 rows of a column),
-    // read back through the transposing LDS read as 16-byte row chunks; two staging buffers alternate (one barrier per piece)
-    const int t4 = lane & 3, q4 = (lane >> 2) & 3, g4 = lane >> 4;
+    // ---- epilogue (conv_epilogue.hpp), piece-wise: one 32-row block of every wave row is staged and copied out at a time; two
+    // staging buffers alternate (one barrier per piece)
     float s1r[NJ], s2r[NJ];                                      // running column sums of the current 64-row sub-tile
     constexpr int G64 = (BM / WM) / 64;                           // 64-row sub-tiles per wave
     static_assert(G64 >= 1 && G64 == MI / 2, "wave rows");
@@ -375,63 +373,28 @@ __global__ __launch_bounds__(512, (BM * BN <= 128 * 128) ? 4 : 2) void igemm_bf1
       for (int j = 0; j < NJ; ++j) {
         const int cl = wn * (BN / WN) + j * 32 + l31;
         float s1 = (i & 1) ? s1r[j] : 0.f, s2 = (i & 1) ? s2r[j] : 0.f;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int rl = wm * 32 + 8 * q + 4 * kh;
-          float v0 = acc[i][j][4 * q], v1 = acc[i][j][4 * q + 1], v2 = acc[i][j][4 * q + 2], v3 = acc[i][j][4 * q + 3];
-          if constexpr (affine) {
-            v0 = fmaf(v0, esc[j], esh[j]); v1 = fmaf(v1, esc[j], esh[j]); v2 = fmaf(v2, esc[j], esh[j]); v3 = fmaf(v3, esc[j], esh[j]);
-            if (relu_now) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); v2 = fmaxf(v2, 0.f); v3 = fmaxf(v3, 0.f); }
-          } else if constexpr (EPI == 1) {
-            s1 += v0; s2 = fmaf(v0, v0, s2);
-            s1 += v1; s2 = fmaf(v1, v1, s2);
-            s1 += v2; s2 = fmaf(v2, v2, s2);
-            s1 += v3; s2 = fmaf(v3, v3, s2);
-          }
-          *reinterpret_cast<uint2*>(&sb[cl * CPT + rl]) = make_uint2(ET::pack2(v0, v1), ET::pack2(v2, v3));
-        }
+        if constexpr (EPI == 1) colsum_block(acc[i][j], s1, s2);
+        stage_block<ET>(&sb[cl * CPT + wm * 32 + 4 * kh], acc[i][j], affine, esc[j], esh[j], relu_now);
         s1r[j] = s1; s2r[j] = s2;
         if constexpr (EPI == 1) {
           if (i & 1) {                                            // a 64-row sub-tile is complete: lane halves, then to the scratch
-            s1 += __shfl_xor(s1, 32, 64); s2 += __shfl_xor(s2, 32, 64);
+            colsum_lane_halves(s1, s2);
             if (kh == 0) { red[((wm * G64 + (i >> 1)) * 2 + 0) * BN + cl] = s1; red[((wm * G64 + (i >> 1)) * 2 + 1) * BN + cl] = s2; }
           }
         }
       }
       pp_lds_barrier();                                          // piece i staged
-      u32x2 trlo[NIT], trhi[NIT];
-      {
-        const int sq = lane & 3, sj = (lane >> 2) & 3;
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-          const int Qs = (wave + 8 * it) * 16 + g4 * 4 + sq;
-          const unsigned addr = (unsigned)(uintptr_t)&sb[((Qs % CPR) * 8 + sj) * CPT + 4 * (Qs / CPR)];
-          asm volatile("ds_read_b64_tr_b16 %0, %2\n\tds_read_b64_tr_b16 %1, %2 offset:%3"
-                       : "=&v"(trlo[it]), "=&v"(trhi[it]) : "v"(addr), "i"(4 * CPT * 2) : "memory");
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) asm volatile("" : "+v"(trlo[it]), "+v"(trhi[it]));
-      }
+      uint4 cv[NIT];
+      read_back_chunks<NIT, 8, CPR, CPT>(sb, lane, wave, cv);
 #pragma unroll
       for (int it = 0; it < NIT; ++it) {
-        const int Q = (wave + 8 * it) * 16 + g4 * 4 + q4;
-        const int ch = Q % CPR, rl = 4 * (Q / CPR) + t4;         // piece-local row: wave row rl / 32, row rl % 32 of its block i
+        int rl, ch;                                              // piece-local row: wave row rl / 32, row rl % 32 of its block i
+        copy_unit<8, CPR>(lane, wave, it, rl, ch);
         const int rr = row0 + (rl >> 5) * (BM / WM) + i * 32 + (rl & 31);
         if (rr < g.M) {
-          uint4 v = make_uint4(trlo[it].x, trlo[it].y, trhi[it].x, trhi[it].y);
+          uint4 v = cv[it];
           const int64_t off = (int64_t)rr * g.N + col0 + ch * 8;
-          if (pa.add_src) {
-            const uint4 av = *reinterpret_cast<const uint4*>(pa.add_src + off);
-            unsigned* vw = &v.x; const unsigned* aw = &av.x;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              float lo = ET::lo(vw[q]) + ET::lo(aw[q]);
-              float hi = ET::hi(vw[q]) + ET::hi(aw[q]);
-              if (affine && g.epi_relu) { lo = fmaxf(lo, 0.f); hi = fmaxf(hi, 0.f); }
-              vw[q] = ET::pack2(lo, hi);
-            }
-          }
+          if (pa.add_src) add_chunk<ET>(v, *reinterpret_cast<const uint4*>(pa.add_src + off), affine && g.epi_relu);
           if (!CREID_ABL_ON(g.abl, 8)) *reinterpret_cast<uint4*>(pa.out + off) = v;
         }
       }

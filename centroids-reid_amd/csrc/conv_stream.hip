@@ -14,13 +14,12 @@
 // stores, per-tile (sum, sum of squares) partials of the fp32 accumulators for the BatchNorm that follows).
 // Every wave executes the same sequence of s_barrier's by construction: one per k-chunk, then a fixed number per
 // epilogue; all loop bounds are workgroup-uniform.
-#include "conv_common.hpp"
+#include "conv_epilogue.hpp"
 #include <stdlib.h>
 
 __device__ __attribute__((aligned(128))) unsigned g_stream_zero_page[32];   // rows >= M fetch this page of zeros
 
 namespace {
-template <int N> __device__ __forceinline__ void st_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 __device__ __forceinline__ void st_barrier() { asm volatile("s_barrier" ::: "memory"); }
 }  // namespace
 
@@ -96,7 +95,7 @@ __global__ __launch_bounds__(512, 1) void igemm1x1_stream_kernel(const unsigned 
       for (int kc = 0; kc < KCH; ++kc, ++c) {
         // chunk c (and the weight slab, issued before it) has landed once at most the younger chunks are pending
         const int younger = issued - c - 1;
-        if (younger >= 2) st_wait_vm<8>(); else if (younger == 1) st_wait_vm<4>(); else st_wait_vm<0>();
+        if (younger >= 2) wait_vm<8>(); else if (younger == 1) wait_vm<4>(); else wait_vm<0>();
         st_barrier();                                              // B1(c)
         if (issued < n_chunks && issued - c < NSA) { issue(issued); ++issued; }   // into the slot chunk c-1 just left
       }
@@ -109,7 +108,7 @@ __global__ __launch_bounds__(512, 1) void igemm1x1_stream_kernel(const unsigned 
   }
 
   // ---- consumers
-  st_wait_vm<0>();                                                 // this wave's share of the weight slab
+  wait_vm<0>();                                                 // this wave's share of the weight slab
   int c = 0;
   for (int it = 0; it < n_iter; ++it) {
     const int tile_m = wg_in_group + it * groups, row0 = tile_m * 128;
@@ -243,8 +242,8 @@ int launch_stream1x1(int M, int K, int N, const void* src, const void* wgt, void
 // lacked (profiles/r02_stream1x1_experiment.md: it lost on wide outputs because 256 threads stored alone and the epilogue ran
 // serially after the MFMAs), and with the epilogues of the eval-mode forward:
 //   * all eight waves are alike: wave (wr, wc) multiplies rows wr * 32 .. + 31 of the 128-row tile against the 32-column blocks
-//     2 j + wc, stages them column-major (packed 8-byte LDS stores, read back through the transposing LDS read -- the copy-out of
-//     igemm_bf16_ws_kernel) and all 512 threads copy out;
+//     2 j + wc, stages them column-major (packed 8-byte LDS stores, read back through the transposing LDS read:
+//     conv_epilogue.hpp) and all 512 threads copy out;
 //   * everything a tile needs from memory is requested ONE TILE EARLIER and nothing is waited for inside the tile that issued
 //     it: the A rows of tile t + 2 and the residual chunks of tile t + 1 are loaded into registers at the top of tile t, the A
 //     registers of tile t + 1 (loaded a tile ago) go to the LDS ring there, and the finished 16-byte chunks of tile t - 1 are
@@ -401,13 +400,7 @@ __global__ __launch_bounds__(512, 2) void igemm1x1_stream2_kernel(const unsigned
       }
     }
   };
-  // copy-out map of one half (see igemm_bf16_ws_kernel): lane = 16 g4 + 4 q4 + t4 owns row t4 of a row quad, one column octet
-  const int t4 = lane & 3, q4 = (lane >> 2) & 3, g4 = lane >> 4;
-  auto unit_of = [&](int i, int& rl, int& ch) {
-    const int Q = (wave + 8 * i) * 16 + g4 * 4 + q4;
-    ch = Q % CPR;
-    rl = 4 * (Q / CPR) + t4;
-  };
+  auto unit_of = [&](int i, int& rl, int& ch) { copy_unit<8, CPR>(lane, wave, i, rl, ch); };   // copy-out map of one half
   uint4 resn[NH][NIT];                                  // residual chunks of the NEXT tile (loaded one tile ahead)
   uint4 outv[NH][NIT];                                  // finished chunks of the PREVIOUS tile (stored one tile late)
   auto load_res = [&](int it) {
@@ -509,7 +502,7 @@ __global__ __launch_bounds__(512, 2) void igemm1x1_stream2_kernel(const unsigned
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { const float v = acc[j][r]; s1 += v; s2 = fmaf(v, v, s2); }
-        s1 += __shfl_xor(s1, 32, 64); s2 += __shfl_xor(s2, 32, 64);
+        colsum_lane_halves(s1, s2);
         const int cl = (2 * j + wc) * 32 + l31;
         if (kh == 0) { red[(wr * 2 + 0) * BN + cl] = s1; red[(wr * 2 + 1) * BN + cl] = s2; }
       }
@@ -522,16 +515,7 @@ __global__ __launch_bounds__(512, 2) void igemm1x1_stream2_kernel(const unsigned
       for (int j = 0; j < TW; ++j) {
         if (((2 * j + wc) * 32) / HB != h) continue;              // (wave-uniform)
         const int cl = (2 * j + wc) * 32 - h * HB + l31;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int rl = wr * 32 + 8 * q + 4 * kh;
-          float v0 = acc[j][4 * q], v1 = acc[j][4 * q + 1], v2 = acc[j][4 * q + 2], v3 = acc[j][4 * q + 3];
-          if (epi_scale) {
-            v0 = fmaf(v0, sc[j], sh[j]); v1 = fmaf(v1, sc[j], sh[j]); v2 = fmaf(v2, sc[j], sh[j]); v3 = fmaf(v3, sc[j], sh[j]);
-            if (relu_now) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); v2 = fmaxf(v2, 0.f); v3 = fmaxf(v3, 0.f); }
-          }
-          *reinterpret_cast<uint2*>(&stage[cl * CPT + rl]) = make_uint2(ET::pack2(v0, v1), ET::pack2(v2, v3));
-        }
+        stage_block<ET>(&stage[cl * CPT + wr * 32 + 4 * kh], acc[j], epi_scale != nullptr, sc[j], sh[j], relu_now);
       }
       __syncthreads();                                            // the half is staged (and `red` is complete)
       if (h == 0 && bn_part) {
@@ -541,35 +525,12 @@ __global__ __launch_bounds__(512, 2) void igemm1x1_stream2_kernel(const unsigned
               (red[(0 * 2 + which) * BN + cl] + red[(1 * 2 + which) * BN + cl]) + (red[(2 * 2 + which) * BN + cl] + red[(3 * 2 + which) * BN + cl]);
         }
       }
-      u32x2 trlo[NIT], trhi[NIT];
-      {
-        const int sq = lane & 3, sj = (lane >> 2) & 3;
-#pragma unroll
-        for (int i = 0; i < NIT; ++i) {
-          const int Qs = (wave + 8 * i) * 16 + g4 * 4 + sq;
-          const unsigned addr = (unsigned)(uintptr_t)&stage[((Qs % CPR) * 8 + sj) * CPT + 4 * (Qs / CPR)];
-          asm volatile("ds_read_b64_tr_b16 %0, %2\n\tds_read_b64_tr_b16 %1, %2 offset:%3"
-                       : "=&v"(trlo[i]), "=&v"(trhi[i]) : "v"(addr), "i"(4 * CPT * 2) : "memory");
-        }
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-      for (int i = 0; i < NIT; ++i) asm volatile("" : "+v"(trlo[i]), "+v"(trhi[i]));
+      uint4 cv[NIT];
+      read_back_chunks<NIT, 8, CPR, CPT>(stage, lane, wave, cv);
 #pragma unroll
       for (int i = 0; i < NIT; ++i) {
-        uint4 v = make_uint4(trlo[i].x, trlo[i].y, trhi[i].x, trhi[i].y);
-        if (add_src) {
-          const uint4 a = resc[h][i];
-          unsigned* vw = &v.x; const unsigned* aw = &a.x;
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            float lo = ET::lo(vw[q]) + ET::lo(aw[q]);
-            float hi = ET::hi(vw[q]) + ET::hi(aw[q]);
-            if (epi_relu) { lo = fmaxf(lo, 0.f); hi = fmaxf(hi, 0.f); }
-            vw[q] = ET::pack2(lo, hi);
-          }
-        }
-        outv[h][i] = v;
+        if (add_src) add_chunk<ET>(cv[i], resc[h][i], epi_relu);
+        outv[h][i] = cv[i];
       }
     }
   }
@@ -777,12 +738,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3_c64_kernel(const unsigned shor
       *reinterpret_cast<uint4*>(slot + p * 64 + ((ch ^ ((p >> 1) & 7)) << 3)) = areg[u];
     }
   };
-  const int t4 = lane & 3, q4 = (lane >> 2) & 3, g4 = lane >> 4;
-  auto unit_of = [&](int i, int& rl, int& ch) {
-    const int Q = (wave + 8 * i) * 16 + g4 * 4 + q4;
-    ch = Q % CPR;
-    rl = 4 * (Q / CPR) + t4;
-  };
   uint4 outv[NIT];
   auto store_out = [&](int it) {
     const int64_t row0 = (int64_t)(t_begin + it) * 128;
@@ -791,7 +746,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_c64_kernel(const unsigned shor
 #pragma unroll
     for (int i = 0; i < NIT; ++i) {
       int rl, ch;
-      unit_of(i, rl, ch);
+      copy_unit<8, CPR>(lane, wave, i, rl, ch);
       int64_t pixel = row0 + rl;
       if constexpr (T2D) pixel = ((int64_t)b * H + y0 + rl / TW) * Wimg + x0 + (rl % TW);
       if (!CREID_ABL_ON(abl, 8)) *reinterpret_cast<uint4*>(out + pixel * 64 + ch * 8) = outv[i];
@@ -856,23 +811,11 @@ __global__ __launch_bounds__(512, 2) void conv3x3_c64_kernel(const unsigned shor
       float s1 = 0.f, s2 = 0.f;
 #pragma unroll
       for (int r = 0; r < 16; ++r) { const float v = acc[r]; s1 += v; s2 = fmaf(v, v, s2); }
-      s1 += __shfl_xor(s1, 32, 64); s2 += __shfl_xor(s2, 32, 64);
+      colsum_lane_halves(s1, s2);
       if (kh == 0) { red[(wr * 2 + 0) * 64 + wc * 32 + l31] = s1; red[(wr * 2 + 1) * 64 + wc * 32 + l31] = s2; }
     }
     if (CREID_ABL_ON(abl, 4)) continue;                           // (timing ablation: no staging / copy-out)
-    {
-      const int cl = wc * 32 + l31;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int rl = wr * 32 + 8 * q + 4 * kh;
-        float v0 = acc[4 * q], v1 = acc[4 * q + 1], v2 = acc[4 * q + 2], v3 = acc[4 * q + 3];
-        if (epi_scale) {
-          v0 = fmaf(v0, sc, sh); v1 = fmaf(v1, sc, sh); v2 = fmaf(v2, sc, sh); v3 = fmaf(v3, sc, sh);
-          if (epi_relu) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); v2 = fmaxf(v2, 0.f); v3 = fmaxf(v3, 0.f); }
-        }
-        *reinterpret_cast<uint2*>(&stage[cl * CPT + rl]) = make_uint2(ET::pack2(v0, v1), ET::pack2(v2, v3));
-      }
-    }
+    stage_block<ET>(&stage[(wc * 32 + l31) * CPT + wr * 32 + 4 * kh], acc, epi_scale != nullptr, sc, sh, epi_relu);
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // the tile is staged (and `red` is complete): LDS only --
                                                                   // __syncthreads() would also wait for this tile's loads / stores
     if (bn_part) {
@@ -882,22 +825,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_c64_kernel(const unsigned shor
             (red[(0 * 2 + which) * 64 + cl] + red[(1 * 2 + which) * 64 + cl]) + (red[(2 * 2 + which) * 64 + cl] + red[(3 * 2 + which) * 64 + cl]);
       }
     }
-    u32x2 trlo[NIT], trhi[NIT];
-    {
-      const int sq = lane & 3, sj = (lane >> 2) & 3;
-#pragma unroll
-      for (int i = 0; i < NIT; ++i) {
-        const int Qs = (wave + 8 * i) * 16 + g4 * 4 + sq;
-        const unsigned addr = (unsigned)(uintptr_t)&stage[((Qs % CPR) * 8 + sj) * CPT + 4 * (Qs / CPR)];
-        asm volatile("ds_read_b64_tr_b16 %0, %2\n\tds_read_b64_tr_b16 %1, %2 offset:%3"
-                     : "=&v"(trlo[i]), "=&v"(trhi[i]) : "v"(addr), "i"(4 * CPT * 2) : "memory");
-      }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-    for (int i = 0; i < NIT; ++i) asm volatile("" : "+v"(trlo[i]), "+v"(trhi[i]));
-#pragma unroll
-    for (int i = 0; i < NIT; ++i) outv[i] = make_uint4(trlo[i].x, trlo[i].y, trhi[i].x, trhi[i].y);
+    read_back_chunks<NIT, 8, CPR, CPT>(stage, lane, wave, outv);
   }
   store_out(n_iter - 1);
 }

@@ -1123,13 +1123,8 @@ static int conv_wgrad_phases(const creid_conv_desc* d, const void* x, const void
                              void* ws, size_t ws_bytes, int dtype, void* stream, int phases, const BnBwdFinJob* fin) {
   CREID_CHECK_ARG(d && ws);
   if (ilog2x(d->in_c) < 0 || d->in_c < 64 || d->out_c % 64 != 0) return CREID_E_SHAPE;
-  IGemmGeom g;
-  g.M = (int)(d->batch * d->out_h * d->out_w); g.OH = (int)d->out_h; g.OW = (int)d->out_w;
-  g.SH = (int)d->in_h; g.SW = (int)d->in_w; g.pitch = (int)d->in_c; g.log2span = ilog2x(d->in_c);
-  g.kw = d->kw; g.stride = d->stride; g.pad = d->pad; g.transposed = 0;
-  g.K = (int)(d->kh * d->kw * d->in_c); g.N = (int)d->out_c; g.check_bounds = 1;
+  IGemmGeom g = fwd_geom(d);
   { static const int noinc = [] { const char* e = getenv("CREID_WGRAD_NOINC"); return e ? atoi(e) : 0; }(); if (noinc) g.check_bounds = 2; }
-  igemm_finish_geom(g);
   return run_wgrad(g, dy, x, (int)d->out_c, dw_oihw, d->kw, (int)d->in_c, (int)d->in_c, d->kh, d->kw, accumulate, ws,
                    ws_bytes, dtype, as_stream(stream), phases, fin);
 }
@@ -1145,12 +1140,7 @@ int creid_conv2d_wgrad_x3_partials(const creid_conv_desc* d, const void* x, cons
   const int rc = conv_check_desc(d);
   if (rc) return rc;
   CREID_CHECK_ARG(x && dy && ws);
-  IGemmGeom g;
-  g.M = (int)(d->batch * d->out_h * d->out_w); g.OH = (int)d->out_h; g.OW = (int)d->out_w;
-  g.SH = (int)d->in_h; g.SW = (int)d->in_w; g.pitch = (int)d->in_c; g.log2span = ilog2x(d->in_c);
-  g.kw = d->kw; g.stride = d->stride; g.pad = d->pad; g.transposed = 0;
-  g.K = (int)(d->kh * d->kw * d->in_c); g.N = (int)d->out_c; g.check_bounds = 1;
-  igemm_finish_geom(g);
+  IGemmGeom g = fwd_geom(d);
   const int NCO = (int)d->out_c;
   const WgradPlan p = plan_wgrad(g.M, NCO, g.K, CREID_F32, g.stride);
   if (ws_bytes < (size_t)p.splits * NCO * g.K * sizeof(float)) return CREID_E_WS;
@@ -1189,11 +1179,7 @@ int creid_stem_conv_wgrad(int64_t batch, int64_t H, int64_t W, const void* xpad,
                           int accumulate, void* ws, size_t ws_bytes, int dtype, void* stream) {
   CREID_CHECK_ARG(xpad && dy && dw_oihw && ws && batch > 0 && H > 0 && W > 0);
   if (H % 2 || W % 2) return CREID_E_SHAPE;
-  IGemmGeom g;
-  g.M = (int)(batch * (H / 2) * (W / 2)); g.OH = (int)(H / 2); g.OW = (int)(W / 2);
-  g.SH = (int)(H + 8); g.SW = (int)(W + 6); g.pitch = 4; g.log2span = 5;
-  g.kw = 1; g.stride = 2; g.pad = 0; g.transposed = 0; g.K = 256; g.N = 64; g.check_bounds = 0;
-  igemm_finish_geom(g);
+  IGemmGeom g = stem_geom(batch, H, W);
   return run_wgrad(g, dy, xpad, 64, dw_oihw, 1, 4, 3, 7, 7, accumulate, ws, ws_bytes, dtype, as_stream(stream));
 }
 
