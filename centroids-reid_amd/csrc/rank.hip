@@ -8,6 +8,7 @@
 // Stability makes ties resolve by gallery index.  The row (n x 16 B of scratch) stays
 // L2-resident; HBM traffic is the 4 B/pair read of the matrix and the 8 B/pair index write.
 #include "common.hpp"
+#include "topk_tail.hpp"
 #include <stdlib.h>
 
 namespace {
@@ -511,9 +512,6 @@ __device__ __forceinline__ unsigned tk_key(float d) {
   const unsigned u = __float_as_uint(d);
   return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
 }
-__device__ __forceinline__ float tk_unkey(unsigned k) {
-  return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu));
-}
 }  // namespace
 
 __global__ __launch_bounds__(TK_T) void topk_rows_kernel(const float* __restrict__ dist, int n, int64_t ld, int k,
@@ -567,27 +565,8 @@ __global__ __launch_bounds__(TK_T) void topk_rows_kernel(const float* __restrict
     const unsigned key = tk_key(row[j]);
     if (bucket(key) <= bstar) cand[atomicAdd(&s_cnt, 1u)] = ((unsigned long long)key << 32) | (unsigned)j;
   }
-  int S = 1;
-  while (S < total) S <<= 1;
   __syncthreads();
-  for (int i = total + tid; i < S; i += TK_T) cand[i] = ~0ull;
-  __syncthreads();
-  for (int sz = 2; sz <= S; sz <<= 1) {
-    for (int st = sz >> 1; st > 0; st >>= 1) {
-      for (int i = tid; i < (S >> 1); i += TK_T) {
-        const int a = ((i / st) * st * 2) + (i % st), b = a + st;
-        const bool up = ((a & sz) == 0);
-        const unsigned long long x = cand[a], y = cand[b];
-        if ((x > y) == up) { cand[a] = y; cand[b] = x; }
-      }
-      __syncthreads();
-    }
-  }
-  for (int t = tid; t < k; t += TK_T) {
-    const unsigned long long c = cand[t];
-    out_idx[(int64_t)blockIdx.x * k + t] = (int64_t)(c & 0xffffffffull);
-    if (out_dist) out_dist[(int64_t)blockIdx.x * k + t] = tk_unkey((unsigned)(c >> 32));
-  }
+  tk_sort_emit<TK_T>(cand, total, k, blockIdx.x, out_idx, out_dist);
   if (tid == 0) flags[blockIdx.x] = 0;
 }
 

@@ -15,12 +15,19 @@
 // v_mfma_f32_32x32x2_f32 accumulation is the sequential fmaf chain over k, which kernel 1 reproduces with plain
 // fmaf in the same order, and both use the same "(qq + gg) - 2 dot" epilogue, so positives and negatives compare
 // on identical bits and ties resolve by gallery index exactly like the stable rank kernel.
+//
+// Stream top-k retrieval (inference/get_similar.py:99-125 on a gallery whose m x n matrix should not exist) is the second
+// consumer of the same contraction: sqdist_count_f32_kernel<.., EPI_TOPK> keeps the k-loop, staging and work split and
+// swaps the epilogue for "append (distance, column) to the row's candidate list when the distance is within the row's
+// threshold"; stream_topk_select_kernel sorts each list and keeps the first k.
 #include "common.hpp"
+#include "topk_tail.hpp"
 #include <stdlib.h>
 #include <type_traits>
 
 namespace {
 constexpr int SQ_TM = 64, SQ_TN = 256, SQ_BK = 16;
+constexpr int EPI_COUNT = 0, EPI_TOPK = 1;       // what sqdist_count_f32_kernel does with a finished tile
 // LDS operand image of one 16-deep k-tile: [kh = k & 1][quarter = k >> 2][row][e = (k >> 1) & 1] -- the per-lane MFMA operand is
 // A[i = lane & 31][k = 2 step + (lane >> 5)], so the two values a lane feeds to the two steps of a quarter are one 8-byte unit:
 // a quarter's fragments are 1 + 4 ds_read_b64 per lane (32 lanes x 8 B = one conflict-free 256-B row of banks), and the staging
@@ -147,18 +154,28 @@ __global__ __launch_bounds__(PL_MAXC) void stream_poslist_kernel(
 //          units, where per-row splitting left 2228 x 17661 at 5 tile-times for 4.72 tiles of work per slot (and 3000 x 15000 at
 //          6 for 5.42).  Measured without the gallery sharing of mode 0: no loss at these sizes (profiles/r06_eval_kloop.md).
 // (!FULLK -- a feature width that is not a multiple of 16 -- carries the zero-fill masks on top and runs one workgroup per CU.)
-template <int ABL, bool FULLK>
+//
+// EPI selects the epilogue; everything up to the finished accumulator tile is common.
+//   EPI_COUNT: the evaluation's count described above (the arguments from q_pids to hist_out and skip_count; tau / cand /
+//              cand_count unused).
+//   EPI_TOPK : retrieval.  Every element inside the problem whose key = mono_key(fmaf(-2, acc, qq[row] + gg[col])) -- the bits of
+//              creid_sqdist_matrix -- is <= mono_key(tau[row]) takes a slot of its row's list with a global atomicAdd on
+//              cand_count[row] and, while the slot is below `cap`, stores key << 32 | col there.  Hits are rare (a few hundred
+//              to a thousand of a row's n columns), so the atomics are not a cost.  LDS state per tile: the 64 threshold keys
+//              (s_kmax) next to s_qq; no dynamic LDS; the label / list arguments of the count are unused.
+template <int ABL, bool FULLK, int EPI = EPI_COUNT>
 __global__ __launch_bounds__(256, FULLK ? 2 : 1) void sqdist_count_f32_kernel(
     const float* __restrict__ q, const float* __restrict__ g, const float* __restrict__ qq, const float* __restrict__ gg,
     int m, int n, int D, const int64_t* __restrict__ q_pids, const int64_t* __restrict__ g_pids, int cap, int log2cap,
     const unsigned* __restrict__ pos_key, const int32_t* __restrict__ pos_idx, const int32_t* __restrict__ npos,
-    unsigned* __restrict__ hist_out, int tiles_m, int U, int upw, int mode, int skip_count) {
+    unsigned* __restrict__ hist_out, int tiles_m, int U, int upw, int mode, int skip_count,
+    const float* __restrict__ tau, unsigned long long* __restrict__ cand, int32_t* __restrict__ cand_count) {
   __shared__ __attribute__((aligned(16))) float As[2][2][4][SQ_PA];
   __shared__ __attribute__((aligned(16))) float Bs[2][2][4][SQ_PB];
   __shared__ float s_qq[SQ_TM];
   __shared__ long long s_qpid[SQ_TM];
   __shared__ int s_np[SQ_TM];
-  __shared__ unsigned s_kmax[SQ_TM];
+  __shared__ unsigned s_kmax[SQ_TM];             // count: key of the row's last positive; top-k: key of the row's threshold
   extern __shared__ __attribute__((aligned(16))) unsigned dyn[];
   unsigned* s_keys = dyn;                        // [64][cap]
   unsigned* s_hist = dyn + SQ_TM * cap;          // [64][cap]
@@ -344,14 +361,36 @@ __global__ __launch_bounds__(256, FULLK ? 2 : 1) void sqdist_count_f32_kernel(
     int rbase = wm * 32 + 4 * kh;                  // opaque per tile: the 16 rows' LDS addresses derived from it are recomputed here
     asm volatile("" : "+v"(rbase));                // instead of living in registers (or scratch) across the k-loop
     float gv[NJ];
-    long long gp[NJ];
+    [[maybe_unused]] long long gp[NJ];
     bool okc[NJ];
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
       const int c = col0 + (wn + 2 * j) * 32 + l31;
       okc[j] = c < n;
       gv[j] = okc[j] ? gg[c] : 0.f;
-      gp[j] = okc[j] ? (long long)g_pids[c] : 0;
+      if constexpr (EPI == EPI_COUNT) gp[j] = okc[j] ? (long long)g_pids[c] : 0;
+    }
+    if constexpr (EPI == EPI_TOPK) {
+      // One accumulator row at a time: its threshold is one LDS read, a hit one global atomic (rows beyond m multiply a
+      // clamped copy of the last query row and are dropped here, like columns beyond n).
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int rl = rbase + (r & 3) + 8 * (r >> 2);
+        const float qv = s_qq[rl];
+        const unsigned kt = s_kmax[rl];
+        const bool okr = row0 + rl < m;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+          const unsigned key = mono_key(fmaf(-2.0f, acc[j][r], qv + gv[j]));
+          if (okr && okc[j] && key <= kt) {
+            const int64_t rr = row0 + rl;
+            const int slot = atomicAdd(&cand_count[rr], 1);
+            if (slot < cap)
+              cand[rr * cap + slot] = ((unsigned long long)key << 32) | (unsigned)(col0 + (wn + 2 * j) * 32 + l31);
+          }
+        }
+      }
+      return;
     }
     // Two accumulator rows x NJ column blocks = 2 NJ binary searches in flight per lane: the search is a chain of
     // dependent LDS reads (~100 cycles each), so it is the number of INDEPENDENT chains that sets the epilogue time.
@@ -411,18 +450,26 @@ __global__ __launch_bounds__(256, FULLK ? 2 : 1) void sqdist_count_f32_kernel(
     __syncthreads();                               // the previous segment's histogram has been flushed
     int ts = tid;                                  // opaque: the set-up's LDS addresses are recomputed per segment instead of
     asm volatile("" : "+v"(ts));                   // occupying registers (or scratch) across the k-loops
-    for (int i = ts; i < SQ_TM * cap; i += 256) {
-      const int r = i >> log2cap, rr = row0 + r;
-      s_keys[i] = rr < m ? pos_key[(int64_t)rr * cap + (i & (cap - 1))] : 0xffffffffu;
-      s_hist[i] = 0u;
-    }
-    if (ts < SQ_TM) {
-      const int rr = row0 + ts;
-      const int np = rr < m ? npos[rr] : 0;
-      s_np[ts] = np > 0 ? np : 0;
-      s_qq[ts] = rr < m ? qq[rr] : 0.f;
-      s_qpid[ts] = rr < m ? (long long)q_pids[rr] : 0;
-      s_kmax[ts] = np > 0 ? pos_key[(int64_t)rr * cap + np - 1] : 0u;
+    if constexpr (EPI == EPI_TOPK) {
+      if (ts < SQ_TM) {
+        const int rr = row0 + ts;
+        s_qq[ts] = rr < m ? qq[rr] : 0.f;
+        s_kmax[ts] = rr < m ? mono_key(tau[rr]) : 0u;
+      }
+    } else {
+      for (int i = ts; i < SQ_TM * cap; i += 256) {
+        const int r = i >> log2cap, rr = row0 + r;
+        s_keys[i] = rr < m ? pos_key[(int64_t)rr * cap + (i & (cap - 1))] : 0xffffffffu;
+        s_hist[i] = 0u;
+      }
+      if (ts < SQ_TM) {
+        const int rr = row0 + ts;
+        const int np = rr < m ? npos[rr] : 0;
+        s_np[ts] = np > 0 ? np : 0;
+        s_qq[ts] = rr < m ? qq[rr] : 0.f;
+        s_qpid[ts] = rr < m ? (long long)q_pids[rr] : 0;
+        s_kmax[ts] = np > 0 ? pos_key[(int64_t)rr * cap + np - 1] : 0u;
+      }
     }
     abase = reinterpret_cast<const char*>(q + (int64_t)min(row0, m - 1) * D);
     aoff = (unsigned)(min(row0 + lrow, m - 1) - min(row0, m - 1)) * (unsigned)D * 4u + 16u * lkc;
@@ -438,11 +485,13 @@ __global__ __launch_bounds__(256, FULLK ? 2 : 1) void sqdist_count_f32_kernel(
       else tile(std::integral_constant<int, 1>{}, col, next);
       col += 256;
     }
-    __syncthreads();
-    for (int i = ts; i < SQ_TM * cap; i += 256) {
-      const unsigned v = s_hist[i];
-      const int rr = row0 + (i >> log2cap);
-      if (v && rr < m) atomicAdd(&hist_out[(int64_t)rr * cap + (i & (cap - 1))], v);      // integer: order-independent
+    if constexpr (EPI == EPI_COUNT) {
+      __syncthreads();
+      for (int i = ts; i < SQ_TM * cap; i += 256) {
+        const unsigned v = s_hist[i];
+        const int rr = row0 + (i >> log2cap);
+        if (v && rr < m) atomicAdd(&hist_out[(int64_t)rr * cap + (i & (cap - 1))], v);      // integer: order-independent
+      }
     }
   }
 }
@@ -549,6 +598,64 @@ __global__ __launch_bounds__(256) void plan_query_kernel(const int64_t* __restri
   }
 }
 
+// ----------------------------------------------------------------------------------------
+// 4. retrieval: the k nearest of every candidate list the EPI_TOPK contraction collected.  One workgroup per query; the list
+//    (count <= cap words of key << 32 | column, in the order the atomics gave) goes to LDS and through the sort tail of
+//    topk_rows_kernel.  A list that overflowed (count > cap: entries were dropped) or holds fewer than k entries (NaN
+//    distances never pass the threshold) is flagged and nothing is written for the row.
+// ----------------------------------------------------------------------------------------
+constexpr int TS_T = 1024, TS_MIN_CAP = 64, TS_MAX_CAP = 8192;
+
+__global__ __launch_bounds__(TS_T) void stream_topk_select_kernel(const unsigned long long* __restrict__ cand,
+                                                                  const int32_t* __restrict__ count, int cap, int k,
+                                                                  int64_t* __restrict__ out_idx, float* __restrict__ out_dist,
+                                                                  uint8_t* __restrict__ flags) {
+  extern __shared__ __attribute__((aligned(16))) unsigned long long s_cand[];      // [cap]
+  const int tid = threadIdx.x;
+  const int64_t row = blockIdx.x;
+  const int c = count[row];                                                        // (uniform)
+  if (c > cap || c < k) { if (tid == 0) flags[row] = 1; return; }
+  for (int i = tid; i < c; i += TS_T) s_cand[i] = cand[row * cap + i];
+  __syncthreads();
+  tk_sort_emit<TS_T>(s_cand, c, k, row, out_idx, out_dist);
+  if (tid == 0) flags[row] = 0;
+}
+
+/* The work split of the streamed contraction (sqdist_count_f32_kernel, both epilogues). */
+struct StreamSplit { int tiles_m, U, upw, mode; unsigned grid; };
+static StreamSplit stream_split(int64_t m, int64_t n, int64_t D) {
+  const int tiles_m = (int)((m + SQ_TM - 1) / SQ_TM), tiles_n = (int)((n + SQ_TN - 1) / SQ_TN);
+  const int U = (int)((n + 63) / 64);                           // units of 64 gallery columns per row of query tiles
+  // enough workgroups for two per CU, but never fewer than ~4 gallery tiles per workgroup (per-tile restart cost)
+  static const int target = [] { const char* e = getenv("CREID_STREAM_WGS"); int v = e ? atoi(e) : 0; return v > 0 ? v : 512; }();
+  // mode 0: never MORE than `tper_max` gallery tiles per workgroup: the grid overshoots the 512 slots by up to tiles_m - 1
+  // workgroups, which start when the first ones finish -- harmless when a workgroup is 5 tiles long, a whole second round on an
+  // idle chip when it is 131 (6250 x 200 000: 588 workgroups, 66.0 ms; with <= 8 tiles per workgroup 46.1 ms; HBM-side traffic by
+  // the counters the same under both rules -- profiles/r05_stream_grid.md)
+  static const int tper_max = [] { const char* e = getenv("CREID_STREAM_TPER"); int v = e ? atoi(e) : 0; return v > 0 ? v : 8; }();
+  int nsplit = (target + tiles_m - 1) / tiles_m;
+  if (nsplit < (tiles_n + tper_max - 1) / tper_max) nsplit = (tiles_n + tper_max - 1) / tper_max;
+  if (nsplit > tiles_n) nsplit = tiles_n;
+  if (nsplit < 1) nsplit = 1;
+  const int t_per = (tiles_n + nsplit - 1) / nsplit;
+  nsplit = (tiles_n + t_per - 1) / t_per;                       // drop empty slices
+  // mode 1 (equal runs of units over the resident slots): only while the gallery fits the Infinity Cache beside the queries, the
+  // grid of mode 0 is a single round, and the equal run is shorter than mode 0's longest workgroup by more than the narrow tile
+  // and the second segment cost (~a quarter tile: 2228 x 17661 -- 4.75 tiles against 5 -- measured EQUAL in both modes,
+  // 3000 x 15000 -- 5.5 against 6 -- 5.6 % faster in mode 1; profiles/r06_eval_kloop.md).  CREID_STREAM_BALANCE=0 / 1 forces a
+  // mode (the tests run both).
+  const long long T = (long long)tiles_m * U;
+  const long long wg1 = T / 4 < target ? (T / 4 > 0 ? T / 4 : 1) : target;
+  const char* bal_e = CREID_KNOB_ENV("CREID_STREAM_BALANCE");
+  const int bal = (bal_e && *bal_e) ? atoi(bal_e) : -1;
+  const double run1 = (double)((T + wg1 - 1) / wg1) / 4.0 + 0.3;
+  const int mode = bal >= 0 ? (bal != 0)
+                            : ((double)n * (double)D * 4.0 <= 192e6 && (long long)tiles_m * nsplit <= target && run1 < (double)t_per);
+  const int upw = 4 * t_per;
+  const unsigned grid = mode == 0 ? (unsigned)(tiles_m * nsplit) : (unsigned)wg1;
+  return StreamSplit{tiles_m, U, upw, mode, grid};
+}
+
 extern "C" {
 
 /* Device-side index for the streamed evaluation.  g_pids / g_cams int64[n], q_pids / q_cams int64[m] on the device; the pid
@@ -601,37 +708,9 @@ int creid_stream_count(const float* q, const float* g, const float* qq, const fl
   if (n > 0x7ffffff0LL || m > 0x7ffffff0LL) return CREID_E_SHAPE;
   int log2cap = 0;
   while ((1 << log2cap) < cap) ++log2cap;
-  const int tiles_m = (int)((m + SQ_TM - 1) / SQ_TM), tiles_n = (int)((n + SQ_TN - 1) / SQ_TN);
-  const int U = (int)((n + 63) / 64);                           // units of 64 gallery columns per row of query tiles
-  // enough workgroups for two per CU, but never fewer than ~4 gallery tiles per workgroup (per-tile restart cost)
-  static const int target = [] { const char* e = getenv("CREID_STREAM_WGS"); int v = e ? atoi(e) : 0; return v > 0 ? v : 512; }();
   // timing ablation only (CREID_STREAM_NOEPI=1: contraction without the count epilogue -- results are then wrong)
   static const int skip_count = creid_ablation_env("CREID_STREAM_NOEPI");
-  // mode 0: never MORE than `tper_max` gallery tiles per workgroup: the grid overshoots the 512 slots by up to tiles_m - 1
-  // workgroups, which start when the first ones finish -- harmless when a workgroup is 5 tiles long, a whole second round on an
-  // idle chip when it is 131 (6250 x 200 000: 588 workgroups, 66.0 ms; with <= 8 tiles per workgroup 46.1 ms; HBM-side traffic by
-  // the counters the same under both rules -- profiles/r05_stream_grid.md)
-  static const int tper_max = [] { const char* e = getenv("CREID_STREAM_TPER"); int v = e ? atoi(e) : 0; return v > 0 ? v : 8; }();
-  int nsplit = (target + tiles_m - 1) / tiles_m;
-  if (nsplit < (tiles_n + tper_max - 1) / tper_max) nsplit = (tiles_n + tper_max - 1) / tper_max;
-  if (nsplit > tiles_n) nsplit = tiles_n;
-  if (nsplit < 1) nsplit = 1;
-  const int t_per = (tiles_n + nsplit - 1) / nsplit;
-  nsplit = (tiles_n + t_per - 1) / t_per;                       // drop empty slices
-  // mode 1 (equal runs of units over the resident slots): only while the gallery fits the Infinity Cache beside the queries, the
-  // grid of mode 0 is a single round, and the equal run is shorter than mode 0's longest workgroup by more than the narrow tile
-  // and the second segment cost (~a quarter tile: 2228 x 17661 -- 4.75 tiles against 5 -- measured EQUAL in both modes,
-  // 3000 x 15000 -- 5.5 against 6 -- 5.6 % faster in mode 1; profiles/r06_eval_kloop.md).  CREID_STREAM_BALANCE=0 / 1 forces a
-  // mode (the tests run both).
-  const long long T = (long long)tiles_m * U;
-  const long long wg1 = T / 4 < target ? (T / 4 > 0 ? T / 4 : 1) : target;
-  const char* bal_e = CREID_KNOB_ENV("CREID_STREAM_BALANCE");
-  const int bal = (bal_e && *bal_e) ? atoi(bal_e) : -1;
-  const double run1 = (double)((T + wg1 - 1) / wg1) / 4.0 + 0.3;
-  const int mode = bal >= 0 ? (bal != 0)
-                            : ((double)n * (double)D * 4.0 <= 192e6 && (long long)tiles_m * nsplit <= target && run1 < (double)t_per);
-  const int upw = 4 * t_per;
-  const unsigned grid = mode == 0 ? (unsigned)(tiles_m * nsplit) : (unsigned)wg1;
+  const StreamSplit sp = stream_split(m, n, D);
   const size_t dyn = (size_t)2 * SQ_TM * cap * sizeof(unsigned);
 #define CREID_COUNT_LAUNCH_(A, F)                                                                                     \
   do {                                                                                                                 \
@@ -639,9 +718,10 @@ int creid_stream_count(const float* q, const float* g, const float* qq, const fl
                                                           hipFuncAttributeMaxDynamicSharedMemorySize,                  \
                                                           2 * SQ_TM * PL_MAXC * (int)sizeof(unsigned));                \
     if (attr_rc != hipSuccess) return (int)attr_rc;                                                                    \
-    hipLaunchKernelGGL((sqdist_count_f32_kernel<A, F>), dim3(grid), dim3(256), dyn, as_stream(stream),                 \
+    hipLaunchKernelGGL((sqdist_count_f32_kernel<A, F>), dim3(sp.grid), dim3(256), dyn, as_stream(stream),              \
                        q, g, qq, gg, (int)m, (int)n, (int)D, q_pids, g_pids, (int)cap, log2cap, pos_key, pos_idx, npos, hist,  \
-                       tiles_m, U, upw, mode, skip_count & 1);                                                         \
+                       sp.tiles_m, sp.U, sp.upw, sp.mode, skip_count & 1, (const float*)nullptr,                       \
+                       (unsigned long long*)nullptr, (int32_t*)nullptr);                                               \
   } while (0)
 #define CREID_COUNT_LAUNCH(A)                                                                                          \
   do { if (D % SQ_BK == 0) CREID_COUNT_LAUNCH_(A, true); else CREID_COUNT_LAUNCH_(0, false); } while (0)
@@ -673,6 +753,37 @@ int creid_stream_finalize(const int32_t* npos, const uint32_t* hist, int64_t m, 
   CREID_CHECK_ARG(npos && hist && valid && ap && first && cap >= 2);
   hipLaunchKernelGGL(stream_finalize_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, as_stream(stream), npos, hist,
                      (int)m, (int)cap, valid, ap, first);
+  CREID_LAUNCH_RET();
+}
+
+int creid_stream_topk_collect(const float* q, const float* g, const float* qq, const float* gg, int64_t m, int64_t n,
+                              int64_t D, const float* tau, int32_t cap, uint64_t* cand, int32_t* count, void* stream) {
+  CREID_CHECK_ARG(m >= 0 && n > 0 && D > 0);
+  if (cap < TS_MIN_CAP || cap > TS_MAX_CAP || (cap & (cap - 1)) != 0 || D % 4 != 0) return CREID_E_SHAPE;
+  if (n > 0x7ffffff0LL || m > 0x7ffffff0LL) return CREID_E_SHAPE;
+  if (m == 0) return 0;
+  CREID_CHECK_ARG(q && g && qq && gg && tau && cand && count);
+  const StreamSplit sp = stream_split(m, n, D);
+#define CREID_TOPK_LAUNCH(F)                                                                                            \
+  hipLaunchKernelGGL((sqdist_count_f32_kernel<0, F, EPI_TOPK>), dim3(sp.grid), dim3(256), 0, as_stream(stream),         \
+                     q, g, qq, gg, (int)m, (int)n, (int)D, (const int64_t*)nullptr, (const int64_t*)nullptr, (int)cap, 0, \
+                     (const unsigned*)nullptr, (const int32_t*)nullptr, (const int32_t*)nullptr, (unsigned*)nullptr,    \
+                     sp.tiles_m, sp.U, sp.upw, sp.mode, 0, tau, reinterpret_cast<unsigned long long*>(cand), count)
+  if (D % SQ_BK == 0) CREID_TOPK_LAUNCH(true); else CREID_TOPK_LAUNCH(false);
+#undef CREID_TOPK_LAUNCH
+  CREID_LAUNCH_RET();
+}
+
+int creid_stream_topk_select(const uint64_t* cand, const int32_t* count, int64_t m, int32_t cap, int32_t k, int64_t* out_idx,
+                             float* out_dist, uint8_t* flags, void* stream) {
+  CREID_CHECK_ARG(m >= 0 && k >= 1);
+  if (cap < TS_MIN_CAP || cap > TS_MAX_CAP || (cap & (cap - 1)) != 0 || k > 1024 || k > cap) return CREID_E_SHAPE;
+  if (m > 0x7fffffffLL) return CREID_E_SHAPE;
+  if (m == 0) return 0;
+  CREID_CHECK_ARG(cand && count && out_idx && flags);
+  hipLaunchKernelGGL(stream_topk_select_kernel, dim3((unsigned)m), dim3(TS_T), (size_t)cap * sizeof(unsigned long long),
+                     as_stream(stream), reinterpret_cast<const unsigned long long*>(cand), count, (int)cap, (int)k, out_idx,
+                     out_dist, flags);
   CREID_LAUNCH_RET();
 }
 

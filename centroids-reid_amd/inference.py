@@ -126,21 +126,59 @@ def load_gallery(load_dir):
     return np.load(d / "embeddings.npy", allow_pickle=True), np.load(d / "paths.npy", allow_pickle=True)
 
 
+STREAM_MATRIX_BYTES = 1 << 30      # get_similar(streamed="auto"): an m x n fp32 matrix beyond this is not materialised whole
+
+
+def _similar_materialised(q, g, topk, distance_func):
+    """The m x n matrix and its ranking: (indices, distances) as host arrays."""
+    distmat = rm.get_dist_func(distance_func)(x=q, y=g).contiguous()
+    if topk:                                                   # top-k selection kernel: no full sort of the row
+        indices, dist_sel = rm.topk_rows(distmat, min(int(topk), distmat.shape[1]))
+    else:
+        indices = rm.rank_rows(distmat)
+        dist_sel = torch.gather(distmat, 1, indices)
+    return indices.cpu().numpy(), dist_sel.cpu().numpy()
+
+
 def get_similar(embeddings, paths, embeddings_gallery, paths_gallery, topk=0, normalize_features=True,
-                distance_func="euclidean"):
-    """inference/get_similar.py:99-125 -> {query_path: {"indices", "paths", "distances"}} (numpy arrays)."""
+                distance_func="euclidean", streamed="auto", stats=None):
+    """inference/get_similar.py:99-125 -> {query_path: {"indices", "paths", "distances"}} (numpy arrays).
+
+    streamed: False -- the m x n distance matrix is written and every row selected from it (get_dist_func + topk_rows /
+    rank_rows).  True -- reid_metric.topk_stream: the same indices and distance bits with no matrix; squared-L2 top-k only
+    (CreidError for cosine, topk = 0 or k > 1024).  "auto" -- the matrix path unless it would exceed STREAM_MATRIX_BYTES; then
+    the streamed path when the call is streamable and its threshold sample is at most a quarter of the gallery, else the
+    matrix path over chunks of query rows (the result is the same, the matrix never exists whole).
+    stats (a dict) receives "path" ("materialised" | "streamed" | "chunked") and topk_stream's counters."""
+    if streamed not in (True, False, "auto"):
+        raise ValueError(f"streamed must be True, False or 'auto', got {streamed!r}")
     q = torch.as_tensor(np.asarray(embeddings, np.float32)).cuda() if not isinstance(embeddings, torch.Tensor) else embeddings.float().cuda()
     g = torch.as_tensor(np.asarray(embeddings_gallery, np.float32)).cuda() if not isinstance(embeddings_gallery, torch.Tensor) else embeddings_gallery.float().cuda()
     if normalize_features:
         q, g = rm.l2_normalize(q.contiguous()), rm.l2_normalize(g.contiguous())
-    distmat = rm.get_dist_func(distance_func)(x=q.contiguous(), y=g.contiguous()).contiguous()
-    if topk:                                                   # top-k selection kernel: no full sort of the row
-        indices, dist_sel = rm.topk_rows(distmat, min(int(topk), distmat.shape[1]))
-        dist_sel = dist_sel.cpu().numpy()
+    q, g = q.contiguous(), g.contiguous()
+    m, n = q.shape[0], g.shape[0]
+    k = min(int(topk), n) if topk else 0
+    streamable = distance_func == "euclidean" and 1 <= k <= 1024
+    if streamed is True and not streamable:
+        raise L.CreidError("get_similar(streamed=True) is squared-L2 top-k retrieval with 1 <= k <= 1024: "
+                           f"got distance_func={distance_func!r}, topk={topk}")
+    big = m * n * 4 > STREAM_MATRIX_BYTES
+    info = {}
+    if streamed is True or (streamed == "auto" and big and streamable and rm.topk_stream_sample(k, n) <= n // 4):
+        indices, dist_sel = rm.topk_stream(q, g, k, stats=info)
+        idx, dist_sel = indices.cpu().numpy(), dist_sel.cpu().numpy()
+        info["path"] = "streamed"
+    elif streamed == "auto" and big:
+        rows = max(1, STREAM_MATRIX_BYTES // (n * 4))
+        parts = [_similar_materialised(q[r0:r0 + rows], g, topk, distance_func) for r0 in range(0, m, rows)]
+        idx, dist_sel = np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
+        info["path"] = "chunked"
     else:
-        indices = rm.rank_rows(distmat)
-        dist_sel = torch.gather(distmat, 1, indices).cpu().numpy()
-    idx = indices.cpu().numpy()
+        idx, dist_sel = _similar_materialised(q, g, topk, distance_func)
+        info["path"] = "materialised"
+    if stats is not None:
+        stats.update(info)
     paths_gallery = np.asarray(paths_gallery)
     return {qp: {"indices": idx[i, :], "paths": paths_gallery[idx[i, :]], "distances": dist_sel[i, :]}
             for i, qp in enumerate(paths)}

@@ -134,6 +134,70 @@ def topk_rows(distmat: torch.Tensor, k: int):
     return idx, dsel
 
 
+STREAM_TOPK_CAPACITY = 4096           # candidate slots per query (creid_stream_topk_collect: power of two, 64 .. 8192)
+_STREAM_TOPK_CHUNK_BYTES = 256 << 20  # bound on every temporary of topk_stream (sample slice, candidate lists, repaired rows)
+
+
+def topk_stream_sample(k: int, n: int) -> int:
+    """Default threshold sample of topk_stream: S = clamp(max(ceil(k n / 1024), 1024), k, n) gallery rows.  The k-th smallest
+    of S evenly strided columns sits near the (k n / S)-th smallest of the row, so a query collects about k n / S <= 1024
+    candidates -- a quarter of the default capacity -- and the sample adds S / n ~ k / 1024 of the contraction."""
+    return max(k, min(n, max(-(-k * n // 1024), 1024)))
+
+
+def topk_stream(q: torch.Tensor, g: torch.Tensor, k: int, qq=None, gg=None, *, sample=None, capacity=None, stats=None):
+    """topk_rows(get_euclidean(q, g, qq, gg), k) -- (indices int64 [m, k], squared-L2 distances fp32 [m, k]), the same indices
+    and the same distance bits, ties by gallery index -- WITHOUT the m x n matrix (fp32 features, k <= min(n, 1024)):
+      1. threshold: `sample` gallery rows at a fixed stride (a gallery sorted by pid does not bias it) go through the
+         materialised kernels; tau[row] = the k-th smallest of the m x sample slice.  The k-th smallest over ANY >= k columns
+         bounds the row's true k-th distance from above, and both paths produce the same bits, so the bound is exact;
+      2. creid_stream_topk_collect: the full contraction, tile by tile; every (distance <= tau[row], column) is appended to the
+         row's candidate list (`capacity` slots);
+      3. creid_stream_topk_select: sorts each list by (distance, index) and keeps the first k.
+    Rows whose list overflowed (a loose threshold, massive ties) are flagged and redone through get_euclidean + topk_rows in
+    bounded row chunks.  `stats` (a dict) receives sample, capacity, fallback_rows and max_candidates."""
+    L.require_gpu(q, g, qq, gg)
+    if q.dtype != torch.float32 or g.dtype != torch.float32 or q.dim() != 2 or g.dim() != 2 or q.shape[1] != g.shape[1]:
+        raise L.CreidError("topk_stream needs fp32 [m, D] and [n, D] features")
+    m, n, k = q.shape[0], g.shape[0], int(k)
+    cap = STREAM_TOPK_CAPACITY if capacity is None else int(capacity)
+    if not 1 <= k <= min(n, 1024, cap):
+        raise L.CreidError(f"topk_stream: k = {k} outside 1 .. min(n = {n}, 1024, capacity = {cap})")
+    S = topk_stream_sample(k, n) if sample is None else max(k, min(n, int(sample)))
+    qq = row_sqnorm(q) if qq is None else qq
+    gg = row_sqnorm(g) if gg is None else gg
+    q, g = _pad_width(q), _pad_width(g)
+    D, dev, lib, st = q.shape[1], q.device, L.lib(), L.stream()
+    stride = n // S
+    gs, ggs = g[::stride][:S].contiguous(), gg[::stride][:S].contiguous()
+    idx = torch.empty((m, k), dtype=torch.int64, device=dev)
+    dsel = torch.empty((m, k), dtype=torch.float32, device=dev)
+    flags = torch.zeros(m, dtype=torch.uint8, device=dev)
+    count = torch.zeros(m, dtype=torch.int32, device=dev)
+    step = max(64, _STREAM_TOPK_CHUNK_BYTES // (max(cap * 8, S * 4)) // 64 * 64)
+    for r0 in range(0, m, step):
+        r1 = min(m, r0 + step)
+        qc, qqc = q[r0:r1], qq[r0:r1]
+        tau = topk_rows(get_euclidean(qc, gs, qqc, ggs), k)[1][:, k - 1].contiguous()
+        cand = torch.empty((r1 - r0, cap), dtype=torch.int64, device=dev)
+        L.check(lib.creid_stream_topk_collect(L.ptr(qc), L.ptr(g), L.ptr(qqc), L.ptr(gg), r1 - r0, n, D, L.ptr(tau), cap,
+                                              L.ptr(cand), L.ptr(count[r0:r1]), st), "creid_stream_topk_collect")
+        L.check(lib.creid_stream_topk_select(L.ptr(cand), L.ptr(count[r0:r1]), r1 - r0, cap, k, L.ptr(idx[r0:r1]),
+                                             L.ptr(dsel[r0:r1]), L.ptr(flags[r0:r1]), st), "creid_stream_topk_select")
+        del tau, cand
+    bad = torch.nonzero(flags).flatten()
+    if bad.numel():                                         # overflowed lists (or NaN rows): the materialised kernels, row chunks
+        rows = max(1, _STREAM_TOPK_CHUNK_BYTES // (n * 4))
+        for b0 in range(0, bad.numel(), rows):
+            sel = bad[b0:b0 + rows]
+            ridx, rd = topk_rows(get_euclidean(q.index_select(0, sel), g, qq.index_select(0, sel), gg), k)
+            idx.index_copy_(0, sel, ridx)
+            dsel.index_copy_(0, sel, rd)
+    if stats is not None:
+        stats.update(sample=S, capacity=cap, fallback_rows=int(bad.numel()), max_candidates=int(count.max().item()) if m else 0)
+    return idx, dsel
+
+
 def _dev_i64(a, device):
     if isinstance(a, torch.Tensor):
         return a.to(device=device, dtype=torch.int64).contiguous()

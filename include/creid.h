@@ -146,6 +146,24 @@ int creid_stream_count(const float* q, const float* g, const float* qq, const fl
 int creid_stream_finalize(const int32_t* npos, const uint32_t* hist, int64_t m, int32_t cap, uint8_t* valid,
                           double* ap, int32_t* first, void* stream);
 
+/* ---- top-k retrieval with NO m x n matrix (csrc/stream_eval.hip): what creid_sqdist_matrix (fp32) + creid_topk_rows
+ * return -- the same indices and the same distance bits, ties by gallery index -- from the streamed contraction.
+ *  collect : q fp32 [m][D], g fp32 [n][D], qq / gg their row square norms, D % 4 == 0.  tau fp32 [m]: ANY upper bound
+ *            (inclusive) on the row's k-th smallest distance, e.g. the k-th smallest over a sample of >= k gallery rows
+ *            computed by creid_sqdist_matrix.  Every column with distance <= tau[row] takes a slot of the row's list:
+ *            count int32 [m] (must be ZERO on entry) ends as the number of such columns, cand uint64 [m][cap] holds the
+ *            first min(count, cap) of them in arrival order as (order-preserving image of the fp32 distance) << 32 | column.
+ *            cap = a power of two, 64..8192.
+ *  select  : per row the k smallest (distance, index) of its list, ascending: out_idx int64 [m][k], out_dist fp32 [m][k]
+ *            (nullable).  k <= min(1024, cap).  flags uint8 [m]: 0 = written; 1 = the list overflowed (count > cap) or
+ *            holds fewer than k entries (NaN distances pass no threshold): that row's outputs are unwritten, use
+ *            creid_sqdist_matrix + creid_topk_rows for it.
+ * CREID_E_SHAPE for a cap / k / D outside these limits, before anything is launched; m == 0 returns 0. */
+int creid_stream_topk_collect(const float* q, const float* g, const float* qq, const float* gg, int64_t m, int64_t n,
+                              int64_t D, const float* tau, int32_t cap, uint64_t* cand, int32_t* count, void* stream);
+int creid_stream_topk_select(const uint64_t* cand, const int32_t* count, int64_t m, int32_t cap, int32_t k,
+                             int64_t* out_idx, float* out_dist, uint8_t* flags, void* stream);
+
 /* Measured launch plans (optional).  kind 0 = weight gradient: key (M = batch*out_h*out_w, out_c, K = kh*kw*in_c, 0) ->
  * (tile rows 64|128, tile cols 64|128, pixel splits | ring depth << 16 | producer/consumer waves << 20 | two k-groups << 21);
  * kind 1 = implicit-GEMM forward / data gradient: key (GEMM rows M, GEMM cols N, K, transposed 0|1 | stride << 1) ->
