@@ -143,9 +143,11 @@ __global__ __launch_bounds__(256) void sqdist_f32_kernel(const float* __restrict
   }
   float4 ra[2], rb[2];
   unsigned rmask = 0u;                             // all ones while the staged k-tile lies inside D
-  auto gload = [&](int k0) {                       // branch-free (a k-tile beyond D reads k-tile 0; lstore turns it into zeros)
+  // branch-free: a lane whose 16 bytes lie beyond D reads its row's first 16 bytes (ap / bp hold + 4 lkc; with D < 16 "k-tile 0"
+  // at 4 lkc would run past the row, and past the tensor for its last row); lstore turns it into zeros
+  auto gload = [&](int k0) {
     const bool in = k0 + 4 * lkc < D;
-    const int ko = in ? k0 : 0;
+    const int ko = in ? k0 : -4 * lkc;
     rmask = in ? 0xffffffffu : 0u;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {

@@ -1,0 +1,54 @@
+// What the two streamed contractions (stream_eval.hip: fp32 features on the f32 MFMA; stream_h16.hip: bf16 / f16 features on the
+// 16-bit MFMA) share: the tile geometry the work split is expressed in, the epilogue selector, the list capacities, the
+// order-preserving key of a distance, and the work split itself.
+#pragma once
+#include "common.hpp"
+#include <stdlib.h>
+
+constexpr int SQ_TM = 64, SQ_TN = 256;           // a tile: 64 query rows x 256 gallery columns (four units of 64 columns)
+constexpr int EPI_COUNT = 0, EPI_TOPK = 1;       // what a streamed contraction does with a finished tile
+constexpr int PL_MAXC = 128;                     // positive-list capacity of the count epilogue (LDS: [64][cap] keys + histogram)
+constexpr int TS_MIN_CAP = 64, TS_MAX_CAP = 8192;   // candidate-list capacity of the top-k epilogue
+
+// float -> unsigned with the same order (negatives included; squared distances may be slightly negative)
+__device__ __forceinline__ unsigned mono_key(float d) {
+  const unsigned u = __float_as_uint(d);
+  return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
+}
+
+/* The work split of a streamed contraction (both kernels, both epilogues).  elem_bytes: the size of a feature element (the
+ * gallery's footprint decides between the two modes). */
+struct StreamSplit { int tiles_m, U, upw, mode; unsigned grid; };
+static StreamSplit stream_split(int64_t m, int64_t n, int64_t D, int64_t elem_bytes = 4) {
+  const int tiles_m = (int)((m + SQ_TM - 1) / SQ_TM), tiles_n = (int)((n + SQ_TN - 1) / SQ_TN);
+  const int U = (int)((n + 63) / 64);                           // units of 64 gallery columns per row of query tiles
+  // enough workgroups for two per CU, but never fewer than ~4 gallery tiles per workgroup (per-tile restart cost)
+  static const int target = [] { const char* e = getenv("CREID_STREAM_WGS"); int v = e ? atoi(e) : 0; return v > 0 ? v : 512; }();
+  // mode 0: never MORE than `tper_max` gallery tiles per workgroup: the grid overshoots the 512 slots by up to tiles_m - 1
+  // workgroups, which start when the first ones finish -- harmless when a workgroup is 5 tiles long, a whole second round on an
+  // idle chip when it is 131 (6250 x 200 000: 588 workgroups, 66.0 ms; with <= 8 tiles per workgroup 46.1 ms; HBM-side traffic by
+  // the counters the same under both rules -- profiles/r05_stream_grid.md)
+  static const int tper_max = [] { const char* e = getenv("CREID_STREAM_TPER"); int v = e ? atoi(e) : 0; return v > 0 ? v : 8; }();
+  int nsplit = (target + tiles_m - 1) / tiles_m;
+  if (nsplit < (tiles_n + tper_max - 1) / tper_max) nsplit = (tiles_n + tper_max - 1) / tper_max;
+  if (nsplit > tiles_n) nsplit = tiles_n;
+  if (nsplit < 1) nsplit = 1;
+  const int t_per = (tiles_n + nsplit - 1) / nsplit;
+  nsplit = (tiles_n + t_per - 1) / t_per;                       // drop empty slices
+  // mode 1 (equal runs of units over the resident slots): only while the gallery fits the Infinity Cache beside the queries, the
+  // grid of mode 0 is a single round, and the equal run is shorter than mode 0's longest workgroup by more than the narrow tile
+  // and the second segment cost (~a quarter tile: 2228 x 17661 -- 4.75 tiles against 5 -- measured EQUAL in both modes,
+  // 3000 x 15000 -- 5.5 against 6 -- 5.6 % faster in mode 1; profiles/r06_eval_kloop.md).  CREID_STREAM_BALANCE=0 / 1 forces a
+  // mode (the tests run both).
+  const long long T = (long long)tiles_m * U;
+  const long long wg1 = T / 4 < target ? (T / 4 > 0 ? T / 4 : 1) : target;
+  const char* bal_e = CREID_KNOB_ENV("CREID_STREAM_BALANCE");
+  const int bal = (bal_e && *bal_e) ? atoi(bal_e) : -1;
+  const double run1 = (double)((T + wg1 - 1) / wg1) / 4.0 + 0.3;
+  const int mode = bal >= 0 ? (bal != 0)
+                            : ((double)n * (double)D * (double)elem_bytes <= 192e6 && (long long)tiles_m * nsplit <= target &&
+                               run1 < (double)t_per);
+  const int upw = 4 * t_per;
+  const unsigned grid = mode == 0 ? (unsigned)(tiles_m * nsplit) : (unsigned)wg1;
+  return StreamSplit{tiles_m, U, upw, mode, grid};
+}

@@ -20,27 +20,19 @@
 // consumer of the same contraction: sqdist_count_f32_kernel<.., EPI_TOPK> keeps the k-loop, staging and work split and
 // swaps the epilogue for "append (distance, column) to the row's candidate list when the distance is within the row's
 // threshold"; stream_topk_select_kernel sorts each list and keeps the first k.
-#include "common.hpp"
+// bf16 / f16 features: the same contraction, epilogues and positives on the 16-bit MFMA are in stream_h16.hip.
+#include "stream_common.hpp"
 #include "topk_tail.hpp"
-#include <stdlib.h>
 #include <type_traits>
 
 namespace {
-constexpr int SQ_TM = 64, SQ_TN = 256, SQ_BK = 16;
-constexpr int EPI_COUNT = 0, EPI_TOPK = 1;       // what sqdist_count_f32_kernel does with a finished tile
+constexpr int SQ_BK = 16;                        // (tile geometry, epilogue selector, list capacities, mono_key: stream_common.hpp)
 // LDS operand image of one 16-deep k-tile: [kh = k & 1][quarter = k >> 2][row][e = (k >> 1) & 1] -- the per-lane MFMA operand is
 // A[i = lane & 31][k = 2 step + (lane >> 5)], so the two values a lane feeds to the two steps of a quarter are one 8-byte unit:
 // a quarter's fragments are 1 + 4 ds_read_b64 per lane (32 lanes x 8 B = one conflict-free 256-B row of banks), and the staging
 // side writes a global float4 (k = 4 q .. 4 q + 3) as two ds_write_b64: (x, z) -> kh 0, (y, w) -> kh 1.  Plane pitch = 2 rows +
 // 8 dwords: the four quarter planes a 16-lane store group touches (4 rows x 4 quarters) cover 32 distinct banks.
 constexpr int SQ_PA = SQ_TM * 2 + 8, SQ_PB = SQ_TN * 2 + 8;
-constexpr int PL_MAXC = 128;
-
-// float -> unsigned with the same order (negatives included; squared distances may be slightly negative)
-__device__ __forceinline__ unsigned mono_key(float d) {
-  const unsigned u = __float_as_uint(d);
-  return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
-}
 }  // namespace
 
 // ----------------------------------------------------------------------------------------
@@ -604,7 +596,7 @@ __global__ __launch_bounds__(256) void plan_query_kernel(const int64_t* __restri
 //    topk_rows_kernel.  A list that overflowed (count > cap: entries were dropped) or holds fewer than k entries (NaN
 //    distances never pass the threshold) is flagged and nothing is written for the row.
 // ----------------------------------------------------------------------------------------
-constexpr int TS_T = 1024, TS_MIN_CAP = 64, TS_MAX_CAP = 8192;
+constexpr int TS_T = 1024;
 
 __global__ __launch_bounds__(TS_T) void stream_topk_select_kernel(const unsigned long long* __restrict__ cand,
                                                                   const int32_t* __restrict__ count, int cap, int k,
@@ -621,40 +613,7 @@ __global__ __launch_bounds__(TS_T) void stream_topk_select_kernel(const unsigned
   if (tid == 0) flags[row] = 0;
 }
 
-/* The work split of the streamed contraction (sqdist_count_f32_kernel, both epilogues). */
-struct StreamSplit { int tiles_m, U, upw, mode; unsigned grid; };
-static StreamSplit stream_split(int64_t m, int64_t n, int64_t D) {
-  const int tiles_m = (int)((m + SQ_TM - 1) / SQ_TM), tiles_n = (int)((n + SQ_TN - 1) / SQ_TN);
-  const int U = (int)((n + 63) / 64);                           // units of 64 gallery columns per row of query tiles
-  // enough workgroups for two per CU, but never fewer than ~4 gallery tiles per workgroup (per-tile restart cost)
-  static const int target = [] { const char* e = getenv("CREID_STREAM_WGS"); int v = e ? atoi(e) : 0; return v > 0 ? v : 512; }();
-  // mode 0: never MORE than `tper_max` gallery tiles per workgroup: the grid overshoots the 512 slots by up to tiles_m - 1
-  // workgroups, which start when the first ones finish -- harmless when a workgroup is 5 tiles long, a whole second round on an
-  // idle chip when it is 131 (6250 x 200 000: 588 workgroups, 66.0 ms; with <= 8 tiles per workgroup 46.1 ms; HBM-side traffic by
-  // the counters the same under both rules -- profiles/r05_stream_grid.md)
-  static const int tper_max = [] { const char* e = getenv("CREID_STREAM_TPER"); int v = e ? atoi(e) : 0; return v > 0 ? v : 8; }();
-  int nsplit = (target + tiles_m - 1) / tiles_m;
-  if (nsplit < (tiles_n + tper_max - 1) / tper_max) nsplit = (tiles_n + tper_max - 1) / tper_max;
-  if (nsplit > tiles_n) nsplit = tiles_n;
-  if (nsplit < 1) nsplit = 1;
-  const int t_per = (tiles_n + nsplit - 1) / nsplit;
-  nsplit = (tiles_n + t_per - 1) / t_per;                       // drop empty slices
-  // mode 1 (equal runs of units over the resident slots): only while the gallery fits the Infinity Cache beside the queries, the
-  // grid of mode 0 is a single round, and the equal run is shorter than mode 0's longest workgroup by more than the narrow tile
-  // and the second segment cost (~a quarter tile: 2228 x 17661 -- 4.75 tiles against 5 -- measured EQUAL in both modes,
-  // 3000 x 15000 -- 5.5 against 6 -- 5.6 % faster in mode 1; profiles/r06_eval_kloop.md).  CREID_STREAM_BALANCE=0 / 1 forces a
-  // mode (the tests run both).
-  const long long T = (long long)tiles_m * U;
-  const long long wg1 = T / 4 < target ? (T / 4 > 0 ? T / 4 : 1) : target;
-  const char* bal_e = CREID_KNOB_ENV("CREID_STREAM_BALANCE");
-  const int bal = (bal_e && *bal_e) ? atoi(bal_e) : -1;
-  const double run1 = (double)((T + wg1 - 1) / wg1) / 4.0 + 0.3;
-  const int mode = bal >= 0 ? (bal != 0)
-                            : ((double)n * (double)D * 4.0 <= 192e6 && (long long)tiles_m * nsplit <= target && run1 < (double)t_per);
-  const int upw = 4 * t_per;
-  const unsigned grid = mode == 0 ? (unsigned)(tiles_m * nsplit) : (unsigned)wg1;
-  return StreamSplit{tiles_m, U, upw, mode, grid};
-}
+// (the work split of the streamed contraction: stream_split() in stream_common.hpp, shared with stream_h16.hip)
 
 extern "C" {
 

@@ -141,7 +141,7 @@ def _similar_materialised(q, g, topk, distance_func):
 
 
 def get_similar(embeddings, paths, embeddings_gallery, paths_gallery, topk=0, normalize_features=True,
-                distance_func="euclidean", streamed="auto", stats=None):
+                distance_func="euclidean", streamed="auto", stats=None, compute_dtype=torch.float32):
     """inference/get_similar.py:99-125 -> {query_path: {"indices", "paths", "distances"}} (numpy arrays).
 
     streamed: False -- the m x n distance matrix is written and every row selected from it (get_dist_func + topk_rows /
@@ -149,13 +149,22 @@ def get_similar(embeddings, paths, embeddings_gallery, paths_gallery, topk=0, no
     (CreidError for cosine, topk = 0 or k > 1024).  "auto" -- the matrix path unless it would exceed STREAM_MATRIX_BYTES; then
     the streamed path when the call is streamable and its threshold sample is at most a quarter of the gallery, else the
     matrix path over chunks of query rows (the result is the same, the matrix never exists whole).
+    compute_dtype: torch.float32 (default, the reference's arithmetic), torch.bfloat16 or torch.float16 -- the (optionally
+    normalised) features are rounded ONCE to that type and every path works on the rounded features with the 16-bit MFMA
+    kernels (half the gallery bytes; the distances stay fp32).  The three paths still agree bit for bit with one another.
     stats (a dict) receives "path" ("materialised" | "streamed" | "chunked") and topk_stream's counters."""
     if streamed not in (True, False, "auto"):
         raise ValueError(f"streamed must be True, False or 'auto', got {streamed!r}")
+    if compute_dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise L.CreidError(f"get_similar: compute_dtype must be torch.float32, torch.bfloat16 or torch.float16, got {compute_dtype}")
     q = torch.as_tensor(np.asarray(embeddings, np.float32)).cuda() if not isinstance(embeddings, torch.Tensor) else embeddings.float().cuda()
     g = torch.as_tensor(np.asarray(embeddings_gallery, np.float32)).cuda() if not isinstance(embeddings_gallery, torch.Tensor) else embeddings_gallery.float().cuda()
     if normalize_features:
-        q, g = rm.l2_normalize(q.contiguous()), rm.l2_normalize(g.contiguous())
+        q, g = rm.l2_normalize(q.contiguous(), out_dtype=compute_dtype), rm.l2_normalize(g.contiguous(), out_dtype=compute_dtype)
+    elif compute_dtype != torch.float32:
+        q, g = q.to(compute_dtype), g.to(compute_dtype)
+    if compute_dtype != torch.float32:                         # the 16-bit kernels load 8-element k-chunks; zero columns change nothing
+        q, g = rm._pad_width(q, 8), rm._pad_width(g, 8)
     q, g = q.contiguous(), g.contiguous()
     m, n = q.shape[0], g.shape[0]
     k = min(int(topk), n) if topk else 0

@@ -60,13 +60,16 @@ def get_cosine(x: torch.Tensor, y: torch.Tensor, eps: float = 1e-12) -> torch.Te
     return torch.abs(1 - cos).clamp(min=eps)
 
 
-def _pad_width(feats: torch.Tensor) -> torch.Tensor:
-    """The kernels load 16-byte k-chunks (D % 4 == 0).  Zero columns change neither a norm nor a dot product, so any other
-    width is padded up -- results identical, no kernel special case."""
+_H16 = (torch.bfloat16, torch.float16)
+
+
+def _pad_width(feats: torch.Tensor, mult: int = 4) -> torch.Tensor:
+    """The kernels load 16-byte k-chunks (D % 4 == 0 for fp32, D % 8 == 0 for bf16 / f16).  Zero columns change neither a norm
+    nor a dot product, so any other width is padded up -- results identical, no kernel special case."""
     D = feats.shape[1]
-    if D % 4 == 0:
+    if D % mult == 0:
         return feats
-    return torch.nn.functional.pad(feats, (0, 4 - D % 4)).contiguous()
+    return torch.nn.functional.pad(feats, (0, mult - D % mult)).contiguous()
 
 
 def get_dist_func(func_name="euclidean"):
@@ -147,7 +150,9 @@ def topk_stream_sample(k: int, n: int) -> int:
 
 def topk_stream(q: torch.Tensor, g: torch.Tensor, k: int, qq=None, gg=None, *, sample=None, capacity=None, stats=None):
     """topk_rows(get_euclidean(q, g, qq, gg), k) -- (indices int64 [m, k], squared-L2 distances fp32 [m, k]), the same indices
-    and the same distance bits, ties by gallery index -- WITHOUT the m x n matrix (fp32 features, k <= min(n, 1024)):
+    and the same distance bits, ties by gallery index -- WITHOUT the m x n matrix (fp32, bf16 or f16 features, q and g of one
+    dtype, k <= min(n, 1024); 16-bit features run the contraction on the 16-bit MFMA and the threshold sample, the repair and
+    the norms through the materialised kernels of the same dtype, so the bits are those of the 16-bit get_euclidean):
       1. threshold: `sample` gallery rows at a fixed stride (a gallery sorted by pid does not bias it) go through the
          materialised kernels; tau[row] = the k-th smallest of the m x sample slice.  The k-th smallest over ANY >= k columns
          bounds the row's true k-th distance from above, and both paths produce the same bits, so the bound is exact;
@@ -156,9 +161,12 @@ def topk_stream(q: torch.Tensor, g: torch.Tensor, k: int, qq=None, gg=None, *, s
       3. creid_stream_topk_select: sorts each list by (distance, index) and keeps the first k.
     Rows whose list overflowed (a loose threshold, massive ties) are flagged and redone through get_euclidean + topk_rows in
     bounded row chunks.  `stats` (a dict) receives sample, capacity, fallback_rows and max_candidates."""
+    if q.dtype != g.dtype:
+        raise L.CreidError(f"topk_stream needs q and g of one dtype (fp32, bf16 or f16), got {q.dtype} and {g.dtype}")
     L.require_gpu(q, g, qq, gg)
-    if q.dtype != torch.float32 or g.dtype != torch.float32 or q.dim() != 2 or g.dim() != 2 or q.shape[1] != g.shape[1]:
-        raise L.CreidError("topk_stream needs fp32 [m, D] and [n, D] features")
+    if q.dtype not in (torch.float32,) + _H16 or q.dim() != 2 or g.dim() != 2 or q.shape[1] != g.shape[1]:
+        raise L.CreidError("topk_stream needs [m, D] and [n, D] features of one dtype: fp32, bf16 or f16")
+    h16 = q.dtype in _H16
     m, n, k = q.shape[0], g.shape[0], int(k)
     cap = STREAM_TOPK_CAPACITY if capacity is None else int(capacity)
     if not 1 <= k <= min(n, 1024, cap):
@@ -166,8 +174,9 @@ def topk_stream(q: torch.Tensor, g: torch.Tensor, k: int, qq=None, gg=None, *, s
     S = topk_stream_sample(k, n) if sample is None else max(k, min(n, int(sample)))
     qq = row_sqnorm(q) if qq is None else qq
     gg = row_sqnorm(g) if gg is None else gg
-    q, g = _pad_width(q), _pad_width(g)
+    q, g = _pad_width(q, 8 if h16 else 4), _pad_width(g, 8 if h16 else 4)
     D, dev, lib, st = q.shape[1], q.device, L.lib(), L.stream()
+    dt = L.dtype_code(q)
     stride = n // S
     gs, ggs = g[::stride][:S].contiguous(), gg[::stride][:S].contiguous()
     idx = torch.empty((m, k), dtype=torch.int64, device=dev)
@@ -180,8 +189,12 @@ def topk_stream(q: torch.Tensor, g: torch.Tensor, k: int, qq=None, gg=None, *, s
         qc, qqc = q[r0:r1], qq[r0:r1]
         tau = topk_rows(get_euclidean(qc, gs, qqc, ggs), k)[1][:, k - 1].contiguous()
         cand = torch.empty((r1 - r0, cap), dtype=torch.int64, device=dev)
-        L.check(lib.creid_stream_topk_collect(L.ptr(qc), L.ptr(g), L.ptr(qqc), L.ptr(gg), r1 - r0, n, D, L.ptr(tau), cap,
-                                              L.ptr(cand), L.ptr(count[r0:r1]), st), "creid_stream_topk_collect")
+        if h16:
+            L.check(lib.creid_stream_topk_collect_h16(L.ptr(qc), L.ptr(g), L.ptr(qqc), L.ptr(gg), r1 - r0, n, D, dt, L.ptr(tau),
+                                                      cap, L.ptr(cand), L.ptr(count[r0:r1]), st), "creid_stream_topk_collect_h16")
+        else:
+            L.check(lib.creid_stream_topk_collect(L.ptr(qc), L.ptr(g), L.ptr(qqc), L.ptr(gg), r1 - r0, n, D, L.ptr(tau), cap,
+                                                  L.ptr(cand), L.ptr(count[r0:r1]), st), "creid_stream_topk_collect")
         L.check(lib.creid_stream_topk_select(L.ptr(cand), L.ptr(count[r0:r1]), r1 - r0, cap, k, L.ptr(idx[r0:r1]),
                                              L.ptr(dsel[r0:r1]), L.ptr(flags[r0:r1]), st), "creid_stream_topk_select")
         del tau, cand
@@ -405,9 +418,11 @@ def stream_eval(fq, fg, qq, gg, plan: StreamPlan):
 def _stream_eval(fq, fg, qq, gg, plan: StreamPlan):
     """Per-query (valid u8[m], AP f64[m], first-match rank i32[m]) with no m x n matrix: positives' distances ->
     streamed MFMA contraction with an in-register count epilogue -> histogram prefix.  valid == 2 marks a query
-    whose positive list overflowed the plan's capacity (see StreamPlan.overflow)."""
+    whose positive list overflowed the plan's capacity (see StreamPlan.overflow).  fp32 features run on the f32 MFMA
+    (csrc/stream_eval.hip), bf16 / f16 features (D % 8 == 0) on the 16-bit MFMA (csrc/stream_h16.hip)."""
     L.require_gpu(fq, fg, qq, gg)
-    assert fq.dtype == torch.float32 and fg.dtype == torch.float32
+    assert fq.dtype == fg.dtype and fq.dtype in (torch.float32,) + _H16
+    h16 = fq.dtype in _H16
     m, n, D = fq.shape[0], fg.shape[0], fq.shape[1]
     assert (m, n) == (plan.m, plan.n)
     dev, lib, st = fq.device, L.lib(), L.stream()
@@ -416,12 +431,21 @@ def _stream_eval(fq, fg, qq, gg, plan: StreamPlan):
     pos_idx = torch.empty((m, cap), dtype=torch.int32, device=dev)
     npos = torch.empty(m, dtype=torch.int32, device=dev)
     hist = torch.zeros((m, cap), dtype=torch.int32, device=dev)
-    L.check(lib.creid_stream_poslist(L.ptr(fq), L.ptr(fg), L.ptr(qq), L.ptr(gg), m, n, D, L.ptr(plan.q_slot),
-                                     L.ptr(plan.csr_off), L.ptr(plan.g_order), L.ptr(plan.q_cams), L.ptr(plan.g_cams), cap,
-                                     L.ptr(pos_key), L.ptr(pos_idx), L.ptr(npos), st), "creid_stream_poslist")
-    L.check(lib.creid_stream_count(L.ptr(fq), L.ptr(fg), L.ptr(qq), L.ptr(gg), m, n, D, L.ptr(plan.q_pids),
-                                   L.ptr(plan.g_pids), cap, L.ptr(pos_key), L.ptr(pos_idx), L.ptr(npos), L.ptr(hist), st),
-            "creid_stream_count")
+    if h16:
+        dt = L.dtype_code(fq)
+        L.check(lib.creid_stream_poslist_h16(L.ptr(fq), L.ptr(fg), L.ptr(qq), L.ptr(gg), m, n, D, dt, L.ptr(plan.q_slot),
+                                             L.ptr(plan.csr_off), L.ptr(plan.g_order), L.ptr(plan.q_cams), L.ptr(plan.g_cams),
+                                             cap, L.ptr(pos_key), L.ptr(pos_idx), L.ptr(npos), st), "creid_stream_poslist_h16")
+        L.check(lib.creid_stream_count_h16(L.ptr(fq), L.ptr(fg), L.ptr(qq), L.ptr(gg), m, n, D, dt, L.ptr(plan.q_pids),
+                                           L.ptr(plan.g_pids), cap, L.ptr(pos_key), L.ptr(pos_idx), L.ptr(npos), L.ptr(hist),
+                                           st), "creid_stream_count_h16")
+    else:
+        L.check(lib.creid_stream_poslist(L.ptr(fq), L.ptr(fg), L.ptr(qq), L.ptr(gg), m, n, D, L.ptr(plan.q_slot),
+                                         L.ptr(plan.csr_off), L.ptr(plan.g_order), L.ptr(plan.q_cams), L.ptr(plan.g_cams), cap,
+                                         L.ptr(pos_key), L.ptr(pos_idx), L.ptr(npos), st), "creid_stream_poslist")
+        L.check(lib.creid_stream_count(L.ptr(fq), L.ptr(fg), L.ptr(qq), L.ptr(gg), m, n, D, L.ptr(plan.q_pids),
+                                       L.ptr(plan.g_pids), cap, L.ptr(pos_key), L.ptr(pos_idx), L.ptr(npos), L.ptr(hist), st),
+                "creid_stream_count")
     valid = torch.empty(m, dtype=torch.uint8, device=dev)
     ap = torch.empty(m, dtype=torch.float64, device=dev)
     first = torch.empty(m, dtype=torch.int32, device=dev)
@@ -450,7 +474,8 @@ class R1_mAP:
     def __init__(self, pl_module=None, num_query=0, max_rank=50, feat_norm=True, dist_func="euclidean",
                  compute_dtype=torch.float32, streamed=False):
         """streamed=True: metric-only evaluation that never materialises the distance / index matrices (euclidean,
-        plain camera ids, fp32); `last` then holds the per-query results only.  streamed=False keeps
+        plain camera ids; compute_dtype fp32, bf16 or f16 -- the 16-bit modes run the 16-bit MFMA and return exactly what
+        their materialised evaluation returns); `last` then holds the per-query results only.  streamed=False keeps
         `last["distmat"]` / `last["indices"]` (what the rank-index parity tests and get_similar read)."""
         self.streamed = streamed
         self.num_query = num_query
@@ -473,7 +498,7 @@ class R1_mAP:
         feats = _pad_width(feats.float().contiguous())
         nq = self.num_query
         if (self.streamed and self.dist_name == "euclidean" and not respect_camids
-                and self.compute_dtype == torch.float32):
+                and self.compute_dtype in (torch.float32,) + _H16):
             return self._compute_streamed(feats, pids, camids)
         if self.dist_name == "euclidean":
             if self.feat_norm:
@@ -512,11 +537,16 @@ class R1_mAP:
         nq = self.num_query
         if _normed is not None:                 # the redo of a failed speculation: rows already normalised, nothing printed twice
             f, sq = _normed
-        elif self.feat_norm:
-            print("The test feature is normalized")
-            f, sq = l2_normalize(feats, return_sqnorm=True)
         else:
-            f, sq = feats, row_sqnorm(feats)
+            # exactly the rows and norms of the materialised branch of compute(): both paths multiply the same tensors
+            if self.compute_dtype in _H16:
+                feats = _pad_width(feats, 8)
+            if self.feat_norm:
+                print("The test feature is normalized")
+                f, sq = l2_normalize(feats, out_dtype=self.compute_dtype, return_sqnorm=True)
+            else:
+                f = feats if self.compute_dtype == torch.float32 else feats.to(self.compute_dtype)
+                sq = row_sqnorm(f)
         pids = np.asarray(pids); camids = np.asarray(camids)
         speculative = False
         if plan is None:
@@ -575,15 +605,15 @@ class R1_mAP:
 
     def compute_chunked(self, feats, pids, camids, query_chunk=4096):
         """Galleries whose m x n matrix must not be materialised (the reference's `_commpute_batches_double` path,
-        utils/reid_metric.py:93-110,126-129, chunks the gallery on the host): fp32 features go through the streamed
-        kernels in ONE pass with no matrix at all; other compute dtypes process `query_chunk` query rows at a time
-        (distance tile, rank, CMC/AP scan on the device, only per-query results kept)."""
+        utils/reid_metric.py:93-110,126-129, chunks the gallery on the host): the euclidean distance (fp32, bf16 or f16
+        compute dtype) goes through the streamed kernels in ONE pass with no matrix at all; the cosine distance processes
+        `query_chunk` query rows at a time (distance tile, rank, CMC/AP scan on the device, only per-query results kept)."""
         if not isinstance(feats, torch.Tensor) or not feats.is_cuda:
             raise L.CreidError("R1_mAP.compute_chunked needs device features (no CPU fallback)")
         from .parallel import merge_eval_results
         euclid = self.dist_name == "euclidean"
         feats = _pad_width(feats.float().contiguous())
-        if euclid and self.compute_dtype == torch.float32:
+        if euclid and self.compute_dtype in (torch.float32,) + _H16:
             return self._compute_streamed(feats, pids, camids)
         nq = self.num_query
         if not euclid:

@@ -164,6 +164,30 @@ int creid_stream_topk_collect(const float* q, const float* g, const float* qq, c
 int creid_stream_topk_select(const uint64_t* cand, const int32_t* count, int64_t m, int32_t cap, int32_t k,
                              int64_t* out_idx, float* out_dist, uint8_t* flags, void* stream);
 
+/* ---- the streamed evaluation and the streamed retrieval for 16-bit features (csrc/stream_h16.hip): q / g are bf16 or f16
+ * [m][D] / [n][D] (dtype = CREID_BF16 | CREID_F16, both operands alike), qq / gg their fp32 row square norms; every other
+ * argument has the meaning, the limits and the checks of the fp32 entry point of the same name without _h16 (cap rules, size
+ * limits, m == 0 returns 0 before the pointer checks), plus D % 8 == 0 (16-byte k-chunks; D <= 2^20) else CREID_E_SHAPE and
+ * any other dtype CREID_E_DTYPE -- all before anything is launched.  creid_stream_plan, creid_stream_finalize and
+ * creid_stream_topk_select do not depend on the feature type and serve both.
+ * Contract: a distance is produced with the bits of creid_sqdist_matrix of the SAME dtype -- every accumulator element
+ * starts at 0 and receives one v_mfma_f32_32x32x16_{bf16,f16} per 16-deep k-step in ascending k, lane (l31, kh) supplying
+ * k = 16 step + 8 kh + 0..7 in fragment elements 0..7, k beyond D zero-filled in 16-byte chunks, the query as the A operand;
+ * distance = fmaf(-2, acc, qq[row] + gg[col]).  poslist computes its <= 128 distances per query with the same instruction in
+ * the same step order (the internal summation of a 16-bit MFMA has no scalar equivalent).  Hence the streamed results equal
+ * creid_sqdist_matrix + creid_rank_rows + creid_cmc_ap_ranked / creid_topk_rows on the same 16-bit tensors bit for bit. */
+int creid_stream_poslist_h16(const void* q, const void* g, const float* qq, const float* gg, int64_t m, int64_t n,
+                             int64_t D, int dtype, const int32_t* q_slot, const int64_t* csr_off, const int32_t* g_order,
+                             const int64_t* q_cams, const int64_t* g_cams, int32_t cap, uint32_t* pos_key,
+                             int32_t* pos_idx, int32_t* npos, void* stream);
+int creid_stream_count_h16(const void* q, const void* g, const float* qq, const float* gg, int64_t m, int64_t n,
+                           int64_t D, int dtype, const int64_t* q_pids, const int64_t* g_pids, int32_t cap,
+                           const uint32_t* pos_key, const int32_t* pos_idx, const int32_t* npos, uint32_t* hist,
+                           void* stream);
+int creid_stream_topk_collect_h16(const void* q, const void* g, const float* qq, const float* gg, int64_t m, int64_t n,
+                                  int64_t D, int dtype, const float* tau, int32_t cap, uint64_t* cand, int32_t* count,
+                                  void* stream);
+
 /* Measured launch plans (optional).  kind 0 = weight gradient: key (M = batch*out_h*out_w, out_c, K = kh*kw*in_c, 0) ->
  * (tile rows 64|128, tile cols 64|128, pixel splits | ring depth << 16 | producer/consumer waves << 20 | two k-groups << 21);
  * kind 1 = implicit-GEMM forward / data gradient: key (GEMM rows M, GEMM cols N, K, transposed 0|1 | stride << 1) ->
