@@ -509,6 +509,7 @@ __global__ __launch_bounds__(1024) void cmc_ap_ranked_wide_kernel(const int64_t*
 namespace {
 constexpr int TK_T = 1024, TK_B = 4096, TK_CAP = 4096;
 __device__ __forceinline__ unsigned tk_key(float d) {
+  d = d + 0.0f;  // -0 -> +0, like orderable(): the prefix of the stable rank ties +-0 by gallery index
   const unsigned u = __float_as_uint(d);
   return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
 }

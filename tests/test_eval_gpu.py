@@ -66,7 +66,16 @@ def test_sqdist_16bit_vs_oracle(rm, dt):
     g = torch.from_numpy(rng.standard_normal((777, 512)).astype(np.float32)).to(dt)
     d = rm.get_euclidean(q.cuda(), g.cuda()).cpu()
     ref = ro.sqdist_matrix(q.double(), g.double())   # same rounded inputs, exact arithmetic
-    np.testing.assert_allclose(d.numpy(), ref.numpy(), rtol=1e-4, atol=2e-3)
+    # the bound of tests/eval_exact.py (2 D u sum |q| |g| + u (qq + gg) + u |d|, u = 2^-24) plus the norms computed inside:
+    # a lane's chain of D / 64 squares and a wave sum, (D / 64 + 6) u (qq + gg) -- about 0.02 on distances near 1000, where this
+    # test used to allow rtol 1e-4 + atol 2e-3 ~ 0.1
+    u, D = 2.0 ** -24, q.shape[1]
+    s = (q.double() ** 2).sum(1)[:, None] + (g.double() ** 2).sum(1)[None, :]
+    bound = 2 * D * u * (q.double().abs() @ g.double().abs().t()) + (D // 64 + 6 + 1) * u * s + u * ref.abs()
+    err = (d.double() - ref).abs()
+    print(f"{dt}: max err / bound {float((err / bound).max()):.3f}, max bound {float(bound.max()):.3e}")
+    assert float(bound.max()) < 1e-4 * 1000 + 2e-3
+    assert bool((err <= bound).all()), float((err / bound).max())
 
 
 @pytest.mark.parametrize("m,n", [(1, 1), (3, 63), (2, 64), (5, 65), (7, 1023), (4, 1025), (3, 5000), (600, 333),
@@ -178,11 +187,12 @@ def test_chunked_compute_equals_full(rm):
     np.testing.assert_allclose(topk, topk2, rtol=0, atol=1e-12)
 
 
-@pytest.mark.parametrize("m,n,k", [(7, 50, 1), (33, 1000, 15), (64, 17661, 100), (5, 4000, 1024), (3, 200000, 50)])
+@pytest.mark.parametrize("m,n,k", [(7, 50, 1), (33, 1000, 15), (64, 17661, 100), (5, 4000, 1024), (3, 200000, 50), (5, 40, 30)])
 def test_topk_rows_equals_rank_prefix(m, n, k):
     """creid_topk_rows == the first k columns of the stable rank (ties by gallery index), distances included; rows made
     of duplicated values (exact ties across the k-th position) and a constant row (candidate overflow -> flagged,
-    served by the rank kernel) included."""
+    served by the rank kernel) included.  Row 3 leads with +0 and -0 mixed (equal values: gallery index decides, as in
+    rank_rows, which the k * 2 > n branch -- the last case -- goes through)."""
     from centroids_reid_amd import reid_metric as rm
     rng = np.random.default_rng(m * 31 + n)
     d = rng.standard_normal((m, n)).astype(np.float32) * 3
@@ -190,8 +200,13 @@ def test_topk_rows_equals_rank_prefix(m, n, k):
     if m > 2:
         d[1] = 0.25                                             # constant row
         d[2, ::3] = -7.0
+    if m > 3:
+        d[3] = np.abs(d[3]) + 1.0
+        d[3, 5] = 0.0; d[3, 9] = -0.0; d[3, 2] = -0.0; d[3, 30] = 0.0      # the smallest four: 2, 5, 9, 30 in index order
     dt = torch.from_numpy(d).cuda()
     idx, dsel = rm.topk_rows(dt, k)
+    if m > 3:
+        assert idx[3, :4].tolist() == [2, 5, 9, 30][:k]
     ref = rm.rank_rows(dt)[:, :k]
     assert torch.equal(idx, ref)
     assert torch.equal(dsel, torch.gather(dt, 1, ref))
