@@ -1,6 +1,7 @@
 // What the two streamed contractions (stream_eval.hip: fp32 features on the f32 MFMA; stream_h16.hip: bf16 / f16 features on the
-// 16-bit MFMA) share: the tile geometry the work split is expressed in, the epilogue selector, the list capacities, the
-// order-preserving key of a distance, and the work split itself.
+// 16-bit MFMA) share on both sides of a launch: the tile geometry the work split is expressed in, the epilogue selector, the list
+// capacities and the argument tests of the entry points, the order-preserving key of a distance, the work split (stream_split)
+// and a workgroup's share of it (stream_run).  What the kernels do with a finished tile is in stream_consume.hpp.
 #pragma once
 #include "common.hpp"
 #include <stdlib.h>
@@ -9,6 +10,18 @@ constexpr int SQ_TM = 64, SQ_TN = 256;           // a tile: 64 query rows x 256 
 constexpr int EPI_COUNT = 0, EPI_TOPK = 1;       // what a streamed contraction does with a finished tile
 constexpr int PL_MAXC = 128;                     // positive-list capacity of the count epilogue (LDS: [64][cap] keys + histogram)
 constexpr int TS_MIN_CAP = 64, TS_MAX_CAP = 8192;   // candidate-list capacity of the top-k epilogue
+
+// Argument tests of the entry points.  A list capacity is a power of two inside its epilogue's range (the kernels index with
+// shifts and masks: stream_log2cap); m and n leave room for the 32-bit tile arithmetic.
+static bool stream_cap_ok(int64_t cap, int lo, int hi) { return cap >= lo && cap <= hi && (cap & (cap - 1)) == 0; }
+static bool stream_count_cap_ok(int64_t cap) { return stream_cap_ok(cap, 2, PL_MAXC); }
+static bool stream_topk_cap_ok(int64_t cap) { return stream_cap_ok(cap, TS_MIN_CAP, TS_MAX_CAP); }
+static bool stream_mn_ok(int64_t m, int64_t n) { return m <= 0x7ffffff0LL && n <= 0x7ffffff0LL; }
+static int stream_log2cap(int cap) {
+  int l = 0;
+  while ((1 << l) < cap) ++l;
+  return l;
+}
 
 // float -> unsigned with the same order (negatives included; squared distances may be slightly negative)
 __device__ __forceinline__ unsigned mono_key(float d) {
@@ -51,4 +64,37 @@ static StreamSplit stream_split(int64_t m, int64_t n, int64_t D, int64_t elem_by
   const int upw = 4 * t_per;
   const unsigned grid = mode == 0 ? (unsigned)(tiles_m * nsplit) : (unsigned)wg1;
   return StreamSplit{tiles_m, U, upw, mode, grid};
+}
+
+/* Launch of a count contraction (Kernel: an instantiation of either file's kernel, 256 threads): its dynamic LDS is the query
+ * tile's positive keys and histogram, [64][cap] words each -- beyond the default limit at capacity 128, so every instantiation
+ * raises its own limit once. */
+template <auto Kernel, class... Args>
+static int stream_count_launch(const StreamSplit& sp, int cap, void* stream, Args... args) {
+  static const hipError_t attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                        2 * SQ_TM * PL_MAXC * (int)sizeof(unsigned));
+  if (attr_rc != hipSuccess) return (int)attr_rc;
+  hipLaunchKernelGGL(Kernel, dim3(sp.grid), dim3(256), (size_t)2 * SQ_TM * cap * sizeof(unsigned), as_stream(stream), args...);
+  return (int)hipGetLastError();
+}
+
+// Device side of the split: the run [g0, g1) of workgroup blockIdx.x, in units of the rows laid end to end.
+__device__ __forceinline__ void stream_run(int tiles_m, int U, int upw, int mode, long long& g0, long long& g1) {
+  // XCD-aware order: consecutive ids land on different XCDs; every XCD gets a contiguous run of ids
+  int bid = blockIdx.x;
+  {
+    const int nwg = gridDim.x, xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
+    const int base = (xcd < r8) ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
+    bid = base + (bid >> 3);
+  }
+  if (mode == 0) {
+    const int split = bid / tiles_m, tile_m = bid - split * tiles_m;
+    const int u0 = split * upw;
+    g0 = (long long)tile_m * U + u0;
+    g1 = (long long)tile_m * U + min(U, u0 + upw);
+  } else {
+    const long long T = (long long)tiles_m * U;
+    g0 = bid * T / gridDim.x;
+    g1 = (bid + 1) * T / gridDim.x;
+  }
 }

@@ -1,0 +1,218 @@
+// What a streamed contraction does around and after its k-loop, whatever the operand type: stream_eval.hip (fp32 features, f32
+// MFMA) and stream_h16.hip (bf16 / f16 features, 16-bit MFMA) stage their operands, run their k-loops and walk their run of tiles
+// themselves, and call the pieces here for everything that touches a finished accumulator tile.  A tile is 64 x 256, four waves
+// as 2 x 2 (wm, wn), each 32 rows x NJ blocks of 32 columns (block j of wave wn = columns (wn + 2 j) * 32 ..); accumulator
+// register r of lane (l31 = lane & 31, kh = lane >> 5) is row wm * 32 + 4 kh + (r & 3) + 8 (r >> 2), column l31 of its block.
+//
+//   stream_segment_begin<EPI>   per (query tile, run of columns): the LDS state the consumer reads
+//   stream_tile_consume<EPI, H, NJ>   one finished tile: the count or the top-k epilogue
+//   stream_segment_end          count: the LDS histogram leaves for global memory
+//   STREAM_DISPATCH_NJ          the tile width as a compile-time constant
+//   poslist_pad / poslist_rank_emit   the tail of the two positives kernels
+//
+// This file carries the bit contract of the streamed paths: the distance is fmaf(-2, acc, qq[row] + gg[col]), its key mono_key of
+// it -- the bits of the materialised distance kernels -- and ties resolve by gallery index like the stable rank kernel.
+#pragma once
+#include "stream_common.hpp"
+#include <type_traits>
+
+// The LDS state of a segment: per query row of the tile its norm, pid, number of positives and `kmax` (count: key of the row's last
+// positive; top-k: key of the row's threshold); count only: the rows' positive keys [64][cap] and the histogram [64][cap].
+struct StreamLds {
+  float* qq;
+  long long* qpid;
+  int* np;
+  unsigned* kmax;
+  unsigned* keys;
+  unsigned* hist;
+};
+
+// The problem the consumers see: sizes, list capacity, and the global arrays they read or write (count: q_pids .. hist_out;
+// top-k: tau .. cand_count; the other group is unused and may be null).
+struct StreamProblem {
+  int m, n, cap, log2cap;
+  const float* qq;
+  const float* gg;
+  const int64_t* q_pids;
+  const int64_t* g_pids;
+  const unsigned* pos_key;
+  const int32_t* pos_idx;
+  const int32_t* npos;
+  unsigned* hist_out;
+  const float* tau;
+  unsigned long long* cand;
+  int32_t* cand_count;
+};
+
+// Every thread of the 256-thread workgroup calls it, behind a barrier after the previous segment's stream_segment_end; the
+// barrier that opens the first tile publishes the state.
+template <int EPI>
+__device__ __forceinline__ void stream_segment_begin(const StreamLds& L, const StreamProblem& P, int row0) {
+  int ts = threadIdx.x;                            // opaque: the set-up's LDS addresses are recomputed per segment instead of
+  asm volatile("" : "+v"(ts));                     // occupying registers (or scratch) across the k-loops
+  if constexpr (EPI == EPI_TOPK) {
+    if (ts < SQ_TM) {
+      const int rr = row0 + ts;
+      L.qq[ts] = rr < P.m ? P.qq[rr] : 0.f;
+      L.kmax[ts] = rr < P.m ? mono_key(P.tau[rr]) : 0u;
+    }
+  } else {
+    for (int i = ts; i < SQ_TM * P.cap; i += 256) {
+      const int r = i >> P.log2cap, rr = row0 + r;
+      L.keys[i] = rr < P.m ? P.pos_key[(int64_t)rr * P.cap + (i & (P.cap - 1))] : 0xffffffffu;
+      L.hist[i] = 0u;
+    }
+    if (ts < SQ_TM) {
+      const int rr = row0 + ts;
+      const int np = rr < P.m ? P.npos[rr] : 0;
+      L.np[ts] = np > 0 ? np : 0;
+      L.qq[ts] = rr < P.m ? P.qq[rr] : 0.f;
+      L.qpid[ts] = rr < P.m ? (long long)P.q_pids[rr] : 0;
+      L.kmax[ts] = np > 0 ? P.pos_key[(int64_t)rr * P.cap + np - 1] : 0u;
+    }
+  }
+}
+
+// count: flushes the segment's histogram (every thread of the workgroup, after the segment's last tile)
+__device__ __forceinline__ void stream_segment_end(const StreamLds& L, const StreamProblem& P, int row0) {
+  int ts = threadIdx.x;
+  asm volatile("" : "+v"(ts));                     // opaque, as in stream_segment_begin
+  __syncthreads();
+  for (int i = ts; i < SQ_TM * P.cap; i += 256) {
+    const unsigned v = L.hist[i];
+    const int rr = row0 + (i >> P.log2cap);
+    if (v && rr < P.m) atomicAdd(&P.hist_out[(int64_t)rr * P.cap + (i & (P.cap - 1))], v);      // integer: order-independent
+  }
+}
+
+// The finished tile at (row0, col0) is consumed here, in registers (row-major walk: a row's metadata is read once per NJ
+// columns).  Rows beyond m multiply a clamped copy of the last query row and columns beyond n one of the last gallery row; both
+// are dropped here.
+//   EPI_COUNT: every NEGATIVE's distance becomes "how many positives of this query rank before it" (binary search in the
+//              row's LDS positive list, ties walked by gallery index) and bumps the LDS histogram.  H accumulator rows x NJ
+//              column blocks = H NJ searches in flight per lane: the search is a chain of dependent LDS reads (~100 cycles each),
+//              so it is the number of INDEPENDENT chains that sets the epilogue time -- and the registers it needs.
+//              skip_count & 1: timing ablation, no row has positives (results wrong).
+//   EPI_TOPK : every element whose key is <= the row's threshold key takes a slot of its row's list with a global atomicAdd on
+//              cand_count[row] and, while the slot is below `cap`, stores key << 32 | col there.
+template <int EPI, int H, int NJ>
+__device__ __forceinline__ void stream_tile_consume(const f32x16 (&acc)[NJ], int wm, int wn, int l31, int kh, int row0, int col0,
+                                                    int skip_count, const StreamLds& L, const StreamProblem& P) {
+  int rbase = wm * 32 + 4 * kh;                    // opaque per tile: the 16 rows' LDS addresses derived from it are recomputed here
+  asm volatile("" : "+v"(rbase));                  // instead of living in registers (or scratch) across the k-loop
+  float gv[NJ];
+  [[maybe_unused]] long long gp[NJ];
+  bool okc[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const int c = col0 + (wn + 2 * j) * 32 + l31;
+    okc[j] = c < P.n;
+    gv[j] = okc[j] ? P.gg[c] : 0.f;
+    if constexpr (EPI == EPI_COUNT) gp[j] = okc[j] ? (long long)P.g_pids[c] : 0;
+  }
+  if constexpr (EPI == EPI_TOPK) {
+    // One accumulator row at a time: its threshold is one LDS read, a hit one global atomic.
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int rl = rbase + (r & 3) + 8 * (r >> 2);
+      const float qv = L.qq[rl];
+      const unsigned kt = L.kmax[rl];
+      const bool okr = row0 + rl < P.m;
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        const unsigned key = mono_key(fmaf(-2.0f, acc[j][r], qv + gv[j]));
+        if (okr && okc[j] && key <= kt) {
+          const int64_t rr = row0 + rl;
+          const int slot = atomicAdd(&P.cand_count[rr], 1);
+          if (slot < P.cap)
+            P.cand[rr * P.cap + slot] = ((unsigned long long)key << 32) | (unsigned)(col0 + (wn + 2 * j) * 32 + l31);
+        }
+      }
+    }
+  } else {
+    static_assert(16 % H == 0, "H rows at a time");
+#pragma unroll
+    for (int r = 0; r < 16; r += H) {
+      int rl[H], np[H], lo[H][NJ];
+      unsigned key[H][NJ];
+      bool live[H][NJ];
+      const unsigned* K[H];
+#pragma unroll
+      for (int h = 0; h < H; ++h) {
+        rl[h] = rbase + ((r + h) & 3) + 8 * ((r + h) >> 2);
+        np[h] = (skip_count & 1) ? 0 : L.np[rl[h]];
+        const long long qp = L.qpid[rl[h]];
+        const float qv = L.qq[rl[h]];
+        const unsigned kmax = L.kmax[rl[h]];
+        K[h] = L.keys + (rl[h] << P.log2cap);
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+          key[h][j] = mono_key(fmaf(-2.0f, acc[j][r + h], qv + gv[j]));
+          // positives / removed entries (same pid) are not counted; behind every positive: affects no rank
+          live[h][j] = np[h] > 0 && okc[j] && gp[j] != qp && key[h][j] <= kmax;
+          lo[h][j] = 0;
+        }
+      }
+      if (np[0] == 0 && np[H - 1] == 0) continue;                    // uniform per wave half
+      for (int step = P.cap >> 1; step > 0; step >>= 1) {
+#pragma unroll
+        for (int h = 0; h < H; ++h)
+#pragma unroll
+          for (int j = 0; j < NJ; ++j) lo[h][j] += (K[h][lo[h][j] + step - 1] < key[h][j]) ? step : 0;
+      }
+#pragma unroll
+      for (int h = 0; h < H; ++h)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+          int l = lo[h][j];
+          l += (K[h][l] < key[h][j]) ? 1 : 0;                        // l = #positives with key strictly below
+          if (live[h][j]) {
+            if (l < np[h] && K[h][l] == key[h][j]) {                 // ties: by gallery index (rare)
+              const int c = col0 + (wn + 2 * j) * 32 + l31;
+              int rr_ = row0 + rl[h];
+              asm volatile("" : "+v"(rr_));                          // keeps 16 rows' index pointers out of the k-loop's registers
+              while (l < np[h] && K[h][l] == key[h][j] && P.pos_idx[(int64_t)rr_ * P.cap + l] < c) ++l;
+            }
+            if (l < np[h]) atomicAdd(&L.hist[(rl[h] << P.log2cap) + l], 1u);
+          }
+        }
+    }
+  }
+}
+
+// f(std::integral_constant<int, nj>{}, ...) for the tile width nj = 1 .. 4 units.  A macro on purpose: through a function that
+// takes the callable, in every form tried, the register allocator spills 3-4 SGPRs in the fp32 count kernels and 1 in the 16-bit
+// ones; expanded in place it spills none.
+#define STREAM_DISPATCH_NJ(nj, f, ...)                                      \
+  do {                                                                      \
+    if ((nj) == 4) f(std::integral_constant<int, 4>{}, __VA_ARGS__);        \
+    else if ((nj) == 3) f(std::integral_constant<int, 3>{}, __VA_ARGS__);   \
+    else if ((nj) == 2) f(std::integral_constant<int, 2>{}, __VA_ARGS__);   \
+    else f(std::integral_constant<int, 1>{}, __VA_ARGS__);                  \
+  } while (0)
+
+// ---- the positives kernels (one T-thread workgroup per query): what does not depend on how the distances are produced
+
+// a query's lists start as padding: the count's binary search runs over all `cap` entries
+template <int T>
+__device__ __forceinline__ void poslist_pad(unsigned* __restrict__ okey, int32_t* __restrict__ oidx, int cap) {
+  for (int i = threadIdx.x; i < cap; i += T) { okey[i] = 0xffffffffu; oidx[i] = 0x7fffffff; }
+}
+
+// The nc <= cap candidates (gallery index cand[c], distance key skey[c], both in LDS and published by a barrier) leave sorted by
+// (key, gallery index): rank by counting.
+template <int T>
+__device__ __forceinline__ void poslist_rank_emit(const unsigned* skey, const int* cand, int nc, unsigned* __restrict__ okey,
+                                                  int32_t* __restrict__ oidx, int32_t* __restrict__ npos_q) {
+  for (int c = threadIdx.x; c < nc; c += T) {
+    const unsigned k = skey[c];
+    const int gi = cand[c];
+    int pos = 0;
+    for (int o = 0; o < nc; ++o) {
+      const unsigned ko = skey[o];
+      pos += (ko < k || (ko == k && cand[o] < gi)) ? 1 : 0;
+    }
+    okey[pos] = k; oidx[pos] = gi;
+  }
+  if (threadIdx.x == 0) *npos_q = nc;
+}

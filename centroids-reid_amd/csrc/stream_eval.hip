@@ -20,10 +20,12 @@
 // consumer of the same contraction: sqdist_count_f32_kernel<.., EPI_TOPK> keeps the k-loop, staging and work split and
 // swaps the epilogue for "append (distance, column) to the row's candidate list when the distance is within the row's
 // threshold"; stream_topk_select_kernel sorts each list and keeps the first k.
-// bf16 / f16 features: the same contraction, epilogues and positives on the 16-bit MFMA are in stream_h16.hip.
-#include "stream_common.hpp"
+// What happens to a finished accumulator tile -- both epilogues, the LDS state they read, the histogram flush -- and the tail of
+// the positives kernel do not depend on the feature type: stream_consume.hpp, shared with stream_h16.hip (bf16 / f16 features on
+// the 16-bit MFMA).  The work split, a workgroup's run of it and the entry points' argument tests: stream_common.hpp.  This file
+// keeps what is fp32: the operand staging and LDS image, the k-loop on the f32 MFMA, and the fmaf chain of the positives.
+#include "stream_consume.hpp"
 #include "topk_tail.hpp"
-#include <type_traits>
 
 namespace {
 constexpr int SQ_BK = 16;                        // (tile geometry, epilogue selector, list capacities, mono_key: stream_common.hpp)
@@ -53,7 +55,7 @@ __global__ __launch_bounds__(PL_MAXC) void stream_poslist_kernel(
   const int qi = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   unsigned* okey = pos_key + (int64_t)qi * cap;
   int32_t* oidx = pos_idx + (int64_t)qi * cap;
-  for (int i = tid; i < cap; i += PL_MAXC) { okey[i] = 0xffffffffu; oidx[i] = 0x7fffffff; }   // padding for the search
+  poslist_pad<PL_MAXC>(okey, oidx, cap);
   const int slot = q_slot[qi];
   if (slot < 0) { if (tid == 0) npos[qi] = 0; return; }
   const int64_t c0 = csr_off[slot], c1 = csr_off[slot + 1];
@@ -82,9 +84,8 @@ __global__ __launch_bounds__(PL_MAXC) void stream_poslist_kernel(
   if (nc > cap || nc > PL_MAXC) { if (tid == 0) npos[qi] = -1; return; }   // the caller sends such queries to the general path
   if (nc == 0) { if (tid == 0) npos[qi] = 0; return; }
   const float* __restrict__ qrow = q + (int64_t)qi * D;
-  int gi = 0;
   if (tid < nc) {
-    gi = cand[tid];
+    const int gi = cand[tid];
     const float* __restrict__ grow = g + (int64_t)gi * D;
     float acc = 0.f;
     int k = 0;
@@ -114,16 +115,7 @@ __global__ __launch_bounds__(PL_MAXC) void stream_poslist_kernel(
     skey[tid] = mono_key(fmaf(-2.0f, acc, qq[qi] + gg[gi]));                          // sqdist epilogue, same bits
   }
   __syncthreads();
-  if (tid < nc) {                                      // rank by counting over (key, gallery index)
-    const unsigned k = skey[tid];
-    int pos = 0;
-    for (int c = 0; c < nc; ++c) {
-      const unsigned kc = skey[c];
-      pos += (kc < k || (kc == k && cand[c] < gi)) ? 1 : 0;
-    }
-    okey[pos] = k; oidx[pos] = gi;
-  }
-  if (tid == 0) npos[qi] = nc;
+  poslist_rank_emit<PL_MAXC>(skey, cand, nc, okey, oidx, &npos[qi]);
 }
 
 // ----------------------------------------------------------------------------------------
@@ -147,14 +139,11 @@ __global__ __launch_bounds__(PL_MAXC) void stream_poslist_kernel(
 //          6 for 5.42).  Measured without the gallery sharing of mode 0: no loss at these sizes (profiles/r06_eval_kloop.md).
 // (!FULLK -- a feature width that is not a multiple of 16 -- carries the zero-fill masks on top and runs one workgroup per CU.)
 //
-// EPI selects the epilogue; everything up to the finished accumulator tile is common.
+// EPI selects the epilogue (stream_tile_consume in stream_consume.hpp); everything up to the finished accumulator tile is common.
 //   EPI_COUNT: the evaluation's count described above (the arguments from q_pids to hist_out and skip_count; tau / cand /
 //              cand_count unused).
-//   EPI_TOPK : retrieval.  Every element inside the problem whose key = mono_key(fmaf(-2, acc, qq[row] + gg[col])) -- the bits of
-//              creid_sqdist_matrix -- is <= mono_key(tau[row]) takes a slot of its row's list with a global atomicAdd on
-//              cand_count[row] and, while the slot is below `cap`, stores key << 32 | col there.  Hits are rare (a few hundred
-//              to a thousand of a row's n columns), so the atomics are not a cost.  LDS state per tile: the 64 threshold keys
-//              (s_kmax) next to s_qq; no dynamic LDS; the label / list arguments of the count are unused.
+//   EPI_TOPK : retrieval: the candidate collection (tau, cand, cand_count; cap is the list capacity).  LDS state per tile: the 64
+//              threshold keys (s_kmax) next to s_qq; no dynamic LDS; the label / list arguments of the count are unused.
 template <int ABL, bool FULLK, int EPI = EPI_COUNT>
 __global__ __launch_bounds__(256, FULLK ? 2 : 1) void sqdist_count_f32_kernel(
     const float* __restrict__ q, const float* __restrict__ g, const float* __restrict__ qq, const float* __restrict__ gg,
@@ -174,24 +163,10 @@ __global__ __launch_bounds__(256, FULLK ? 2 : 1) void sqdist_count_f32_kernel(
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
   const int l31 = lane & 31, kh = lane >> 5;
-  // XCD-aware order: consecutive ids land on different XCDs; every XCD gets a contiguous run of ids
-  int bid = blockIdx.x;
-  {
-    const int nwg = gridDim.x, xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    const int base = (xcd < r8) ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
-    bid = base + (bid >> 3);
-  }
+  const StreamLds L{s_qq, s_qpid, s_np, s_kmax, s_keys, s_hist};
+  const StreamProblem P{m, n, cap, log2cap, qq, gg, q_pids, g_pids, pos_key, pos_idx, npos, hist_out, tau, cand, cand_count};
   long long g0, g1;                              // this workgroup's run, in units of the rows laid end to end
-  if (mode == 0) {
-    const int split = bid / tiles_m, tile_m = bid - split * tiles_m;
-    const int u0 = split * upw;
-    g0 = (long long)tile_m * U + u0;
-    g1 = (long long)tile_m * U + min(U, u0 + upw);
-  } else {
-    const long long T = (long long)tiles_m * U;
-    g0 = bid * T / gridDim.x;
-    g1 = (bid + 1) * T / gridDim.x;
-  }
+  stream_run(tiles_m, U, upw, mode, g0, g1);
 
   const int lrow = tid >> 2, lkc = tid & 3;
   // Staging addresses: one wave-uniform base per operand (SGPRs; the k advance is scalar arithmetic) + a 32-bit byte offset per
@@ -349,89 +324,9 @@ __global__ __launch_bounds__(256, FULLK ? 2 : 1) void sqdist_count_f32_kernel(
     for (; t + 2 < nk; t += 2) { body(I0{}, t); body(I1{}, t + 1); }
     if (t + 2 == nk) { body(I0{}, t); last(1); } else last(0);
     if (next >= 0) { set_tile(next); gload(I0{}, 0, 2, 4); }        // flies while the epilogue runs
-    // ---- epilogue: the tile is consumed here (row-major walk: the row's metadata is read once per NJ columns)
-    int rbase = wm * 32 + 4 * kh;                  // opaque per tile: the 16 rows' LDS addresses derived from it are recomputed here
-    asm volatile("" : "+v"(rbase));                // instead of living in registers (or scratch) across the k-loop
-    float gv[NJ];
-    [[maybe_unused]] long long gp[NJ];
-    bool okc[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      const int c = col0 + (wn + 2 * j) * 32 + l31;
-      okc[j] = c < n;
-      gv[j] = okc[j] ? gg[c] : 0.f;
-      if constexpr (EPI == EPI_COUNT) gp[j] = okc[j] ? (long long)g_pids[c] : 0;
-    }
-    if constexpr (EPI == EPI_TOPK) {
-      // One accumulator row at a time: its threshold is one LDS read, a hit one global atomic (rows beyond m multiply a
-      // clamped copy of the last query row and are dropped here, like columns beyond n).
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int rl = rbase + (r & 3) + 8 * (r >> 2);
-        const float qv = s_qq[rl];
-        const unsigned kt = s_kmax[rl];
-        const bool okr = row0 + rl < m;
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-          const unsigned key = mono_key(fmaf(-2.0f, acc[j][r], qv + gv[j]));
-          if (okr && okc[j] && key <= kt) {
-            const int64_t rr = row0 + rl;
-            const int slot = atomicAdd(&cand_count[rr], 1);
-            if (slot < cap)
-              cand[rr * cap + slot] = ((unsigned long long)key << 32) | (unsigned)(col0 + (wn + 2 * j) * 32 + l31);
-          }
-        }
-      }
-      return;
-    }
-    // Two accumulator rows x NJ column blocks = 2 NJ binary searches in flight per lane: the search is a chain of
-    // dependent LDS reads (~100 cycles each), so it is the number of INDEPENDENT chains that sets the epilogue time.
-#pragma unroll
-    for (int r = 0; r < 16; r += 2) {
-      int rl[2], np[2], lo[2][NJ];
-      unsigned key[2][NJ];
-      bool live[2][NJ];
-      const unsigned* K[2];
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        rl[h] = rbase + ((r + h) & 3) + 8 * ((r + h) >> 2);
-        np[h] = (skip_count & 1) ? 0 : s_np[rl[h]];
-        const long long qp = s_qpid[rl[h]];
-        const float qv = s_qq[rl[h]];
-        const unsigned kmax = s_kmax[rl[h]];
-        K[h] = s_keys + (rl[h] << log2cap);
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-          key[h][j] = mono_key(fmaf(-2.0f, acc[j][r + h], qv + gv[j]));
-          // positives / removed entries (same pid) are not counted; behind every positive: affects no rank
-          live[h][j] = np[h] > 0 && okc[j] && gp[j] != qp && key[h][j] <= kmax;
-          lo[h][j] = 0;
-        }
-      }
-      if (np[0] == 0 && np[1] == 0) continue;                      // uniform per wave half
-      for (int step = cap >> 1; step > 0; step >>= 1) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-          for (int j = 0; j < NJ; ++j) lo[h][j] += (K[h][lo[h][j] + step - 1] < key[h][j]) ? step : 0;
-      }
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-          int l = lo[h][j];
-          l += (K[h][l] < key[h][j]) ? 1 : 0;                      // l = #positives with key strictly below
-          if (live[h][j]) {
-            if (l < np[h] && K[h][l] == key[h][j]) {               // ties: by gallery index (rare)
-              const int c = col0 + (wn + 2 * j) * 32 + l31;
-              int rr_ = row0 + rl[h];
-              asm volatile("" : "+v"(rr_));                        // keeps 16 rows' index pointers out of the k-loop's registers
-              while (l < np[h] && K[h][l] == key[h][j] && pos_idx[(int64_t)rr_ * cap + l] < c) ++l;
-            }
-            if (l < np[h]) atomicAdd(&s_hist[(rl[h] << log2cap) + l], 1u);
-          }
-        }
-    }
+    // Two accumulator rows at a time in the count: with one workgroup's registers to itself (FULLK: half a CU's) this kernel
+    // can afford 2 NJ independent search chains per lane.
+    stream_tile_consume<EPI, 2, NJ>(acc, wm, wn, l31, kh, row0, col0, skip_count, L, P);
   };
 
   while (g0 < g1) {                               // the run's segments: one per row it touches
@@ -440,29 +335,7 @@ __global__ __launch_bounds__(256, FULLK ? 2 : 1) void sqdist_count_f32_kernel(
     g0 += u1 - u0;
     row0 = row * SQ_TM;
     __syncthreads();                               // the previous segment's histogram has been flushed
-    int ts = tid;                                  // opaque: the set-up's LDS addresses are recomputed per segment instead of
-    asm volatile("" : "+v"(ts));                   // occupying registers (or scratch) across the k-loops
-    if constexpr (EPI == EPI_TOPK) {
-      if (ts < SQ_TM) {
-        const int rr = row0 + ts;
-        s_qq[ts] = rr < m ? qq[rr] : 0.f;
-        s_kmax[ts] = rr < m ? mono_key(tau[rr]) : 0u;
-      }
-    } else {
-      for (int i = ts; i < SQ_TM * cap; i += 256) {
-        const int r = i >> log2cap, rr = row0 + r;
-        s_keys[i] = rr < m ? pos_key[(int64_t)rr * cap + (i & (cap - 1))] : 0xffffffffu;
-        s_hist[i] = 0u;
-      }
-      if (ts < SQ_TM) {
-        const int rr = row0 + ts;
-        const int np = rr < m ? npos[rr] : 0;
-        s_np[ts] = np > 0 ? np : 0;
-        s_qq[ts] = rr < m ? qq[rr] : 0.f;
-        s_qpid[ts] = rr < m ? (long long)q_pids[rr] : 0;
-        s_kmax[ts] = np > 0 ? pos_key[(int64_t)rr * cap + np - 1] : 0u;
-      }
-    }
+    stream_segment_begin<EPI>(L, P, row0);
     abase = reinterpret_cast<const char*>(q + (int64_t)min(row0, m - 1) * D);
     aoff = (unsigned)(min(row0 + lrow, m - 1) - min(row0, m - 1)) * (unsigned)D * 4u + 16u * lkc;
     const int cend = u1 * 64;
@@ -471,20 +344,10 @@ __global__ __launch_bounds__(256, FULLK ? 2 : 1) void sqdist_count_f32_kernel(
     gload(I0{}, 0, 2, 4);
     while (col < cend) {
       const int nj = min(4, (cend - col) >> 6), next = col + 256 < cend ? col + 256 : -1;
-      if (nj == 4) tile(std::integral_constant<int, 4>{}, col, next);
-      else if (nj == 3) tile(std::integral_constant<int, 3>{}, col, next);
-      else if (nj == 2) tile(std::integral_constant<int, 2>{}, col, next);
-      else tile(std::integral_constant<int, 1>{}, col, next);
+      STREAM_DISPATCH_NJ(nj, tile, col, next);
       col += 256;
     }
-    if constexpr (EPI == EPI_COUNT) {
-      __syncthreads();
-      for (int i = ts; i < SQ_TM * cap; i += 256) {
-        const unsigned v = s_hist[i];
-        const int rr = row0 + (i >> log2cap);
-        if (v && rr < m) atomicAdd(&hist_out[(int64_t)rr * cap + (i & (cap - 1))], v);      // integer: order-independent
-      }
-    }
+    if constexpr (EPI == EPI_COUNT) stream_segment_end(L, P, row0);
   }
 }
 
@@ -613,8 +476,6 @@ __global__ __launch_bounds__(TS_T) void stream_topk_select_kernel(const unsigned
   if (tid == 0) flags[row] = 0;
 }
 
-// (the work split of the streamed contraction: stream_split() in stream_common.hpp, shared with stream_h16.hip)
-
 extern "C" {
 
 /* Device-side index for the streamed evaluation.  g_pids / g_cams int64[n], q_pids / q_cams int64[m] on the device; the pid
@@ -650,8 +511,8 @@ int creid_stream_poslist(const float* q, const float* g, const float* qq, const 
   CREID_CHECK_ARG(m >= 0 && n > 0 && D > 0);
   if (m == 0) return 0;
   CREID_CHECK_ARG(q && g && qq && gg && q_slot && csr_off && g_order && q_cams && g_cams && pos_key && pos_idx && npos);
-  if (cap < 2 || cap > PL_MAXC || (cap & (cap - 1)) != 0) return CREID_E_SHAPE;
-  if (n > 0x7ffffff0LL || m > 0x7ffffff0LL) return CREID_E_SHAPE;
+  if (!stream_count_cap_ok(cap)) return CREID_E_SHAPE;
+  if (!stream_mn_ok(m, n)) return CREID_E_SHAPE;
   hipLaunchKernelGGL(stream_poslist_kernel, dim3((unsigned)m), dim3(PL_MAXC), 0, as_stream(stream), q, g, qq, gg, (int)D, q_slot,
                      csr_off, g_order, q_cams, g_cams, (int)cap, pos_key, pos_idx, npos);
   CREID_LAUNCH_RET();
@@ -663,25 +524,16 @@ int creid_stream_count(const float* q, const float* g, const float* qq, const fl
   CREID_CHECK_ARG(m >= 0 && n > 0 && D > 0);
   if (m == 0) return 0;
   CREID_CHECK_ARG(q && g && qq && gg && q_pids && g_pids && pos_key && pos_idx && npos && hist);
-  if (cap < 2 || cap > PL_MAXC || (cap & (cap - 1)) != 0 || D % 4 != 0) return CREID_E_SHAPE;
-  if (n > 0x7ffffff0LL || m > 0x7ffffff0LL) return CREID_E_SHAPE;
-  int log2cap = 0;
-  while ((1 << log2cap) < cap) ++log2cap;
+  if (!stream_count_cap_ok(cap) || D % 4 != 0) return CREID_E_SHAPE;
+  if (!stream_mn_ok(m, n)) return CREID_E_SHAPE;
+  const int log2cap = stream_log2cap(cap);
   // timing ablation only (CREID_STREAM_NOEPI=1: contraction without the count epilogue -- results are then wrong)
   static const int skip_count = creid_ablation_env("CREID_STREAM_NOEPI");
   const StreamSplit sp = stream_split(m, n, D);
-  const size_t dyn = (size_t)2 * SQ_TM * cap * sizeof(unsigned);
 #define CREID_COUNT_LAUNCH_(A, F)                                                                                     \
-  do {                                                                                                                 \
-    static const hipError_t attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(sqdist_count_f32_kernel<A, F>), \
-                                                          hipFuncAttributeMaxDynamicSharedMemorySize,                  \
-                                                          2 * SQ_TM * PL_MAXC * (int)sizeof(unsigned));                \
-    if (attr_rc != hipSuccess) return (int)attr_rc;                                                                    \
-    hipLaunchKernelGGL((sqdist_count_f32_kernel<A, F>), dim3(sp.grid), dim3(256), dyn, as_stream(stream),              \
-                       q, g, qq, gg, (int)m, (int)n, (int)D, q_pids, g_pids, (int)cap, log2cap, pos_key, pos_idx, npos, hist,  \
-                       sp.tiles_m, sp.U, sp.upw, sp.mode, skip_count & 1, (const float*)nullptr,                       \
-                       (unsigned long long*)nullptr, (int32_t*)nullptr);                                               \
-  } while (0)
+  return stream_count_launch<sqdist_count_f32_kernel<A, F>>(                                                           \
+      sp, (int)cap, stream, q, g, qq, gg, (int)m, (int)n, (int)D, q_pids, g_pids, (int)cap, log2cap, pos_key, pos_idx, npos, hist, \
+      sp.tiles_m, sp.U, sp.upw, sp.mode, skip_count & 1, (const float*)nullptr, (unsigned long long*)nullptr, (int32_t*)nullptr)
 #define CREID_COUNT_LAUNCH(A)                                                                                          \
   do { if (D % SQ_BK == 0) CREID_COUNT_LAUNCH_(A, true); else CREID_COUNT_LAUNCH_(0, false); } while (0)
 #ifdef CREID_ABL_BUILD
@@ -702,7 +554,6 @@ int creid_stream_count(const float* q, const float* g, const float* qq, const fl
 #endif
 #undef CREID_COUNT_LAUNCH
 #undef CREID_COUNT_LAUNCH_
-  CREID_LAUNCH_RET();
 }
 
 int creid_stream_finalize(const int32_t* npos, const uint32_t* hist, int64_t m, int32_t cap, uint8_t* valid, double* ap,
@@ -718,8 +569,8 @@ int creid_stream_finalize(const int32_t* npos, const uint32_t* hist, int64_t m, 
 int creid_stream_topk_collect(const float* q, const float* g, const float* qq, const float* gg, int64_t m, int64_t n,
                               int64_t D, const float* tau, int32_t cap, uint64_t* cand, int32_t* count, void* stream) {
   CREID_CHECK_ARG(m >= 0 && n > 0 && D > 0);
-  if (cap < TS_MIN_CAP || cap > TS_MAX_CAP || (cap & (cap - 1)) != 0 || D % 4 != 0) return CREID_E_SHAPE;
-  if (n > 0x7ffffff0LL || m > 0x7ffffff0LL) return CREID_E_SHAPE;
+  if (!stream_topk_cap_ok(cap) || D % 4 != 0) return CREID_E_SHAPE;
+  if (!stream_mn_ok(m, n)) return CREID_E_SHAPE;
   if (m == 0) return 0;
   CREID_CHECK_ARG(q && g && qq && gg && tau && cand && count);
   const StreamSplit sp = stream_split(m, n, D);
@@ -736,7 +587,7 @@ int creid_stream_topk_collect(const float* q, const float* g, const float* qq, c
 int creid_stream_topk_select(const uint64_t* cand, const int32_t* count, int64_t m, int32_t cap, int32_t k, int64_t* out_idx,
                              float* out_dist, uint8_t* flags, void* stream) {
   CREID_CHECK_ARG(m >= 0 && k >= 1);
-  if (cap < TS_MIN_CAP || cap > TS_MAX_CAP || (cap & (cap - 1)) != 0 || k > 1024 || k > cap) return CREID_E_SHAPE;
+  if (!stream_topk_cap_ok(cap) || k > 1024 || k > cap) return CREID_E_SHAPE;
   if (m > 0x7fffffffLL) return CREID_E_SHAPE;
   if (m == 0) return 0;
   CREID_CHECK_ARG(cand && count && out_idx && flags);

@@ -10,16 +10,15 @@
 // bits of the materialised one, the exact-threshold argument of topk_stream and the tie rule of the count carry over, and the
 // streamed results equal the materialised ones bit for bit.
 //
-//   sqdist_stream_h16_kernel<DT, EPI>   persistent: a workgroup walks a run of gallery tiles for one query tile (the work
-//                                       split of the fp32 kernel: stream_split(), both modes) and consumes every finished
-//                                       64 x 256 tile in registers with the count or the top-k epilogue.  The epilogues are
-//                                       this file's own copies of sqdist_count_f32_kernel's: that kernel's register
-//                                       allocation is tuned to the last VGPR and was left alone.
+//   sqdist_stream_h16_kernel<DT, EPI>   persistent: a workgroup walks a run of gallery tiles for one query tile and hands every
+//                                       finished 64 x 256 tile, in registers, to the count or the top-k epilogue.
 //   stream_poslist_h16_kernel<DT>       the distances of a query to its <= 128 positives on the same MFMA (a 16-bit MFMA's
 //                                       internal summation cannot be reproduced with an fmaf chain).
-// The plan, finalize and top-k select launches of stream_eval.hip do not depend on the feature type and serve both.
-#include "stream_common.hpp"
-#include <type_traits>
+// This file keeps what is 16-bit: the operand staging and LDS image, the k-loop, and the positives' distances.  The epilogues, the
+// LDS state they read, the histogram flush and the positives' tail are stream_consume.hpp's, the work split (stream_split,
+// stream_run) and the argument tests stream_common.hpp's -- one copy each, shared with the fp32 kernels of stream_eval.hip.  The
+// plan, finalize and top-k select launches of stream_eval.hip do not depend on the feature type and serve both.
+#include "stream_consume.hpp"
 
 namespace {
 constexpr int H_BK = 64;                         // k-tile: 64 elements = one 128-byte LDS row = 8 chunks of 16 bytes
@@ -50,7 +49,7 @@ __global__ __launch_bounds__(64) void stream_poslist_h16_kernel(
   const int qi = blockIdx.x, lane = threadIdx.x;
   unsigned* okey = pos_key + (int64_t)qi * cap;
   int32_t* oidx = pos_idx + (int64_t)qi * cap;
-  for (int i = lane; i < cap; i += 64) { okey[i] = 0xffffffffu; oidx[i] = 0x7fffffff; }   // padding for the search
+  poslist_pad<64>(okey, oidx, cap);
   const int slot = q_slot[qi];
   if (slot < 0) { if (lane == 0) npos[qi] = 0; return; }
   const int64_t c0 = csr_off[slot], c1 = csr_off[slot + 1];
@@ -136,17 +135,7 @@ __global__ __launch_bounds__(64) void stream_poslist_h16_kernel(
   else if (nblk == 3) dist(std::integral_constant<int, 3>{});
   else dist(std::integral_constant<int, 4>{});
   __syncthreads();
-  for (int c = lane; c < nc; c += 64) {                // rank by counting over (key, gallery index)
-    const unsigned k = skey[c];
-    const int gi = cand[c];
-    int pos = 0;
-    for (int o = 0; o < nc; ++o) {
-      const unsigned ko = skey[o];
-      pos += (ko < k || (ko == k && cand[o] < gi)) ? 1 : 0;
-    }
-    okey[pos] = k; oidx[pos] = gi;
-  }
-  if (lane == 0) npos[qi] = nc;
+  poslist_rank_emit<64>(skey, cand, nc, okey, oidx, &npos[qi]);
 }
 
 // ----------------------------------------------------------------------------------------
@@ -159,8 +148,8 @@ __global__ __launch_bounds__(64) void stream_poslist_h16_kernel(
 //    1 + NJ fragments for NJ MFMAs.  A k-tile is fetched into registers while the previous one is multiplied and replaces it
 //    in LDS between two barriers; the second workgroup of the CU covers those waits.  The kernel is bound by operand traffic
 //    (51 FLOP per operand byte) and its epilogue, not by the MFMA (profiles/stream_h16.md).
-//    The work split, the clamped rows / columns, the narrow last tile (NJ < 4) and both epilogues are the fp32 kernel's; see
-//    stream_eval.hip.
+//    The work split (both modes), the clamped rows / columns and the narrow last tile (NJ < 4) are described at
+//    sqdist_count_f32_kernel in stream_eval.hip.
 // ----------------------------------------------------------------------------------------
 template <int DT, int EPI>
 __global__ __launch_bounds__(256, 2) void sqdist_stream_h16_kernel(
@@ -181,24 +170,10 @@ __global__ __launch_bounds__(256, 2) void sqdist_stream_h16_kernel(
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
   const int l31 = lane & 31, kh = lane >> 5;
-  // XCD-aware order: consecutive ids land on different XCDs; every XCD gets a contiguous run of ids
-  int bid = blockIdx.x;
-  {
-    const int nwg = gridDim.x, xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    const int base = (xcd < r8) ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
-    bid = base + (bid >> 3);
-  }
+  const StreamLds L{s_qq, s_qpid, s_np, s_kmax, s_keys, s_hist};
+  const StreamProblem P{m, n, cap, log2cap, qq, gg, q_pids, g_pids, pos_key, pos_idx, npos, hist_out, tau, cand, cand_count};
   long long g0, g1;                              // this workgroup's run, in units of the rows laid end to end
-  if (mode == 0) {
-    const int split = bid / tiles_m, tile_m = bid - split * tiles_m;
-    const int u0 = split * upw;
-    g0 = (long long)tile_m * U + u0;
-    g1 = (long long)tile_m * U + min(U, u0 + upw);
-  } else {
-    const long long T = (long long)tiles_m * U;
-    g0 = bid * T / gridDim.x;
-    g1 = (bid + 1) * T / gridDim.x;
-  }
+  stream_run(tiles_m, U, upw, mode, g0, g1);
 
   // Staging: a pass of the 256 threads covers 32 rows x 8 chunks; the query tile is 2 passes, the gallery tile 8 (2 per unit).
   // Row lrow + 32 i has the swizzle of row lrow, so one LDS offset serves every pass.
@@ -281,92 +256,10 @@ __global__ __launch_bounds__(256, 2) void sqdist_stream_h16_kernel(
     }
     // the next tile's k-tile 0: under the (light) top-k epilogue; behind the count epilogue, whose searches need the registers
     if constexpr (EPI == EPI_TOPK) { if (next >= 0) { set_tile(next); gload(0, 8); } }
-    // ---- epilogue: the tile is consumed here (row-major walk: the row's metadata is read once per NJ columns)
-    int rbase = wm * 32 + 4 * kh;                  // opaque per tile: the 16 rows' LDS addresses derived from it are recomputed here
-    asm volatile("" : "+v"(rbase));                // instead of living in registers (or scratch) across the k-loop
-    float gv[NJ];
-    [[maybe_unused]] long long gp[NJ];
-    bool okc[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      const int c = col0 + (wn + 2 * j) * 32 + l31;
-      okc[j] = c < n;
-      gv[j] = okc[j] ? gg[c] : 0.f;
-      if constexpr (EPI == EPI_COUNT) gp[j] = okc[j] ? (long long)g_pids[c] : 0;
-    }
-    if constexpr (EPI == EPI_TOPK) {
-      // One accumulator row at a time: its threshold is one LDS read, a hit one global atomic (rows beyond m multiply a
-      // clamped copy of the last query row and are dropped here, like columns beyond n).
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int rl = rbase + (r & 3) + 8 * (r >> 2);
-        const float qv = s_qq[rl];
-        const unsigned kt = s_kmax[rl];
-        const bool okr = row0 + rl < m;
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-          const unsigned key = mono_key(fmaf(-2.0f, acc[j][r], qv + gv[j]));
-          if (okr && okc[j] && key <= kt) {
-            const int64_t rr = row0 + rl;
-            const int slot = atomicAdd(&cand_count[rr], 1);
-            if (slot < cap)
-              cand[rr * cap + slot] = ((unsigned long long)key << 32) | (unsigned)(col0 + (wn + 2 * j) * 32 + l31);
-          }
-        }
-      }
-      return;
-    }
-    // H accumulator rows x NJ column blocks = H NJ binary searches in flight per lane (the search is a chain of dependent LDS
-    // reads).  The fp32 kernel runs two rows at a time; one row keeps this kernel inside the 256 registers of two workgroups
-    // per CU, and the second workgroup fills the gaps of the chains.
-    constexpr int H = 1;
-#pragma unroll
-    for (int r = 0; r < 16; r += H) {
-      int rl[H], np[H], lo[H][NJ];
-      unsigned key[H][NJ];
-      bool live[H][NJ];
-      const unsigned* K[H];
-#pragma unroll
-      for (int h = 0; h < H; ++h) {
-        rl[h] = rbase + ((r + h) & 3) + 8 * ((r + h) >> 2);
-        np[h] = s_np[rl[h]];
-        const long long qp = s_qpid[rl[h]];
-        const float qv = s_qq[rl[h]];
-        const unsigned kmax = s_kmax[rl[h]];
-        K[h] = s_keys + (rl[h] << log2cap);
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-          key[h][j] = mono_key(fmaf(-2.0f, acc[j][r + h], qv + gv[j]));
-          // positives / removed entries (same pid) are not counted; behind every positive: affects no rank
-          live[h][j] = np[h] > 0 && okc[j] && gp[j] != qp && key[h][j] <= kmax;
-          lo[h][j] = 0;
-        }
-      }
-      if (np[0] == 0 && np[H - 1] == 0) continue;                      // uniform per wave half
-      for (int step = cap >> 1; step > 0; step >>= 1) {
-#pragma unroll
-        for (int h = 0; h < H; ++h)
-#pragma unroll
-          for (int j = 0; j < NJ; ++j) lo[h][j] += (K[h][lo[h][j] + step - 1] < key[h][j]) ? step : 0;
-      }
-#pragma unroll
-      for (int h = 0; h < H; ++h)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-          int l = lo[h][j];
-          l += (K[h][l] < key[h][j]) ? 1 : 0;                      // l = #positives with key strictly below
-          if (live[h][j]) {
-            if (l < np[h] && K[h][l] == key[h][j]) {               // ties: by gallery index (rare)
-              const int c = col0 + (wn + 2 * j) * 32 + l31;
-              int rr_ = row0 + rl[h];
-              asm volatile("" : "+v"(rr_));                        // keeps 16 rows' index pointers out of the k-loop's registers
-              while (l < np[h] && K[h][l] == key[h][j] && pos_idx[(int64_t)rr_ * cap + l] < c) ++l;
-            }
-            if (l < np[h]) atomicAdd(&s_hist[(rl[h] << log2cap) + l], 1u);
-          }
-        }
-    }
-    if (next >= 0) { set_tile(next); gload(0, 8); }
+    // One accumulator row at a time in the count (the fp32 kernel runs two): one row's NJ search chains keep this kernel inside
+    // the 256 registers of two workgroups per CU, and the second workgroup fills the gaps of the chains.
+    stream_tile_consume<EPI, 1, NJ>(acc, wm, wn, l31, kh, row0, col0, 0, L, P);
+    if constexpr (EPI == EPI_COUNT) { if (next >= 0) { set_tile(next); gload(0, 8); } }
   };
 
   while (g0 < g1) {                               // the run's segments: one per row it touches
@@ -375,29 +268,7 @@ __global__ __launch_bounds__(256, 2) void sqdist_stream_h16_kernel(
     g0 += u1 - u0;
     row0 = row * SQ_TM;
     __syncthreads();                               // the previous segment's histogram has been flushed
-    int ts = tid;                                  // opaque: the set-up's LDS addresses are recomputed per segment instead of
-    asm volatile("" : "+v"(ts));                   // occupying registers across the k-loops
-    if constexpr (EPI == EPI_TOPK) {
-      if (ts < SQ_TM) {
-        const int rr = row0 + ts;
-        s_qq[ts] = rr < m ? qq[rr] : 0.f;
-        s_kmax[ts] = rr < m ? mono_key(tau[rr]) : 0u;
-      }
-    } else {
-      for (int i = ts; i < SQ_TM * cap; i += 256) {
-        const int r = i >> log2cap, rr = row0 + r;
-        s_keys[i] = rr < m ? pos_key[(int64_t)rr * cap + (i & (cap - 1))] : 0xffffffffu;
-        s_hist[i] = 0u;
-      }
-      if (ts < SQ_TM) {
-        const int rr = row0 + ts;
-        const int np = rr < m ? npos[rr] : 0;
-        s_np[ts] = np > 0 ? np : 0;
-        s_qq[ts] = rr < m ? qq[rr] : 0.f;
-        s_qpid[ts] = rr < m ? (long long)q_pids[rr] : 0;
-        s_kmax[ts] = np > 0 ? pos_key[(int64_t)rr * cap + np - 1] : 0u;
-      }
-    }
+    stream_segment_begin<EPI>(L, P, row0);
     const int r0c = min(row0, m - 1);
     abase = reinterpret_cast<const char*>(q + (int64_t)r0c * D);
 #pragma unroll
@@ -408,20 +279,10 @@ __global__ __launch_bounds__(256, 2) void sqdist_stream_h16_kernel(
     gload(0, 8);
     while (col < cend) {
       const int nj = min(4, (cend - col) >> 6), next = col + 256 < cend ? col + 256 : -1;
-      if (nj == 4) tile(std::integral_constant<int, 4>{}, col, next);
-      else if (nj == 3) tile(std::integral_constant<int, 3>{}, col, next);
-      else if (nj == 2) tile(std::integral_constant<int, 2>{}, col, next);
-      else tile(std::integral_constant<int, 1>{}, col, next);
+      STREAM_DISPATCH_NJ(nj, tile, col, next);
       col += 256;
     }
-    if constexpr (EPI == EPI_COUNT) {
-      __syncthreads();
-      for (int i = ts; i < SQ_TM * cap; i += 256) {
-        const unsigned v = s_hist[i];
-        const int rr = row0 + (i >> log2cap);
-        if (v && rr < m) atomicAdd(&hist_out[(int64_t)rr * cap + (i & (cap - 1))], v);      // integer: order-independent
-      }
-    }
+    if constexpr (EPI == EPI_COUNT) stream_segment_end(L, P, row0);
   }
 }
 
@@ -438,8 +299,8 @@ int creid_stream_poslist_h16(const void* q, const void* g, const float* qq, cons
   CREID_CHECK_ARG(m >= 0 && n > 0 && D > 0);
   if (m == 0) return 0;
   CREID_CHECK_ARG(q && g && qq && gg && q_slot && csr_off && g_order && q_cams && g_cams && pos_key && pos_idx && npos);
-  if (cap < 2 || cap > PL_MAXC || (cap & (cap - 1)) != 0 || D % 8 != 0 || D > H_MAX_D) return CREID_E_SHAPE;
-  if (n > 0x7ffffff0LL || m > 0x7ffffff0LL) return CREID_E_SHAPE;
+  if (!stream_count_cap_ok(cap) || D % 8 != 0 || D > H_MAX_D) return CREID_E_SHAPE;
+  if (!stream_mn_ok(m, n)) return CREID_E_SHAPE;
   if (!creid_is16(dtype)) return CREID_E_DTYPE;
   const unsigned short* qh = static_cast<const unsigned short*>(q);
   const unsigned short* gh = static_cast<const unsigned short*>(g);
@@ -458,37 +319,27 @@ int creid_stream_count_h16(const void* q, const void* g, const float* qq, const 
   CREID_CHECK_ARG(m >= 0 && n > 0 && D > 0);
   if (m == 0) return 0;
   CREID_CHECK_ARG(q && g && qq && gg && q_pids && g_pids && pos_key && pos_idx && npos && hist);
-  if (cap < 2 || cap > PL_MAXC || (cap & (cap - 1)) != 0 || D % 8 != 0 || D > H_MAX_D) return CREID_E_SHAPE;
-  if (n > 0x7ffffff0LL || m > 0x7ffffff0LL) return CREID_E_SHAPE;
+  if (!stream_count_cap_ok(cap) || D % 8 != 0 || D > H_MAX_D) return CREID_E_SHAPE;
+  if (!stream_mn_ok(m, n)) return CREID_E_SHAPE;
   if (!creid_is16(dtype)) return CREID_E_DTYPE;
-  int log2cap = 0;
-  while ((1 << log2cap) < cap) ++log2cap;
+  const int log2cap = stream_log2cap(cap);
   const StreamSplit sp = stream_split(m, n, D, 2);
-  const size_t dyn = (size_t)2 * SQ_TM * cap * sizeof(unsigned);
   const unsigned short* qh = static_cast<const unsigned short*>(q);
   const unsigned short* gh = static_cast<const unsigned short*>(g);
 #define CREID_COUNT_H16_LAUNCH(DT)                                                                                          \
-  do {                                                                                                                       \
-    static const hipError_t attr_rc =                                                                                        \
-        hipFuncSetAttribute(reinterpret_cast<const void*>(sqdist_stream_h16_kernel<DT, EPI_COUNT>),                          \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 2 * SQ_TM * PL_MAXC * (int)sizeof(unsigned));         \
-    if (attr_rc != hipSuccess) return (int)attr_rc;                                                                          \
-    hipLaunchKernelGGL((sqdist_stream_h16_kernel<DT, EPI_COUNT>), dim3(sp.grid), dim3(256), dyn, as_stream(stream), qh, gh,  \
-                       qq, gg, (int)m, (int)n, (int)D, q_pids, g_pids, (int)cap, log2cap, pos_key, pos_idx, npos, hist,        \
-                       sp.tiles_m, sp.U, sp.upw, sp.mode, (const float*)nullptr, (unsigned long long*)nullptr,               \
-                       (int32_t*)nullptr);                                                                                   \
-  } while (0)
+  return stream_count_launch<sqdist_stream_h16_kernel<DT, EPI_COUNT>>(                                                       \
+      sp, (int)cap, stream, qh, gh, qq, gg, (int)m, (int)n, (int)D, q_pids, g_pids, (int)cap, log2cap, pos_key, pos_idx, npos, hist, \
+      sp.tiles_m, sp.U, sp.upw, sp.mode, (const float*)nullptr, (unsigned long long*)nullptr, (int32_t*)nullptr)
   if (dtype == CREID_BF16) CREID_COUNT_H16_LAUNCH(CREID_BF16); else CREID_COUNT_H16_LAUNCH(CREID_F16);
 #undef CREID_COUNT_H16_LAUNCH
-  CREID_LAUNCH_RET();
 }
 
 int creid_stream_topk_collect_h16(const void* q, const void* g, const float* qq, const float* gg, int64_t m, int64_t n,
                                   int64_t D, int dtype, const float* tau, int32_t cap, uint64_t* cand, int32_t* count,
                                   void* stream) {
   CREID_CHECK_ARG(m >= 0 && n > 0 && D > 0);
-  if (cap < TS_MIN_CAP || cap > TS_MAX_CAP || (cap & (cap - 1)) != 0 || D % 8 != 0 || D > H_MAX_D) return CREID_E_SHAPE;
-  if (n > 0x7ffffff0LL || m > 0x7ffffff0LL) return CREID_E_SHAPE;
+  if (!stream_topk_cap_ok(cap) || D % 8 != 0 || D > H_MAX_D) return CREID_E_SHAPE;
+  if (!stream_mn_ok(m, n)) return CREID_E_SHAPE;
   if (!creid_is16(dtype)) return CREID_E_DTYPE;
   if (m == 0) return 0;
   CREID_CHECK_ARG(q && g && qq && gg && tau && cand && count);

@@ -32,11 +32,11 @@ def test_hot_kernels_keep_their_occupancy_budget():
     rows = _table()
     if not rows:
         pytest.skip("no resource tables (library not built here)")
-    seen = 0
+    seen = two_per_cu = 0
     for name, kv in rows.items():
         base, args = _demangled(name)
         if base in ("igemm_bf16_ws_kernel", "igemm_bf16_dma_kernel", "wgrad_bf16_dma_kernel", "sqdist_f32_kernel",
-                    "sqdist_count_f32_kernel", "igemm1x1_stream_kernel"):
+                    "sqdist_count_f32_kernel", "sqdist_stream_h16_kernel", "igemm1x1_stream_kernel"):
             assert int(kv.get("scratch", 0)) == 0, (name, kv)
             assert int(kv.get("vgpr_spill", 0)) == 0, (name, kv)
             seen += 1
@@ -47,7 +47,14 @@ def test_hot_kernels_keep_their_occupancy_budget():
             if args[:2] == [64, 2] and (len(args) < 3 or args[2] == 128):
                 limit = 80                                   # the 128 x 64 two-stage tile runs THREE workgroups per CU (6 waves / SIMD)
             assert int(kv["vgprs"]) + int(kv.get("agprs", 0)) <= limit, (name, kv)
-    assert seen >= 6
+        if base == "sqdist_stream_h16_kernel" or (base == "sqdist_count_f32_kernel" and "Lb1E" in name.split("Ev")[0]):
+            # __launch_bounds__(256, 2): every 16-bit streamed kernel and the FULLK (second template argument true) fp32 ones
+            # run two workgroups per CU = 2 waves per SIMD, so 256 registers per lane and not one more.
+            assert int(kv["vgprs"]) + int(kv.get("agprs", 0)) <= 256, (name, kv)
+            assert int(kv["occupancy"]) >= 2, (name, kv)
+            two_per_cu += 1
+    assert seen >= 10
+    assert two_per_cu >= 6                                       # 2 dtypes x 2 epilogues, and the FULLK fp32 count and top-k
 
 
 def test_no_shipped_kernel_spills():
