@@ -7,7 +7,8 @@
 //       Three kernels share that tiling:
 //         igemm_bf16_ws_kernel   512 threads, producer waves issue the global->LDS DMA gather (the A rows come from
 //                                different image rows / taps) into an NS-stage ring, consumer waves multiply -- the
-//                                default for every 1x1 / 3x3 layer;
+//                                default for every 1x1 / 3x3 layer (igemm_bf16_halo_kernel: the same kernel with the A operand
+//                                resident in LDS, for the stride-1 3x3 layers whose tile is whole image rows);
 //         igemm_bf16_dma_kernel  256 threads, every wave issues its DMA pieces and multiplies -- the stem (32-element
 //                                taps, two per k-tile), CREID_IGEMM_WS=0 and the plans that name it;
 //         igemm_bf16_kernel      register-staged gather -- the fallback under CREID_IGEMM_DMA=0 / CREID_STEM_DMA=0.
@@ -18,6 +19,7 @@
 // accumulators for the training-mode BatchNorm that follows every convolution.
 #include "conv_epilogue.hpp"
 #include <type_traits>
+#include <atomic>
 #include "wgrad_reduce.hpp"
 #include "tune.hpp"
 #include <stdlib.h>
@@ -798,6 +800,205 @@ __global__ __launch_bounds__(512, (BN == 64 && NS == 2 && BM == 128) ? 6 : ((NS 
   igemm_tile_epilogue<ET, BM, BN, NT>(g, smem, acc, out, add_src, bn_part, bnred, tile_m, row0, col0, pixel_of);
 }
 
+// ------------------------------------------------------------------------------------ bf16, resident halo tile
+// The stride-1 3 x 3 convolutions (forward and data gradient) whose 128-row tile is whole image rows of one image: the nine
+// taps of such a tile read the same (128 / OW + 2) x (OW + 2) source pixels shifted by one, and the producer/consumer kernel
+// above sends them through the global->LDS DMA nine times (the LDS fill, not the MFMA, sets its k-tile time).  Here the
+// producer waves DMA that halo image ONCE, in the prologue, and only the weight tiles stream through the NS-deep ring.
+//   halo image : C / 64 planes of [slot][64 channels] (the 128-byte row format of an A stage); slot = hr * (OW + 2) + hc holds
+//                source pixel (y0 - 1 + hr, hc - 1) of the tile's image, y0 = the tile's first image row; slots outside the
+//                image (and the padding up to whole DMA pieces) are filled from the zero page.  The 16-byte chunk index is
+//                XOR-swizzled by key(hr, hc) = ((hc >> 1) + (OW == 8 ? 4 * hr : 0)) & 7: the 16 lanes of a ds_read_b128
+//                group then hit 16 different (slot parity, chunk) bank groups under every tap shift (OW >= 32: one halo row
+//                per 32 lanes; OW = 16: two rows, equal columns 16 apart; OW = 8: four rows, + 4 per row separates them).
+//   fill       : a DMA instruction writes 8 consecutive slots of one plane; every producer wave issues HALO_PW pieces per
+//                plane (so the vmcnt bookkeeping is the same in all four).  Order: plane 0, weight tiles 0 .. NS-2, planes
+//                1 .. P-1 -- k-tile t < P needs plane t only, so the first multiplies start after about the bytes of
+//                today's first k-tile and the other planes land behind them.
+//   k-loop     : tap-major, 64-wide k-tiles inside a tap (plane kc), 16-wide slices, one accumulation chain per sub-tile --
+//                the order of the tile kernels, so every output bit is theirs.  Row r of the tile under tap (tr, ts) reads
+//                slot (r / OW + dr) * (OW + 2) + r % OW + dc, (dr, dc) = (tr, ts) forward, (2 - tr, 2 - ts) transposed.
+// Consumer sub-tiles, C staging and the epilogue (igemm_tile_epilogue), and the piggy-backed split reduction are those of
+// igemm_bf16_ws_kernel<BN, NS, 128>.
+constexpr int halo_pw(int C) { return C == 64 ? 9 : 6; }                 // DMA pieces per producer wave per plane (36 / 24 KB planes)
+constexpr int halo_lds_bytes(int C, int BN, int NS) { return ((C / 64) * 4 * halo_pw(C) * 512 + NS * BN * 64) * 2; }
+
+template <int C, int BN, int NS, typename ET = Bf16T>
+__global__ __launch_bounds__(512, halo_lds_bytes(C, BN, NS) <= 80 * 1024 ? 2 : 1) void igemm_bf16_halo_kernel(IGemmGeom g, const unsigned short* __restrict__ src,
+                                                                const unsigned short* __restrict__ wgt,
+                                                                unsigned short* __restrict__ out,
+                                                                const unsigned short* __restrict__ add_src,
+                                                                float* __restrict__ bn_part, int tiles_n,
+                                                                BnRedArgs bnred, WRedJob wred) {
+  constexpr int NT = 512, BM = 128;
+  constexpr int BK = 64, TNW = BN / 64, NBI = BN / 32, MI = 2;
+  constexpr int P = C / 64, PW = halo_pw(C);                    // planes; halo pieces per producer wave per plane
+  constexpr int PLANE = 4 * PW * 512, HALO = P * PLANE;          // elements
+  constexpr int CPT = BM + 4;
+  constexpr int TILE_B = BN * BK;
+  constexpr int CPR = BN / 8, NRG = NT / CPR;
+  constexpr int RED_ELEMS = NRG * 2 * BN * 2;
+  constexpr int LDS0 = (HALO + NS * TILE_B) > (BN * CPT) ? (HALO + NS * TILE_B) : (BN * CPT);
+  constexpr int LDS_ELEMS = LDS0 > RED_ELEMS ? LDS0 : RED_ELEMS;
+  static_assert(C == 64 || C == 128 || C == 256, "channels per tap");
+  static_assert(NS >= 2 && NS <= 4, "ring depth");
+  static_assert(LDS_ELEMS * 2 < 160 * 1024, "halo image + weight ring must fit the LDS");
+  static_assert(sizeof(float) * (4 * 512 + 8192) <= LDS_ELEMS * 2, "reduce scratch of the piggy-backed job");
+  static_assert((NS - 2) * NBI + (P - 1) * PW <= 63, "vmcnt is a 6-bit counter");
+  __shared__ __attribute__((aligned(1024))) unsigned short smem[LDS_ELEMS];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int nred = wred.ws ? wred.nblocks : 0;                   // (as in igemm_bf16_ws_kernel: the LAST workgroups reduce)
+  const int ntile_wgs = (int)gridDim.x - nred;
+  if ((int)blockIdx.x >= ntile_wgs) {
+    wgrad_reduce_block<NT>(wred, (int)blockIdx.x - ntile_wgs, reinterpret_cast<float*>(smem));
+    return;
+  }
+  const bool producer = wave >= 4;
+  const int cw = wave & 3;
+  const int wm = cw >> 1, wn = cw & 1;
+  const int bid = xcd_remap((int)blockIdx.x, ntile_wgs);
+  const int tile_m = bid / tiles_n, tile_n = bid % tiles_n;
+  const int row0 = tile_m * BM, col0 = tile_n * BN;
+  const int l31 = lane & 31, kh = lane >> 5;
+  const int hp = g.OW + 2;                                       // halo row pitch (slots)
+  const int kmul = g.OW == 8 ? 4 : 0;                            // swizzle key: + 4 per halo row where a lane group spans four rows
+  constexpr int nk = 9 * P;
+
+  f32x16 acc[MI][TNW];
+  if (producer) {
+    const int lr8 = lane >> 3, lcp = lane & 7;
+    const int ohow = g.OH * g.OW;
+    const int img = row0 / ohow, y0 = (row0 - img * ohow) / g.OW;   // the tile: rows y0 .. y0 + 128 / OW - 1 of image img
+    const int nslot = (BM / g.OW + 2) * hp;
+    const float inv_hp = 1.0f / (float)hp;
+    const unsigned short* zpage = reinterpret_cast<const unsigned short*>(g_zero_page);
+    typedef const void __attribute__((address_space(1)))* gptr_t;
+    typedef void __attribute__((address_space(3)))* lptr_t;
+    const unsigned short* hptr[PW];
+    int hstep[PW];
+#pragma unroll
+    for (int j = 0; j < PW; ++j) {                               // plane 0; piece j of this wave = slots (j * 4 + cw) * 8 .. + 7
+      const int slot = (j * 4 + cw) * 8 + lr8;
+      int hr, hc;
+      fast_divmod(slot, hp, inv_hp, hr, hc);
+      const int iy = y0 - 1 + hr, ix = hc - 1;
+      const bool ok = slot < nslot && (unsigned)iy < (unsigned)g.SH && (unsigned)ix < (unsigned)g.SW;
+      const int key = ((hc >> 1) + kmul * hr) & 7;
+      hptr[j] = ok ? src + (int64_t)((img * g.SH + iy) * g.SW + ix) * g.pitch + ((lcp ^ key) << 3) : zpage;
+      hstep[j] = ok ? BK : 0;
+      __builtin_amdgcn_global_load_lds((gptr_t)hptr[j], (lptr_t)(smem + (j * 4 + cw) * 512), 16, 0, 0);
+    }
+    const unsigned short* wp[NBI];
+#pragma unroll
+    for (int i = 0; i < NBI; ++i) {
+      const int r = (i * 4 + cw) * 8 + lr8;
+      wp[i] = wgt + (int64_t)(col0 + r) * g.K + ((lcp ^ ((r >> 1) & 7)) << 3);
+    }
+    auto issue = [&](int buf) {                                  // the next weight tile (running pointers)
+      unsigned short* lb = smem + HALO + buf * TILE_B + cw * 512;
+#pragma unroll
+      for (int i = 0; i < NBI; ++i) {
+        __builtin_amdgcn_global_load_lds((gptr_t)wp[i], (lptr_t)(lb + i * 2048), 16, 0, 0);
+        wp[i] += BK;
+      }
+    };
+#pragma unroll
+    for (int p = 0; p < NS - 1; ++p) issue(p);
+#pragma unroll
+    for (int p = 1; p < P; ++p)
+#pragma unroll
+      for (int j = 0; j < PW; ++j) {
+        hptr[j] += hstep[j];
+        __builtin_amdgcn_global_load_lds((gptr_t)hptr[j], (lptr_t)(smem + p * PLANE + (j * 4 + cw) * 512), 16, 0, 0);
+      }
+    // instructions still allowed in flight at B_t while planes are landing (t < P): behind plane t (and weight tile t, issued
+    // before plane 1 when t <= NS - 2) come the planes t + 1 .. P - 1 and the t weight tiles issued inside the loop so far
+    constexpr int W0 = (NS - 2) * NBI + (P - 1) * PW;
+    constexpr int W1 = (P > 2 ? (P - 2) * PW : 0) + NBI;
+    constexpr int W2 = (P > 3 ? (P - 3) * PW : 0) + 2 * NBI;
+    int buf = 0;
+    for (int t = 0; t < nk; ++t) {
+      if (P > 1 && t == 0) wait_vm<W0>();
+      else if (P > 1 && t == 1 && NS >= 3) wait_vm<W1>();
+      else if (P > 2 && t == 2 && NS >= 4) wait_vm<W2>();
+      else {
+        const int younger = min(nk - 1 - t, NS - 2);
+        if constexpr (NS >= 4) { if (younger == 2) wait_vm<2 * NBI>(); }
+        if constexpr (NS >= 3) { if (younger == 1) wait_vm<1 * NBI>(); }
+        if (younger == 0) wait_vm<0>();
+      }
+      asm volatile("s_barrier" ::: "memory");                    // B_t
+      if (t + NS - 1 < nk) issue(buf == 0 ? NS - 1 : buf - 1);
+      buf = (buf + 1 == NS) ? 0 : buf + 1;
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+      for (int j = 0; j < TNW; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    const int log2ow = 31 - __clz(g.OW);
+    int hr0[MI], hc0[MI];
+#pragma unroll
+    for (int i = 0; i < MI; ++i) {
+      const int r = wm * (BM / 2) + i * 32 + l31;
+      hr0[i] = r >> log2ow; hc0[i] = r & (g.OW - 1);
+    }
+    int buf = 0, tr = 0, ts = 0;
+    for (int tap = 0; tap < 9; ++tap) {
+      const int dr = g.transposed ? 2 - tr : tr, dc = g.transposed ? 2 - ts : ts;
+      int aoff[MI], kx[MI];                                      // this tap's slot (elements) and swizzle key ^ k half, per row block
+#pragma unroll
+      for (int i = 0; i < MI; ++i) {
+        const int hr = hr0[i] + dr, hc = hc0[i] + dc;
+        aoff[i] = (hr * hp + hc) * BK;
+        kx[i] = (((hc >> 1) + kmul * hr) & 7) ^ kh;
+      }
+      if (++ts == 3) { ts = 0; ++tr; }
+#pragma unroll
+      for (int kc = 0; kc < P; ++kc) {
+        asm volatile("s_barrier" ::: "memory");                  // B_t, t = tap * P + kc: weight tile t (and plane kc) is in LDS
+        const unsigned short* As = smem + kc * PLANE;
+        const unsigned short* Bs = smem + HALO + buf * TILE_B;
+        buf = (buf + 1 == NS) ? 0 : buf + 1;
+        s16x8 a[2][MI], b[2][TNW];
+        auto load_frags = [&](int kk, int sl) {
+          const int ch = 2 * kk + kh;
+#pragma unroll
+          for (int i = 0; i < MI; ++i)
+            a[sl][i] = *reinterpret_cast<const s16x8*>(&As[aoff[i] + (((2 * kk) ^ kx[i]) << 3)]);
+#pragma unroll
+          for (int j = 0; j < TNW; ++j) {
+            const int c = wn * (BN / 2) + j * 32 + l31;
+            b[sl][j] = *reinterpret_cast<const s16x8*>(&Bs[c * BK + ((ch ^ ((c >> 1) & 7)) << 3)]);
+          }
+        };
+        auto mma = [&](int sl) {
+          if (CREID_ABL_ON(g.abl, 1)) return;
+#pragma unroll
+          for (int i = 0; i < MI; ++i)
+#pragma unroll
+            for (int j = 0; j < TNW; ++j)
+              acc[i][j] = ET::mfma(a[sl][i], b[sl][j], acc[i][j]);
+        };
+        load_frags(0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        load_frags(1, 1); mma(0);
+        __builtin_amdgcn_sched_barrier(0);
+        load_frags(2, 0); mma(1);
+        __builtin_amdgcn_sched_barrier(0);
+        load_frags(3, 1); mma(0);
+        __builtin_amdgcn_sched_barrier(0);
+        mma(1);
+      }
+    }
+  }
+  __syncthreads();
+
+  igemm_tile_epilogue<ET, BM, BN, NT>(g, smem, acc, out, add_src, bn_part, bnred, tile_m, row0, col0, [](int rr) { return rr; });
+}
+
 // ------------------------------------------------------------------------------------ f32
 template <int BN>
 __global__ __launch_bounds__(256) void igemm_f32_kernel(IGemmGeom g, const float* __restrict__ src,
@@ -979,6 +1180,22 @@ static int ws_stages_env() {
   return v;
 }
 
+// What igemm_bf16_halo_kernel covers: 3x3, stride 1, pad 1 (forward or transposed) over C = 64 | 128 | 256 channels per tap,
+// 128-row tiles that are whole rows of one image (OW = 8 .. 64 divides 128, OH * OW a multiple of 128), and a halo image
+// ((128 / OW + 2) x (OW + 2) slots) plus weight ring that fit the planes and the LDS the instantiation has.
+static bool igemm_halo_covers(const IGemmGeom& g, int bn, int stages) {
+  const int c = 1 << g.log2span;
+  if (g.kw != 3 || g.K != 9 * c || g.stride != 1 || g.pad != 1 || !g.check_bounds || g.parity || g.pitch != c) return false;
+  if (c != 64 && c != 128 && c != 256) return false;
+  if (g.SH != g.OH || g.SW != g.OW) return false;
+  if (g.OW != 8 && g.OW != 16 && g.OW != 32 && g.OW != 64) return false;
+  if ((g.OH * g.OW) % 128 != 0 || g.M % (g.OH * g.OW) != 0) return false;
+  if ((128 / g.OW + 2) * (g.OW + 2) > 32 * halo_pw(c)) return false;
+  if (stages < 2 || stages > 4 || (bn != 64 && bn != 128)) return false;
+  return halo_lds_bytes(c, bn, stages) < 160 * 1024;
+}
+static std::atomic<long long> g_halo_launches{0};
+
 static int launch_igemm(const IGemmGeom& g_in, const void* src, const void* wgt, void* out, const void* add_src,
                         float* bn_part, int dtype, hipStream_t s, BnRedArgs bnred = BnRedArgs{},
                         const WRedJob* wred_in = nullptr) {
@@ -1119,6 +1336,32 @@ static int launch_igemm(const IGemmGeom& g_in, const void* src, const void* wgt,
       // 4 x 32 KB at BN = 128 is one workgroup per CU (the C staging reuses the ring): only on request of a measured plan
       if (ws_stages == 4 && bn == 128 && !(tuned_stages == 4 && use_ws != 2)) ws_stages = 3;
       const dim3 grid_ws((unsigned)(tiles_m * tiles_n + (wred.ws ? wred.nblocks : 0)));
+      // stride-1 3x3 on whole-image-row tiles: the same tile, ring depth and epilogue with the A operand resident in LDS
+      // (igemm_bf16_halo_kernel; identical bits).  CREID_IGEMM_HALO=0: the launches below
+      {
+        const char* he = CREID_KNOB_ENV("CREID_IGEMM_HALO");               // read per call: tests toggle it
+        if ((!he || atoi(he) != 0) && igemm_halo_covers(gp, bn, ws_stages)) {
+          const int hc = 1 << gp.log2span;
+#define CREID_HALO_LAUNCH1(C_, BN_, NS_, ET_)                                                                             \
+  hipLaunchKernelGGL((igemm_bf16_halo_kernel<C_, BN_, NS_, ET_>), grid_ws, block_ws, 0, s, gp, (const unsigned short*)src, \
+                     (const unsigned short*)wgt, (unsigned short*)out, (const unsigned short*)add_src, bn_part, tiles_n,  \
+                     bnred, wred)
+#define CREID_HALO_LAUNCH(C_, BN_, NS_) do { if (dtype == CREID_F16) CREID_HALO_LAUNCH1(C_, BN_, NS_, F16T); else CREID_HALO_LAUNCH1(C_, BN_, NS_, Bf16T); } while (0)
+          // (a 4-deep ring that does not fit beside the halo image is refused by igemm_halo_covers: that name is never launched)
+#define CREID_HALO_STAGES(C_, BN_) do { constexpr int NS4 = halo_lds_bytes(C_, BN_, 4) < 160 * 1024 ? 4 : 3;            \
+                                        if (ws_stages == 4) CREID_HALO_LAUNCH(C_, BN_, NS4);                            \
+                                        else if (ws_stages == 2) CREID_HALO_LAUNCH(C_, BN_, 2); else CREID_HALO_LAUNCH(C_, BN_, 3); } while (0)
+#define CREID_HALO_BN(C_) do { if (bn == 128) CREID_HALO_STAGES(C_, 128); else CREID_HALO_STAGES(C_, 64); } while (0)
+          if (hc == 64) CREID_HALO_BN(64); else if (hc == 128) CREID_HALO_BN(128); else CREID_HALO_BN(256);
+#undef CREID_HALO_BN
+#undef CREID_HALO_STAGES
+#undef CREID_HALO_LAUNCH
+#undef CREID_HALO_LAUNCH1
+          g_halo_launches.fetch_add(1, std::memory_order_relaxed);
+          ran(0);
+          return (int)hipGetLastError();
+        }
+      }
 #define CREID_WS_LAUNCH1(BN_, NS_, ET_)                                                                               \
   hipLaunchKernelGGL((igemm_bf16_ws_kernel<BN_, NS_, 128, ET_>), grid_ws, block_ws, 0, s, gp, (const unsigned short*)src, \
                      (const unsigned short*)wgt, (unsigned short*)out, (const unsigned short*)add_src, bn_part, tiles_n, \
@@ -1194,6 +1437,8 @@ static int check_desc(const creid_conv_desc* d) {
 int conv_check_desc(const creid_conv_desc* d) { return check_desc(d); }
 
 extern "C" {
+
+int64_t creid_igemm_halo_launches(void) { return (int64_t)g_halo_launches.load(std::memory_order_relaxed); }
 
 int64_t creid_conv2d_bn_partial_rows(const creid_conv_desc* d) {
   if (!d) return 0;

@@ -475,6 +475,9 @@ typedef struct {
  * bn_partial (nullable) receives per-128-row-tile (sum, sumsq) of the fp32 accumulators,
  * float [creid_conv2d_bn_partial_rows(d)][2][out_c], for the BatchNorm that follows. */
 int64_t creid_conv2d_bn_partial_rows(const creid_conv_desc* d);
+/* Launches so far (this process) of the resident-halo form of the producer/consumer kernel: stride-1 3x3 forward / data
+ * gradient, 64 | 128 | 256 channels, 128-row tiles of whole image rows; CREID_IGEMM_HALO=0 turns it off.  Same bits either way. */
+int64_t creid_igemm_halo_launches(void);
 int creid_conv2d_fwd_nhwc(const creid_conv_desc* d, const void* x, const void* w_krsc, void* y,
                           float* bn_partial, int dtype, void* stream);
 /* Eval-mode forward of conv -> BatchNorm -> (+ residual) -> (ReLU) in ONE launch (modelling/backbones/resnet.py:67-87 under
