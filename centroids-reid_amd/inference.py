@@ -17,22 +17,27 @@ import torch
 
 from . import _lib as L
 from . import reid_metric as rm
+from .transforms import RaggedImages
 
 
 def _inference(model, batch, use_cuda=True, normalize_with_bn=True, transform=None):
     """inference_utils.py:104-113: eval-mode backbone (+ BNNeck).  `data` is the reference's fp32 NCHW batch, or -- with
     `transform` = ReidTransforms(cfg).build_transforms(is_train=False) -- a uint8 [B, H, W, 3] batch of resized images: the test
-    transform (build.py:27-31 after the Resize) then runs on the device and writes the stem convolution's operand directly."""
+    transform (build.py:27-31 after the Resize) then runs on the device and writes the stem convolution's operand directly.
+    Images that are NOT resized come as a transforms.RaggedImages or as a plain list of uint8 [h, w, 3] arrays of any sizes
+    (packed here): the Resize then runs on the device as well, with Pillow's result byte for byte."""
     model.eval()
     with torch.no_grad():
         data, _, filename = batch
-        if data.dtype == torch.uint8:
+        data = _as_batch_data(data)
+        if isinstance(data, RaggedImages) or data.dtype == torch.uint8:
             if transform is None:
                 raise ValueError("uint8 image batches need `transform` (transforms.ReidTransforms(cfg).build_transforms(False))")
             if callable(transform) and getattr(transform, "_lazy_cfg", None) is not None:
                 transform = transform()                          # built on the first uint8 batch only (run_inference)
             # the device-side transform IS a GPU kernel: a uint8 batch goes to the device whatever `use_cuda` says (the flag only
             # keeps the reference's meaning for float batches, which a CPU-resident model could not run here anyway)
+            # (a RaggedImages is resized to the transform's size first, on the device too: transforms.DeviceTransform.resize_batch)
             data = transform(data.cuda(), layout="stem", dtype=model.backbone.engine_for(False).dtype)   # (bf16x3: fp32)
         else:
             data = data.cuda() if use_cuda else data
@@ -42,10 +47,25 @@ def _inference(model, batch, use_cuda=True, normalize_with_bn=True, transform=No
         return global_feat, filename
 
 
+def _as_batch_data(data):
+    """A loader batch's `data` as run_inference handles it: a tensor, or a RaggedImages (a list of images is packed)."""
+    if isinstance(data, (list, tuple)):
+        return RaggedImages.pack(data)
+    return data
+
+
+def _can_join(a, b) -> bool:
+    """Whether two batches' `data` can be concatenated into one forward."""
+    if isinstance(a, RaggedImages) or isinstance(b, RaggedImages):
+        return isinstance(a, RaggedImages) and isinstance(b, RaggedImages) and a.device == b.device
+    return a.dtype == b.dtype and a.shape[1:] == b.shape[1:] and a.device == b.device
+
+
 def run_inference(model, val_loader, cfg=None, print_freq=0, use_cuda=True, transform=None, macro_batch=512):
     """inference_utils.py:116-131 -> (embeddings float32 [N, D] ndarray, paths ndarray); the embeddings are
     also kept on the device in `run_inference.last_device_embeddings` for a following get_similar().  A loader of uint8
-    [B, H, W, 3] batches is normalised on the device (`transform`, or the test transform built from `cfg`).
+    [B, H, W, 3] batches is normalised on the device (`transform`, or the test transform built from `cfg`); a loader of
+    RaggedImages, or of plain lists of uint8 [h, w, 3] arrays of any sizes, is resized there first (transforms.py).
 
     macro_batch (round 5): consecutive loader batches are concatenated until at least this many images are waiting and embedded
     with ONE forward -- the eval-mode forward treats every image independently (BatchNorm folded to running statistics, eval-mode
@@ -71,18 +91,23 @@ def run_inference(model, val_loader, cfg=None, print_freq=0, use_cuda=True, tran
         nonlocal pend, npend
         if not pend:
             return
-        data = pend[0][0] if len(pend) == 1 else torch.cat([b[0] for b in pend])
+        if len(pend) == 1:
+            data = pend[0][0]
+        elif isinstance(pend[0][0], RaggedImages):
+            data = RaggedImages.cat([b[0] for b in pend])
+        else:
+            data = torch.cat([b[0] for b in pend])
         names = [n for b in pend for n in list(b[2])]
         e, p = _inference(model, (data, None, names), use_cuda, transform=transform)
         embs.append(e.float())
         paths.extend(list(p))
         pend, npend = [], 0
     for batch in val_loader:
-        data = batch[0]
-        if pend and (data.dtype != pend[0][0].dtype or data.shape[1:] != pend[0][0].shape[1:] or data.device != pend[0][0].device):
+        data = _as_batch_data(batch[0])
+        if pend and not _can_join(pend[0][0], data):
             flush()                                              # batches that cannot be concatenated go separately
-        pend.append(batch)
-        npend += data.shape[0]
+        pend.append((data, *batch[1:]))
+        npend += len(data)
         if not macro_batch or npend >= macro_batch:
             flush()
     flush()

@@ -636,6 +636,28 @@ int creid_image_to_nhwc4_pad(const float* x_nchw, int64_t B, int64_t H, int64_t 
 int creid_augment_u8(const uint8_t* src_hwc, const int32_t* params, int64_t B, int64_t H, int64_t W, int64_t pad,
                      float mean0, float mean1, float mean2, float std0, float std1, float std2, float erase0, float erase1,
                      float erase2, int32_t layout, int32_t dtype, void* out, void* stream);
+/* The Resize in front of those transforms (datasets/transforms/build.py:17,28: T.Resize((H, W)) on a PIL RGB image =
+ * Image.resize((W, H), BILINEAR)) on a ragged uint8 batch, EQUAL to Pillow's result byte for byte.
+ *   src: `src_bytes` bytes, the images packed back to back as HWC RGB; offsets: int64 [B], byte offset of each image (any
+ *   alignment); sizes: int32 [B, 2] = (h, w), sides 1..16384; out: uint8 [B, H, W, 3], H and W 1..4096 -- the tensor
+ *   creid_augment_u8 takes.  tables: `table_len` int32 holding one coefficient table per distinct (source side -> target side)
+ *   pair of the batch; table_offsets: int32 [B, 2] = where the image's (w -> W) and (h -> H) tables start.
+ * Arithmetic (Pillow's 8-bit resample; per axis with `in` source and `out` target samples, in float64 on the host):
+ *   scale = in / out; fs = max(scale, 1); ksize = 2 ceil(fs) + 1; for output sample xx: center = (xx + 0.5) scale,
+ *   xmin = max((int)(center - fs + 0.5), 0), xmax = min((int)(center + fs + 0.5), in), n = xmax - xmin; tap x < n weighs
+ *   w = max(0, 1 - |(x + xmin - center + 0.5) (1 / fs)|), divided by the sum of the w in tap order; k = (int)(w 2^22 + 0.5).
+ *   A table is {xmin, n} for each of the `out` samples, then ksize coefficients for each (k[0..n), zero beyond); in == out is
+ *   the identity table (xmin = xx, n = 1, k = 2^22, ksize 3).
+ *   On the device, integers only: the horizontal pass first, sample = clip8((2^21 + sum_x k[x] pixel[xmin + x]) >> 22) per
+ *   channel in int32, ROUNDED TO uint8, then the vertical pass over those values in the same way.  The intermediate image is
+ *   never written to memory.
+ * Only the pointers and B, H, W, src_bytes, table_len can be checked on the host (CREID_E_ARG before any launch).  The kernel
+ * itself refuses whatever the device-side metadata would send out of bounds: an image whose extent does not fit `src_bytes`,
+ * whose sides are outside 1..16384 or whose tables do not fit `table_len` comes out black, and tap ranges are clamped into
+ * the image. */
+int creid_resize_u8(const uint8_t* src, int64_t src_bytes, const int64_t* offsets, const int32_t* sizes, const int32_t* tables,
+                    int64_t table_len, const int32_t* table_offsets, int64_t B, int64_t H, int64_t W, uint8_t* out,
+                    void* stream);
 /* fp32 OIHW master weights -> compute-dtype [O][r][s][I] (forward) and [I][r][s][O] (dgrad, nullable).
  * CREID_BF16X3: w_krsc = bf16 [2][O][r][s][I], hi plane then lo plane; w_crsk must be NULL (no data gradient in that mode),
  * else CREID_E_ARG.  creid_weight_prep_multi with CREID_BF16X3 writes the same two planes and ignores the crsk fields. */
