@@ -156,7 +156,10 @@ STREAM_MATRIX_BYTES = 1 << 30      # get_similar(streamed="auto"): an m x n fp32
 
 def _similar_materialised(q, g, topk, distance_func):
     """The m x n matrix and its ranking: (indices, distances) as host arrays."""
-    distmat = rm.get_dist_func(distance_func)(x=q, y=g).contiguous()
+    return _select_rows(rm.get_dist_func(distance_func)(x=q, y=g).contiguous(), topk)
+
+
+def _select_rows(distmat, topk):
     if topk:                                                   # top-k selection kernel: no full sort of the row
         indices, dist_sel = rm.topk_rows(distmat, min(int(topk), distmat.shape[1]))
     else:
@@ -166,7 +169,7 @@ def _similar_materialised(q, g, topk, distance_func):
 
 
 def get_similar(embeddings, paths, embeddings_gallery, paths_gallery, topk=0, normalize_features=True,
-                distance_func="euclidean", streamed="auto", stats=None, compute_dtype=torch.float32):
+                distance_func="euclidean", streamed="auto", stats=None, compute_dtype=torch.float32, reranking=False):
     """inference/get_similar.py:99-125 -> {query_path: {"indices", "paths", "distances"}} (numpy arrays).
 
     streamed: False -- the m x n distance matrix is written and every row selected from it (get_dist_func + topk_rows /
@@ -177,7 +180,15 @@ def get_similar(embeddings, paths, embeddings_gallery, paths_gallery, topk=0, no
     compute_dtype: torch.float32 (default, the reference's arithmetic), torch.bfloat16 or torch.float16 -- the (optionally
     normalised) features are rounded ONCE to that type and every path works on the rounded features with the 16-bit MFMA
     kernels (half the gallery bytes; the distances stay fp32).  The three paths still agree bit for bit with one another.
-    stats (a dict) receives "path" ("materialised" | "streamed" | "chunked") and topk_stream's counters."""
+    reranking: True (the defaults of reid_metric.re_ranking) or a dict of k1 / k2 / lambda_value -- the k-reciprocal re-ranked
+    matrix is ranked in place of the distance matrix and the returned "distances" are its values; always the materialised path
+    (CreidError with streamed=True, a 16-bit compute_dtype or the cosine distance).
+    stats (a dict) receives "path" ("materialised" | "streamed" | "chunked" | "reranked"), topk_stream's counters and
+    re_ranking's statistics."""
+    rr = rm.rerank_options(reranking)
+    if rr is not None and (streamed is True or compute_dtype != torch.float32 or distance_func != "euclidean"):
+        raise L.CreidError("get_similar(reranking=...) re-ranks the materialised squared-L2 fp32 matrix: not with streamed=True, "
+                           f"compute_dtype={compute_dtype} or distance_func={distance_func!r}")
     if streamed not in (True, False, "auto"):
         raise ValueError(f"streamed must be True, False or 'auto', got {streamed!r}")
     if compute_dtype not in (torch.float32, torch.bfloat16, torch.float16):
@@ -199,7 +210,10 @@ def get_similar(embeddings, paths, embeddings_gallery, paths_gallery, topk=0, no
                            f"got distance_func={distance_func!r}, topk={topk}")
     big = m * n * 4 > STREAM_MATRIX_BYTES
     info = {}
-    if streamed is True or (streamed == "auto" and big and streamable and rm.topk_stream_sample(k, n) <= n // 4):
+    if rr is not None:
+        idx, dist_sel = _select_rows(rm.re_ranking(q, g, **rr, stats=info), topk)
+        info["path"] = "reranked"
+    elif streamed is True or (streamed == "auto" and big and streamable and rm.topk_stream_sample(k, n) <= n // 4):
         indices, dist_sel = rm.topk_stream(q, g, k, stats=info)
         idx, dist_sel = indices.cpu().numpy(), dist_sel.cpu().numpy()
         info["path"] = "streamed"

@@ -211,6 +211,182 @@ def topk_stream(q: torch.Tensor, g: torch.Tensor, k: int, qq=None, gg=None, *, s
     return idx, dsel
 
 
+RERANK_DEFAULTS = dict(k1=20, k2=6, lambda_value=0.3)
+_RERANK_LDS = 64 << 10                # dynamic LDS of every csrc/rerank.hip kernel
+
+
+def rerank_options(reranking):
+    """The `reranking=` argument of R1_mAP / get_similar: False / None -> None; True -> the defaults of re_ranking; a dict of
+    k1 / k2 / lambda_value -> those over the defaults."""
+    if reranking is None or reranking is False:
+        return None
+    if reranking is True:
+        return dict(RERANK_DEFAULTS)
+    if isinstance(reranking, dict) and set(reranking) <= set(RERANK_DEFAULTS):
+        return {**RERANK_DEFAULTS, **reranking}
+    raise L.CreidError(f"reranking must be False, True or a dict of k1 / k2 / lambda_value, got {reranking!r}")
+
+
+def _pow2_at_least(v: int) -> int:
+    p = 1
+    while p < v:
+        p *= 2
+    return p
+
+
+def _csr_from_counts(count: torch.Tensor) -> torch.Tensor:
+    rowptr = torch.zeros(count.shape[0] + 1, dtype=torch.int64, device=count.device)
+    rowptr[1:] = torch.cumsum(count, 0, dtype=torch.int64)
+    return rowptr
+
+
+class _StageClock:
+    """Device events at stage boundaries (only when asked for: stats={"timing": True}); the host's waits between two marks
+    fall inside the stage that caused them, so the stages add up to the call."""
+
+    def __init__(self, on):
+        self.on, self.marks = on, []
+        self.mark("start")
+
+    def mark(self, name):
+        if self.on:
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record()
+            self.marks.append((name, ev))
+
+    def stage_ms(self):
+        self.marks[-1][1].synchronize()
+        return {name: prev.elapsed_time(ev) for (_, prev), (name, ev) in zip(self.marks, self.marks[1:])}
+
+
+def re_ranking(q: torch.Tensor, g: torch.Tensor, k1: int = 20, k2: int = 6, lambda_value: float = 0.3, *, stats=None,
+               debug=None) -> torch.Tensor:
+    """k-reciprocal re-ranking (Zhong et al., CVPR 2017) of fp32 device features q [nq, D], g [ng, D]: the fp32 [nq, ng]
+    matrix (1 - lambda) * Jaccard + lambda * d / max_row(d), to be ranked like a distance matrix -- with no N x N matrix
+    (N = nq + ng) at any point: the only [nq, ng] tensors are the result and get_euclidean(q, g).
+
+    X = cat(q, g); d = get_euclidean's squared L2; every ordering is by (d, index).
+      1. neighbours N_{k1+1}(i): topk_stream(X, X, k1 + 1);  M_i = max_j d(i, j): get_euclidean over bounded row chunks + amax;
+         od = d / M_i (0 where M_i == 0);
+      2. creid_rerank_recip: R(i, k) = {j in N_{k+1}(i) : i in N_{k+1}(j)}, R*(i) = R(i, k1) united with every R(c, kh),
+         c in R(i, k1), kh = around(k1 / 2), whose overlap with R(i, k1) exceeds 2/3 of it -- sorted CSR rows (count, scan, fill);
+      3. creid_rerank_weights: V(i, j) = exp(-od(i, j)) normalised over R*(i);
+      4. creid_rerank_expand (k2 > 1): V'(i) = mean of V over N_{k2}(i);
+      5. creid_rerank_blend: J(i, j) = 1 - s / (2 - s), s = sum_c min(V'(i, c), V'(j, c)); pairs that share no column keep J = 1.
+    The result does not depend on launch order: two calls return the same bits.
+    Limits (CreidError): CPU tensors; k1 + 1 > min(N, 1024); k2 < 1 or k2 > k1 + 1; lambda outside [0, 1]; and rows that do not
+    fit the kernels' LDS (a worst-case R* row of (k1 + 1)(kh + 2) entries: k1 <= 125; the k2 merged rows of one V' row: 4096
+    entries; D <= 16380).
+    stats (a dict) receives nnz_v, nnz_vprime, max_row_v, max_row_vprime and temp_bytes (per stage, the bytes of the
+    temporaries it allocates, from their shapes; the [nq, ng] distance matrix is not a temporary), and -- when it comes in holding timing=True -- stage_ms (per stage, between device events); debug (a dict) receives the neighbour table, the row maxima and the CSR arrays of R* / V
+    (rstar_rowptr, rstar_cols, v_vals) and of V' (vprime_rowptr, vprime_cols, vprime_vals)."""
+    if not isinstance(q, torch.Tensor) or not isinstance(g, torch.Tensor):
+        raise L.CreidError("re_ranking needs device tensors (no CPU fallback)")
+    L.require_gpu(q, g)
+    if q.dtype != torch.float32 or g.dtype != torch.float32 or q.dim() != 2 or g.dim() != 2 or q.shape[1] != g.shape[1]:
+        raise L.CreidError("re_ranking needs fp32 [nq, D] and [ng, D] features")
+    nq, ng = q.shape[0], g.shape[0]
+    N, k1, k2, lam = nq + ng, int(k1), int(k2), float(lambda_value)
+    if k1 < 0 or k1 + 1 > min(N, 1024):
+        raise L.CreidError(f"re_ranking: k1 + 1 = {k1 + 1} outside 1 .. min(N = {N}, 1024)")
+    if k2 < 1 or k2 > k1 + 1:
+        raise L.CreidError(f"re_ranking: k2 = {k2} outside 1 .. k1 + 1 = {k1 + 1}")
+    if not 0.0 <= lam <= 1.0:
+        raise L.CreidError(f"re_ranking: lambda_value = {lambda_value} outside [0, 1]")
+    K, kh = k1 + 1, int(np.around(k1 / 2))
+    if 4 * (K + kh + 1 + _pow2_at_least(K * (kh + 2))) > _RERANK_LDS:
+        raise L.CreidError(f"re_ranking: a worst-case reciprocal row of (k1 + 1)(kh + 2) = {K * (kh + 2)} entries does not fit "
+                           "the set kernel's LDS (k1 <= 125)")
+    dev, lib, st = q.device, L.lib(), L.stream()
+    if nq == 0 or ng == 0:
+        return torch.empty((nq, ng), dtype=torch.float32, device=dev)
+    X = _pad_width(torch.cat([q, g]).contiguous())
+    D = X.shape[1]
+    if 4 * (D + 4) > _RERANK_LDS:
+        raise L.CreidError(f"re_ranking: D = {D} does not fit the weight kernel's LDS (D <= 16380)")
+    clock = _StageClock(bool(stats) and bool(stats.get("timing")))
+    xx = row_sqnorm(X)
+    temp = {}
+    # 1. neighbours and row maxima
+    nb, _ = topk_stream(X, X, K, xx, xx)
+    del _
+    clock.mark("neighbours")
+    rowmax = torch.empty(N, dtype=torch.float32, device=dev)
+    rows = max(1, _STREAM_TOPK_CHUNK_BYTES // (N * 4))
+    for r0 in range(0, N, rows):
+        r1 = min(N, r0 + rows)
+        rowmax[r0:r1] = get_euclidean(X[r0:r1], X, xx[r0:r1], xx).amax(dim=1)
+    temp["neighbours"] = nb.numel() * 12 + min(_STREAM_TOPK_CHUNK_BYTES, N * STREAM_TOPK_CAPACITY * 8)
+    temp["row_maxima"] = min(rows, N) * N * 4
+    clock.mark("row_maxima")
+    # 2. reciprocal sets: count, scan, fill
+    count = torch.empty(N, dtype=torch.int32, device=dev)
+    L.check(lib.creid_rerank_recip(L.ptr(nb), N, K, kh, None, L.ptr(count), None, st), "creid_rerank_recip")
+    rowptr = _csr_from_counts(count)
+    nnz = int(rowptr[-1].item())
+    cols = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)
+    L.check(lib.creid_rerank_recip(L.ptr(nb), N, K, kh, L.ptr(rowptr), None, L.ptr(cols), st), "creid_rerank_recip")
+    temp["reciprocal_sets"] = N * 4 + (N + 1) * 8 + nnz * 4
+    clock.mark("reciprocal_sets")
+    # 3. weights
+    vals = torch.empty(max(nnz, 1), dtype=torch.float32, device=dev)
+    L.check(lib.creid_rerank_weights(L.ptr(X), L.ptr(xx), L.ptr(rowmax), N, D, L.ptr(rowptr), L.ptr(cols), L.ptr(vals), st),
+            "creid_rerank_weights")
+    temp["weights"] = nnz * 4
+    lens = rowptr[1:] - rowptr[:-1]
+    max_row_v = int(lens.max().item())
+    clock.mark("weights")
+    # 4. local query expansion
+    if k2 > 1:
+        merged = lens[nb[:, :k2]].sum(dim=1)
+        cap = _pow2_at_least(max(int(merged.max().item()), 1))
+        if 12 * cap + 4 * (k2 + 1 + 4) > _RERANK_LDS:
+            raise L.CreidError(f"re_ranking: the k2 = {k2} rows merged into one row of V' hold up to {int(merged.max().item())} "
+                               "entries; the expansion kernel's LDS takes 4096")
+        count2 = torch.empty(N, dtype=torch.int32, device=dev)
+        L.check(lib.creid_rerank_expand(L.ptr(nb), N, K, k2, L.ptr(rowptr), L.ptr(cols), L.ptr(vals), cap, None, L.ptr(count2),
+                                        None, None, st), "creid_rerank_expand")
+        rowptr2 = _csr_from_counts(count2)
+        nnz2 = int(rowptr2[-1].item())
+        cols2 = torch.empty(max(nnz2, 1), dtype=torch.int32, device=dev)
+        vals2 = torch.empty(max(nnz2, 1), dtype=torch.float32, device=dev)
+        L.check(lib.creid_rerank_expand(L.ptr(nb), N, K, k2, L.ptr(rowptr), L.ptr(cols), L.ptr(vals), cap, L.ptr(rowptr2), None,
+                                        L.ptr(cols2), L.ptr(vals2), st), "creid_rerank_expand")
+        temp["expansion"] = N * k2 * 8 + N * 12 + (N + 1) * 8 + nnz2 * 8
+        del merged, count2
+    else:
+        rowptr2, cols2, vals2, nnz2 = rowptr, cols, vals, nnz
+        temp["expansion"] = 0
+    clock.mark("expansion")
+    # 5. blend: the gallery rows of V' column-major (a stable sort keeps the gallery indices ascending inside a column)
+    lens2 = rowptr2[1:] - rowptr2[:-1]
+    g0, g1, max_row_q, max_row_vp = (int(v) for v in torch.stack([rowptr2[nq], rowptr2[N], lens2[:nq].max(), lens2.max()]).tolist())
+    tile = min((ng + 31) // 32 * 32, 128 << 10)
+    if max_row_q * 8 + tile // 8 > _RERANK_LDS:
+        raise L.CreidError(f"re_ranking: a query row of V' with {max_row_q} entries does not fit the blend kernel's LDS")
+    gcols = cols2[g0:g1]
+    grows = torch.repeat_interleave(torch.arange(ng, dtype=torch.int32, device=dev), lens2[nq:])
+    colrows = grows[torch.sort(gcols, stable=True).indices].contiguous()
+    colptr = torch.zeros(N + 1, dtype=torch.int64, device=dev)
+    colptr[1:] = torch.cumsum(torch.bincount(gcols.long(), minlength=N), 0)
+    temp["column_index"] = (g1 - g0) * 32 + (N + 1) * 16
+    del grows, gcols
+    clock.mark("column_index")
+    dist = get_euclidean(X[:nq], X[nq:], xx[:nq].contiguous(), xx[nq:].contiguous())
+    out = torch.empty_like(dist)
+    L.check(lib.creid_rerank_blend(L.ptr(dist), L.ptr(rowmax), nq, ng, lam, L.ptr(rowptr2), L.ptr(cols2), L.ptr(vals2),
+                                   L.ptr(colptr), L.ptr(colrows), max_row_q, L.ptr(out), st), "creid_rerank_blend")
+    clock.mark("blend")
+    if stats is not None:
+        stats.update(nnz_v=nnz, nnz_vprime=nnz2, max_row_v=max_row_v, max_row_vprime=max_row_vp, temp_bytes=temp)
+        if clock.on:
+            stats["stage_ms"] = clock.stage_ms()
+    if debug is not None:
+        debug.update(neighbours=nb, rowmax=rowmax, rstar_rowptr=rowptr, rstar_cols=cols[:nnz], v_vals=vals[:nnz],
+                     vprime_rowptr=rowptr2, vprime_cols=cols2[:nnz2], vprime_vals=vals2[:nnz2], dist=dist)
+    return out
+
+
 def _dev_i64(a, device):
     if isinstance(a, torch.Tensor):
         return a.to(device=device, dtype=torch.int64).contiguous()
@@ -472,11 +648,15 @@ class R1_mAP:
     MODEL.USE_CENTROIDS); trainer/logger lookups of the reference are optional here."""
 
     def __init__(self, pl_module=None, num_query=0, max_rank=50, feat_norm=True, dist_func="euclidean",
-                 compute_dtype=torch.float32, streamed=False):
+                 compute_dtype=torch.float32, streamed=False, reranking=False):
         """streamed=True: metric-only evaluation that never materialises the distance / index matrices (euclidean,
         plain camera ids; compute_dtype fp32, bf16 or f16 -- the 16-bit modes run the 16-bit MFMA and return exactly what
         their materialised evaluation returns); `last` then holds the per-query results only.  streamed=False keeps
-        `last["distmat"]` / `last["indices"]` (what the rank-index parity tests and get_similar read)."""
+        `last["distmat"]` / `last["indices"]` (what the rank-index parity tests and get_similar read).
+        reranking=True (the defaults of re_ranking) or a dict of k1 / k2 / lambda_value: on the materialised euclidean fp32 path
+        the k-reciprocal re-ranked matrix takes the place of `distmat`; ranking and evaluation are unchanged.  CreidError with
+        streamed=True, a 16-bit compute_dtype, the cosine distance or compute_chunked."""
+        self.reranking = rerank_options(reranking)
         self.streamed = streamed
         self.num_query = num_query
         self.max_rank = max_rank
@@ -491,6 +671,9 @@ class R1_mAP:
         self.dist_name = dist_func
         self.dist_func = get_dist_func(dist_func)
         self.last = {}
+        if self.reranking is not None and (streamed or compute_dtype != torch.float32 or dist_func != "euclidean"):
+            raise L.CreidError("R1_mAP(reranking=...) re-ranks the materialised euclidean fp32 matrix: not with streamed=True, "
+                               f"compute_dtype={compute_dtype} or dist_func={dist_func!r}")
 
     def compute(self, feats, pids, camids, respect_camids=False):
         if not isinstance(feats, torch.Tensor) or not feats.is_cuda:
@@ -507,7 +690,10 @@ class R1_mAP:
             else:
                 f = feats if self.compute_dtype == torch.float32 else feats.to(self.compute_dtype)
                 sq = row_sqnorm(f)
-            distmat = get_euclidean(f[:nq], f[nq:], sq[:nq].contiguous(), sq[nq:].contiguous())
+            if self.reranking is not None:
+                distmat = re_ranking(f[:nq], f[nq:], **self.reranking)
+            else:
+                distmat = get_euclidean(f[:nq], f[nq:], sq[:nq].contiguous(), sq[nq:].contiguous())
         else:
             f = l2_normalize(feats) if self.feat_norm else feats
             distmat = self.dist_func(f[:nq].contiguous(), f[nq:].contiguous())
@@ -610,6 +796,8 @@ class R1_mAP:
         `query_chunk` query rows at a time (distance tile, rank, CMC/AP scan on the device, only per-query results kept)."""
         if not isinstance(feats, torch.Tensor) or not feats.is_cuda:
             raise L.CreidError("R1_mAP.compute_chunked needs device features (no CPU fallback)")
+        if self.reranking is not None:
+            raise L.CreidError("R1_mAP.compute_chunked never holds the [nq, ng] matrix that reranking replaces: use compute()")
         from .parallel import merge_eval_results
         euclid = self.dist_name == "euclidean"
         feats = _pad_width(feats.float().contiguous())

@@ -188,6 +188,39 @@ int creid_stream_topk_collect_h16(const void* q, const void* g, const float* qq,
                                   int64_t D, int dtype, const float* tau, int32_t cap, uint64_t* cand, int32_t* count,
                                   void* stream);
 
+/* ---- k-reciprocal re-ranking (Zhong et al., CVPR 2017; csrc/rerank.hip): the sparse stages between the streamed top-k and
+ * the ranking kernels.  X = cat(q, g) fp32 [N][D], d = creid_sqdist_matrix's squared L2, every ordering by (d, index);
+ * nb int64 [N][K], K = k1 + 1: row i's K nearest columns of X (creid_stream_topk_* on (X, X)); rowmax fp32 [N]:
+ * M_i = max_j d(i, j); od(i, j) = d(i, j) / M_i (0 where M_i == 0).  Sparse rows are CSR: rowptr int64 [N + 1], columns
+ * int32 ascending and distinct inside a row, values fp32.
+ *  recip   : R(i, k) = { j in nb[i][:k+1] : i in nb[j][:k+1] };  R*(i) = R(i, k1) united with every R(c, kh), c in R(i, k1),
+ *            that has 3 |R(c, kh) & R(i, k1)| > 2 |R(c, kh)|.  cols == NULL: count int32 [N] receives |R*(i)|; else
+ *            cols[rowptr[i] ..] receives R*(i) (rowptr = the exclusive scan of count).  0 <= kh < K <= min(N, 1024);
+ *            CREID_E_SHAPE when a worst-case row, K (kh + 2) entries, does not fit the kernel's LDS.
+ *  weights : vals[p] = exp(-od(i, j)) / sum over row i of exp(-od(i, .)) for every listed (i, j = cols[p]), with
+ *            d(i, j) = fmaf(-2, <x_i, x_j>, qq[i] + qq[j]); qq fp32 [N] the row square norms; D % 4 == 0, D <= 16380.
+ *  expand  : V'(i) = (1 / k2) sum_{t < k2} V(nb[i][t]), addends in that order.  cap = a power of two >= the largest
+ *            sum_{t < k2} |V(nb[i][t])| over all rows (12 cap + 4 k2 bytes of LDS must fit, else CREID_E_SHAPE).
+ *            cols2 == NULL: count2 int32 [N] receives |V'(i)|; else cols2 / vals2 [rowptr2[i] ..] receive the row.
+ *  blend   : out[i][j] = (1 - lambda) J(i, nq + j) + lambda dist[i][j] / M_i over dist fp32 [nq][ng] =
+ *            creid_sqdist_matrix(q, g), J = 1 - s / (2 - s), s = sum_c min(V'(i, c), V'(nq + j, c)) in ascending c.  A dense
+ *            pass writes (1 - lambda) + lambda dist / M_i (J = 1: no shared column) everywhere; a sparse pass rewrites the
+ *            pairs that share a column, found through colptr int64 [N + 1] / colrows int32: the gallery rows of V' (row
+ *            indices 0 .. ng - 1) column-major, ascending inside a column.  rowptr / cols / vals: V' of all N rows;
+ *            max_row = the longest query row.  Each pair is written by exactly one lane and its value does not depend on
+ *            which; no floating-point atomics.
+ * Every stage returns 0 for N == 0 and checks its limits before anything is launched. */
+int creid_rerank_recip(const int64_t* nb, int64_t N, int32_t K, int32_t kh, const int64_t* rowptr, int32_t* count,
+                       int32_t* cols, void* stream);
+int creid_rerank_weights(const float* X, const float* qq, const float* rowmax, int64_t N, int64_t D,
+                         const int64_t* rowptr, const int32_t* cols, float* vals, void* stream);
+int creid_rerank_expand(const int64_t* nb, int64_t N, int32_t K, int32_t k2, const int64_t* rowptr, const int32_t* cols,
+                        const float* vals, int32_t cap, const int64_t* rowptr2, int32_t* count2, int32_t* cols2,
+                        float* vals2, void* stream);
+int creid_rerank_blend(const float* dist, const float* rowmax, int64_t nq, int64_t ng, float lambda,
+                       const int64_t* rowptr, const int32_t* cols, const float* vals, const int64_t* colptr,
+                       const int32_t* colrows, int32_t max_row, float* out, void* stream);
+
 /* Measured launch plans (optional).  kind 0 = weight gradient: key (M = batch*out_h*out_w, out_c, K = kh*kw*in_c, 0) ->
  * (tile rows 64|128, tile cols 64|128, pixel splits | ring depth << 16 | producer/consumer waves << 20 | two k-groups << 21);
  * kind 1 = implicit-GEMM forward / data gradient: key (GEMM rows M, GEMM cols N, K, transposed 0|1 | stride << 1) ->
