@@ -23,8 +23,11 @@ struct BnBwdFinJob {
 };
 
 // One workgroup of NT threads finalizes channels [block*CW, block*CW + CW).  lds: >= NT*4 bytes.
+// active = false (uniform per wave): a wave of a larger workgroup that only keeps the barrier -- the NT active threads then sum
+// in exactly the grouping of an NT-thread workgroup.
 template <int NT, int CW>
-__device__ __forceinline__ void bn_bwd_finalize_block_cw(const BnBwdFinJob& j, int block, void* lds) {
+__device__ __forceinline__ void bn_bwd_finalize_block_cw(const BnBwdFinJob& j, int block, void* lds, bool active = true) {
+  if (!active) { __syncthreads(); return; }
   constexpr int RG = NT / CW, NW = NT / 64;
   double* red = reinterpret_cast<double*>(lds);              // [NW][2][CW]
   const int tid = threadIdx.x, cl = tid % CW, rg = tid / CW;
@@ -72,9 +75,9 @@ __device__ __forceinline__ void bn_bwd_finalize_block_cw(const BnBwdFinJob& j, i
 }
 
 template <int NT>
-__device__ __forceinline__ void bn_bwd_finalize_block(const BnBwdFinJob& j, int block, void* lds) {
-  if (j.cw == 4) bn_bwd_finalize_block_cw<NT, 4>(j, block, lds);     // uniform over the launch
-  else bn_bwd_finalize_block_cw<NT, 16>(j, block, lds);
+__device__ __forceinline__ void bn_bwd_finalize_block(const BnBwdFinJob& j, int block, void* lds, bool active = true) {
+  if (j.cw == 4) bn_bwd_finalize_block_cw<NT, 4>(j, block, lds, active);     // uniform over the launch
+  else bn_bwd_finalize_block_cw<NT, 16>(j, block, lds, active);
 }
 
 static inline void bn_bwd_fin_shape(BnBwdFinJob& j) {       // host: channels per workgroup and workgroup count

@@ -5,10 +5,13 @@
 // this is a "TN" GEMM.  bf16: the tiles land in LDS exactly as they lie in memory ([pixel][channel])
 // and the MFMA fragments (8 consecutive pixels of one channel per lane) come out of gfx950's
 // transposing LDS read `ds_read_b64_tr_b16` -- no register or memory transpose.
-//   wgrad_bf16_dma_kernel (all 1x1 / 3x3 layers): both tiles are fetched with the global->LDS DMA into linear
+//   wgrad_bf16_dma_kernel (1x1 / 3x3 layers): both tiles are fetched with the global->LDS DMA into linear
 //     rows, bank conflicts avoided by an XOR swizzle of 64-byte units applied on the DMA source column; the
 //     gathered operand's pixel coordinates advance incrementally (64 pixels per k-step); fragment reads run one
 //     16-pixel slice ahead of the MFMAs.
+//   wgrad_bf16_taps_kernel (stride-1 pad-1 3x3 layers, C_in 64..512, OW 8 / 16 / 32): one workgroup owns 64 co x 64 ci x ALL NINE
+//     taps; per 128-pixel k-step the dY tile and the X halo patch enter LDS once, a tap is a per-lane slot address.  Same
+//     workspace layout, its own split count (plan_wgrad_route); CREID_WGRAD_TAPS=0 puts these layers back on the kernel above.
 //   wgrad_bf16_kernel (stem, span 32): register-staged 16-B stores, row pitch = tile width + 32 elements.
 // f32 (parity mode): K-major LDS is the natural layout for v_mfma_f32_32x32x2_f32.
 // The pixel range is split over gridDim.y workgroups; fp32 partial tiles go to the workspace and
@@ -18,6 +21,7 @@
 #include "bn_fin.hpp"
 #include "tune.hpp"
 #include <stdlib.h>
+#include <atomic>
 
 namespace {
 constexpr int WKS = 64;   // pixels per k-step (bf16)
@@ -516,6 +520,223 @@ __global__ __launch_bounds__(WS ? 512 : 256 * KG, (KG * NS * (TM + TN) * 128 <= 
       }
 }
 
+// ------------------------------------------------------------------------------------ bf16 / f16, nine taps per workgroup
+// Stride-1 pad-1 3x3 layers.  wgrad_bf16_dma_kernel gives every workgroup one (co-tile, tap x ci-tile) output tile, so the dY tile
+// of a pixel range is DMA'd by nine times as many workgroups as a 1x1 layer of the same width needs and the X tile is fetched nine
+// times under one-pixel shifts.  Here ONE workgroup owns (64 co x 64 ci x all nine taps) over its pixel range: per 128-pixel k-step
+// (whole image rows of one image) the dY tile [128][64] enters LDS once and so does the X HALO patch of the same pixels -- output
+// rows + 2, OW + 2 slots of 64 channels each, out-of-image slots fetched from the zero page.  Every 16-pixel slice's dY fragment
+// is read from LDS once and multiplied against nine X fragments: a tap (r, s) is only another per-lane slot address,
+//   slot(pixel p, r, s) = (p / OW + r) * (OW + 2) + p % OW + s.
+// Rows are 128 bytes; the 64-byte-unit XOR key of a row / slot is (index >> 1) & 1, applied on the DMA source column and again in
+// the read address: four CONSECUTIVE slots -- what a 16-lane group of a transposing read touches, whatever the tap's shift -- land
+// on four different 16-bank ranges.  512 threads = two k-groups of four waves over ONE ring: a group multiplies four of a step's
+// eight slices, each of its waves holding a 32 x 32 tile of all nine taps (144 accumulator registers, two waves per SIMD), and
+// the groups' accumulators are merged through LDS before the store -- half the partial tiles of a split twice as fine.
+// Fragment reads run one UNIT (three taps of one slice: 6 or 8 transposing reads) ahead of the MFMAs, so the 4-bit lgkmcnt
+// suffices.  Partial tiles go to the workspace [split][NCO][K = 9 * C_in] (tap-major columns), i.e. the layout of the tile kernels:
+// the split reductions are shared.  1-D grid, all tiles of a pixel range on one XCD; the first workgroups carry the BatchNorm job.
+constexpr int TPK = 128;   // pixels per k-step (tap-fused kernel): split lengths are multiples of it
+
+template <int OW>
+struct TapsGeom {
+  static constexpr int ROWS = TPK / OW, HP = OW + 2, NSLOT = (ROWS + 2) * HP;   // halo patch of a k-step: rows x slots per row
+  static constexpr int NIH = (NSLOT + 63) / 64;                                 // halo DMA instructions per wave (8 slots each, 8 waves)
+  static constexpr int TILE_A = TPK * 64, STAGE = TILE_A + NIH * 64 * 64;       // elements
+  static constexpr int slice_slot(int kk) { return kk * 16 + 2 * ((kk * 16) / OW); }   // first halo slot of 16-pixel slice kk
+};
+
+template <int NW>
+__device__ __forceinline__ void tr_wait_unit(s16x4& al, s16x4& ah, s16x4 (&bl)[3], s16x4 (&bh)[3]) {
+  asm volatile("s_waitcnt lgkmcnt(%8)" : "+v"(al), "+v"(ah), "+v"(bl[0]), "+v"(bh[0]), "+v"(bl[1]), "+v"(bh[1]), "+v"(bl[2]), "+v"(bh[2]) : "n"(NW) : "memory");
+}
+
+// fragment reads of unit U = (slice U / 3, taps 3 * (U % 3) ..+2): the slice's dY fragment with its first tap group
+template <int OW, int U>
+__device__ __forceinline__ void taps_load_unit(unsigned fa, const unsigned (&fb)[9], unsigned sb, s16x4 (&al)[2], s16x4 (&ah)[2],
+                                               s16x4 (&bl)[2][3], s16x4 (&bh)[2][3]) {
+  constexpr int KK = U / 3, G = U % 3, S = TapsGeom<OW>::slice_slot(KK), FLIP = ((S >> 1) & 1) * 64;
+  if constexpr (G == 0) tr_load2<KK * 16 * 128, (KK * 16 + 4) * 128>(fa + sb, al[KK & 1], ah[KK & 1]);
+#pragma unroll
+  for (int j = 0; j < 3; ++j) tr_load2<S * 128, (S + 4) * 128>((fb[3 * G + j] ^ (unsigned)FLIP) + sb, bl[U & 1][j], bh[U & 1][j]);
+}
+
+template <int OW, typename ET, int U>
+__device__ __forceinline__ void taps_unit(unsigned fa, const unsigned (&fb)[9], unsigned sb, s16x4 (&al)[2], s16x4 (&ah)[2],
+                                          s16x4 (&bl)[2][3], s16x4 (&bh)[2][3], f32x16 (&acc)[9]) {
+  constexpr int NU = 3 * (TPK / 32), KK = U / 3, G = U % 3;           // a k-group multiplies four of a step's eight slices
+  if constexpr (U + 1 < NU) {
+    taps_load_unit<OW, U + 1>(fa, fb, sb, al, ah, bl, bh);
+    tr_wait_unit<((U + 1) % 3 == 0) ? 8 : 6>(al[KK & 1], ah[KK & 1], bl[U & 1], bh[U & 1]);
+  } else {
+    tr_wait_unit<0>(al[KK & 1], ah[KK & 1], bl[U & 1], bh[U & 1]);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  const s16x8 a = __builtin_shufflevector(al[KK & 1], ah[KK & 1], 0, 1, 2, 3, 4, 5, 6, 7);
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const s16x8 b = __builtin_shufflevector(bl[U & 1][j], bh[U & 1][j], 0, 1, 2, 3, 4, 5, 6, 7);
+    acc[3 * G + j] = ET::mfma(a, b, acc[3 * G + j]);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  if constexpr (U + 1 < NU) taps_unit<OW, ET, U + 1>(fa, fb, sb, al, ah, bl, bh, acc);
+}
+
+template <int OW, typename ET>
+__global__ __launch_bounds__(512, 2) void wgrad_bf16_taps_kernel(const unsigned short* __restrict__ dy, const unsigned short* __restrict__ x,
+                                                                  int M, int OH, int CIN, int NCO, float* __restrict__ ws, int tiles,
+                                                                  int tiles_ci, int splits, int m_per_split, BnBwdFinJob fin) {
+  using G = TapsGeom<OW>;
+  constexpr int NS = 3, NIA = TPK / 64, NIH = G::NIH, LPT = NIA + NIH, STAGE = G::STAGE;
+  static_assert(NS * STAGE * 2 <= 160 * 1024 && (NS - 2) * LPT <= 63 && (G::slice_slot(7) + 4) * 128 < 65536, "LDS ring / vmcnt / ds offset");
+  // k-group 1 reads slices 4..7 through k-group 0's immediate offsets: same swizzle flips, one constant slot distance
+  static_assert(((G::slice_slot(4) >> 1) & 1) == 0 && G::slice_slot(5) - G::slice_slot(1) == G::slice_slot(4) &&
+                G::slice_slot(6) - G::slice_slot(2) == G::slice_slot(4) && G::slice_slot(7) - G::slice_slot(3) == G::slice_slot(4), "k-groups");
+  static_assert(5 * 16 * 256 * 4 <= NS * STAGE * 2, "accumulator exchange");
+  __shared__ __attribute__((aligned(1024))) unsigned short smem[NS * STAGE];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;          // 8 waves: all issue the DMA
+  const int kg = wave >> 2, wm = (wave >> 1) & 1, wn = wave & 1;            // k-group; the wave's 32 x 32 corner of the 64 x 64 tile
+  // carried job (bn_fin.hpp), as in wgrad_bf16_dma_kernel: the first workgroups (a multiple of 8, so the tiles keep their XCD);
+  // 256 of the threads, so that the sums have the grouping -- the bits -- of the stand-alone launch
+  int bid0 = (int)blockIdx.x;
+  if (fin.partial) {
+    const int nf8 = (fin.nblocks + 7) & ~7;
+    if (bid0 < nf8) {
+      if (bid0 < fin.nblocks) bn_bwd_finalize_block<256>(fin, bid0, smem, tid < 256);
+      return;
+    }
+    bid0 -= nf8;
+  }
+  // XCD placement of wgrad_bf16_dma_kernel: workgroup b runs on XCD b % 8; all tiles of a pixel range (split) go to one XCD, or,
+  // with 1 / 2 / 4 splits, to the 8 / splits XCDs that share the range
+  int tile, split;
+  if (splits >= 8 || (8 % splits) != 0) {
+    const int j = bid0 >> 3, ls = j / tiles;
+    tile = j - ls * tiles;
+    split = (bid0 & 7) + 8 * ls;
+    if (split >= splits) return;
+  } else {
+    const int x8 = bid0 & 7, share = 8 / splits;
+    split = x8 % splits;
+    tile = x8 / splits + share * (bid0 >> 3);
+    if (tile >= tiles) return;
+  }
+  const int tile_co = tile / tiles_ci, tile_ci = tile - tile_co * tiles_ci;
+  const int co0 = tile_co * 64, ci0 = tile_ci * 64;
+  // M and the split length are multiples of TPK and a k-step never leaves its image (OH * OW % TPK == 0): every step is whole
+  const int m_begin = split * m_per_split, m_end = min(M, m_begin + m_per_split);
+  const int nt = (m_end - m_begin) / TPK;
+  const unsigned short* zpage = reinterpret_cast<const unsigned short*>(g_wgrad_zero_page);
+
+  // DMA lane maps: 8 lanes (16-B chunks) per 128-byte row, a wave instruction covers 8 rows / slots; swizzled source column
+  const int dr = lane >> 3, dq = lane & 7;
+  const unsigned short* pa[NIA];
+#pragma unroll
+  for (int i = 0; i < NIA; ++i) {
+    const int row = (i * 8 + wave) * 8 + dr, key = (row >> 1) & 1;
+    pa[i] = dy + (int64_t)(m_begin + row) * NCO + co0 + (((((dq >> 2) ^ key) << 2) + (dq & 3)) << 3);
+  }
+  // halo slot t = (hr, hx) holds the source pixel (oy0 - 1 + hr, hx - 1) of the step's image: relative to the step's first pixel
+  // that is (hr - 1) * OW + hx - 1 pixels away, the same for every step; only the vertical bound moves with oy0
+  int hoff[NIH], hrow[NIH];
+#pragma unroll
+  for (int i = 0; i < NIH; ++i) {
+    const int t = (i * 8 + wave) * 8 + dr, hr = t / G::HP, hx = t - hr * G::HP, key = (t >> 1) & 1;
+    const bool xok = t < G::NSLOT && hx >= 1 && hx <= OW;
+    hrow[i] = xok ? hr - 1 : (1 << 20);                                  // (a slot never filled fails the row test below)
+    hoff[i] = ((hr - 1) * OW + hx - 1) * CIN + ci0 + (((((dq >> 2) ^ key) << 2) + (dq & 3)) << 3);
+  }
+  const unsigned short* xs = x + (int64_t)m_begin * CIN;                   // the issued step's first pixel
+  int oy0 = (m_begin % (OH * OW)) / OW;                                    // and its image row
+  typedef const void __attribute__((address_space(1)))* gptr_t;
+  typedef void __attribute__((address_space(3)))* lptr_t;
+  auto issue = [&](int buf) {
+    unsigned short* la = smem + buf * STAGE + wave * 512;
+    unsigned short* lh = la + G::TILE_A;
+#pragma unroll
+    for (int i = 0; i < NIA; ++i) {
+      __builtin_amdgcn_global_load_lds((gptr_t)pa[i], (lptr_t)(la + i * 4096), 16, 0, 0);
+      pa[i] += (int64_t)TPK * NCO;
+    }
+#pragma unroll
+    for (int i = 0; i < NIH; ++i) {
+      const unsigned short* p = ((unsigned)(oy0 + hrow[i]) < (unsigned)OH) ? xs + hoff[i] : zpage;
+      __builtin_amdgcn_global_load_lds((gptr_t)p, (lptr_t)(lh + i * 4096), 16, 0, 0);
+    }
+    xs += (int64_t)TPK * CIN;
+    oy0 += G::ROWS;
+    if (oy0 >= OH) oy0 = 0;
+  };
+
+  f32x16 acc[9];
+#pragma unroll
+  for (int t = 0; t < 9; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+
+  // transposing-read lane map (wgrad_bf16_dma_kernel) and the per-tap halo slot of this lane's pixel row
+  const int li = lane & 15;
+  const int t_row = 8 * (lane >> 5) + (li >> 2), t_col = 16 * ((lane >> 4) & 1) + 4 * (li & 3);
+  const unsigned lds0 = (unsigned)(uintptr_t)smem;
+  const int cola = wm * 32 + t_col, colb = wn * 32 + t_col;
+  const unsigned fa = lds0 + 2u * (unsigned)((kg * 64 + t_row) * 64 + (((cola >> 5) ^ ((t_row >> 1) & 1)) << 5) + (cola & 31));
+  const int slot0 = t_row + 2 * (t_row / OW) + kg * G::slice_slot(4);
+  unsigned fb[9];
+#pragma unroll
+  for (int t = 0; t < 9; ++t) {
+    const int slot = slot0 + (t / 3) * G::HP + (t % 3);
+    fb[t] = lds0 + 2u * (unsigned)(G::TILE_A + slot * 64 + (((colb >> 5) ^ ((slot >> 1) & 1)) << 5) + (colb & 31));
+  }
+  auto compute = [&](unsigned sb) {
+    s16x4 al[2], ah[2], bl[2][3], bh[2][3];
+    taps_load_unit<OW, 0>(fa, fb, sb, al, ah, bl, bh);
+    taps_unit<OW, ET, 0>(fa, fb, sb, al, ah, bl, bh, acc);
+  };
+#pragma unroll
+  for (int p = 0; p < NS - 1; ++p)
+    if (p < nt) issue(p);
+  int buf = 0;
+  for (int t = 0; t < nt; ++t) {
+    const int younger = min(nt - 1 - t, NS - 2);
+    if (younger == 1) wg_wait_vm<LPT>(); else wg_wait_vm<0>();
+    asm volatile("s_barrier" ::: "memory");     // bare barrier: a fence would drain the whole ring (vmcnt 0)
+    if (t + NS - 1 < nt) issue(buf == 0 ? NS - 1 : buf - 1);
+    compute((unsigned)(buf * STAGE * 2));
+    buf = (buf + 1 == NS) ? 0 : buf + 1;
+  }
+  // k-group 1 hands its accumulators to k-group 0 through LDS (five taps, then four: the ring is dead and holds 80 KB of them);
+  // fixed order, so the result is deterministic, and ONE set of partial tiles leaves the CU
+  {
+    float* ex = reinterpret_cast<float*>(smem);
+    const int t256 = tid & 255;
+#pragma unroll
+    for (int t0 = 0; t0 < 9; t0 += 5) {
+      __syncthreads();
+      if (kg == 1) {
+#pragma unroll
+        for (int t = t0; t < (t0 == 0 ? 5 : 9); ++t)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) ex[((t - t0) * 16 + r) * 256 + t256] = acc[t][r];
+      }
+      __syncthreads();
+      if (kg == 0) {
+#pragma unroll
+        for (int t = t0; t < (t0 == 0 ? 5 : 9); ++t)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) acc[t][r] += ex[((t - t0) * 16 + r) * 256 + t256];
+      }
+    }
+    if (kg == 1) return;
+  }
+  // partial tiles -> workspace [split][NCO][K], column = tap * C_in + ci
+  const int l31 = lane & 31, kh = lane >> 5, K = 9 * CIN;
+  float* wsp = ws + ((int64_t)split * NCO + co0 + wm * 32 + 4 * kh) * K + ci0 + wn * 32 + l31;
+#pragma unroll
+  for (int t = 0; t < 9; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) wsp[(int64_t)((r & 3) + 8 * (r >> 2)) * K + t * CIN] = acc[t][r];
+}
+
 template <int TM, int TN>
 __global__ __launch_bounds__(256) void wgrad_f32_kernel(IGemmGeom g, const float* __restrict__ dy,
                                                         const float* __restrict__ x, int NCO, float* __restrict__ ws,
@@ -834,7 +1055,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_taps_kernel(const float* __r
 // ------------------------------------------------------------------------------------ host
 static int ilog2x(int64_t v) { int l = 0; while ((1LL << l) < v) ++l; return ((1LL << l) == v) ? l : -1; }
 
-struct WgradPlan { int tm, tn, tiles, tiles_k, splits, m_per_split, xcd, stages, ws, kg; };   // stages / ws / kg: 0 = default
+struct WgradPlan { int tm, tn, tiles, tiles_k, splits, m_per_split, xcd, stages, ws, kg, taps; };   // stages / ws / kg: 0 = default; taps: wgrad_bf16_taps_kernel
 
 static WgradPlan plan_wgrad(int M, int NCO, int K, int dtype, int stride = 1) {
   // The fp32 partial tiles cost  workgroups x TM x TN x 8 bytes  of traffic per layer (write + re-read by the
@@ -848,7 +1069,7 @@ static WgradPlan plan_wgrad(int M, int NCO, int K, int dtype, int stride = 1) {
   const int ks = creid_is16(dtype) ? WKS : WKF;
   const int cand[3][2] = {{128, 128}, {128, 64}, {64, 64}};
   WgradPlan p;
-  p.stages = 0; p.ws = 0; p.kg = 0;
+  p.stages = 0; p.ws = 0; p.kg = 0; p.taps = 0;
   TunePlan tp;
   const bool have_plan = creid_is16(dtype) && creid_tune_lookup(CREID_TUNE_WGRAD, M, NCO, K, stride << 1, tp);
   if (have_plan && !((tp.p0 == 64 || tp.p0 == 128) && (tp.p1 == 64 || tp.p1 == 128) && NCO % tp.p0 == 0 && K % tp.p1 == 0 && tp.p2 >= 1))
@@ -895,6 +1116,70 @@ static WgradPlan plan_wgrad(int M, int NCO, int K, int dtype, int stride = 1) {
     if (p.splits <= max_splits_pref) break;
   }
   return p;
+}
+
+// ---- the tap-fused route (wgrad_bf16_taps_kernel): coverage, split count and workspace are decided HERE for every caller
+// (creid_conv2d_wgrad_workspace_bytes, wgrad_make_reduce_job, run_wgrad), so the three always agree
+struct WgradShape { int kh, kw, pad, cin, OH, OW, SH, SW; };
+
+static WgradShape wgrad_shape_of(const creid_conv_desc* d) {
+  return WgradShape{d->kh, d->kw, d->pad, (int)d->in_c, (int)d->out_h, (int)d->out_w, (int)d->in_h, (int)d->in_w};
+}
+
+static std::atomic<int64_t> g_taps_launches{0};
+
+static bool wgrad_taps_covers(int M, int NCO, int dtype, int stride, const WgradShape& sh) {
+  if (!creid_is16(dtype) || sh.kh != 3 || sh.kw != 3 || stride != 1 || sh.pad != 1) return false;
+  if (sh.cin != 64 && sh.cin != 128 && sh.cin != 256 && sh.cin != 512) return false;
+  if (NCO <= 0 || NCO % 64 != 0 || sh.SH != sh.OH || sh.SW != sh.OW) return false;
+  if (sh.OW != 8 && sh.OW != 16 && sh.OW != 32) return false;
+  // a k-step is TPK pixels = whole rows of ONE image
+  return (sh.OH * sh.OW) % TPK == 0 && M > 0 && M % (sh.OH * sh.OW) == 0;
+}
+
+static WgradPlan plan_wgrad_route(int M, int NCO, int K, int dtype, int stride, const WgradShape& sh) {
+  WgradPlan p = plan_wgrad(M, NCO, K, dtype, stride);      // (the registry lookup counts its hit / decline on either route)
+  const char* e = CREID_KNOB_ENV("CREID_WGRAD_TAPS");      // read per call: tests toggle it
+  if ((e && atoi(e) == 0) || !wgrad_taps_covers(M, NCO, dtype, stride, sh)) return p;
+  // One workgroup per CU (its LDS ring is > 80 KB), each writing 9 x 64 x 64 fp32 partials (147 KB) that the split reduction --
+  // carried by the next data-gradient launch -- reads back.  Measured (profiles/wgrad_taps.md): with 1 or 4 tile-groups (64 and 128
+  // channels) 256 workgroups of 4 k-steps make that launch 2-8 us slower than the tile kernel's partials did; ~170 workgroups of
+  // 6 k-steps keep the kernel's gain and leave the carrier where it was.  16 and 64 tile-groups: one workgroup per CU.
+  p.taps = 1; p.tm = 64; p.tn = 64; p.stages = 3; p.ws = 0; p.kg = 0; p.xcd = 1;
+  p.tiles_k = sh.cin / 64;
+  p.tiles = (NCO / 64) * p.tiles_k;
+  const int steps = M / TPK;
+  // CREID_WGRAD_TAPS_WGS: the workgroup target, for experiments and for tests that need many k-steps per workgroup at small shapes
+  const char* we = CREID_KNOB_ENV("CREID_WGRAD_TAPS_WGS");
+  const int target = (we && atoi(we) > 0) ? atoi(we) : (p.tiles <= 4 ? 192 : 256);
+  int splits = (target + p.tiles / 2) / p.tiles;
+  if (splits > steps) splits = steps;
+  if (splits < 1) splits = 1;
+  const int per = (steps + splits - 1) / splits;
+  p.m_per_split = per * TPK;
+  p.splits = (steps + per - 1) / per;
+  return p;
+}
+
+// returns true when the launch carried the BatchNorm-backward finalize job (always, when one is given: the grid is 1-D)
+static bool launch_wgrad_taps(const IGemmGeom& g, const void* dy, const void* x, int NCO, float* ws, const WgradPlan& p, int dtype,
+                              hipStream_t s, const BnBwdFinJob* fin_in) {
+  BnBwdFinJob fin{};
+  if (fin_in) fin = *fin_in;
+  const unsigned nf8 = fin.partial ? (unsigned)((fin.nblocks + 7) & ~7) : 0u;
+  const bool ranged = p.splits >= 8 || (8 % p.splits) != 0;
+  const int share = ranged ? 1 : 8 / p.splits;
+  const unsigned nwg = ranged ? (unsigned)(p.tiles * ((p.splits + 7) / 8) * 8) : (unsigned)(8 * ((p.tiles + share - 1) / share));
+  const int cin = 1 << g.log2span;
+#define CREID_WT_LAUNCH(OW_, ET_)                                                                                          \
+  hipLaunchKernelGGL((wgrad_bf16_taps_kernel<OW_, ET_>), dim3(nwg + nf8), dim3(512), 0, s, (const unsigned short*)dy,      \
+                     (const unsigned short*)x, g.M, g.OH, cin, NCO, ws, p.tiles, p.tiles_k, p.splits, p.m_per_split, fin)
+#define CREID_WT_OW(OW_) do { if (dtype == CREID_F16) CREID_WT_LAUNCH(OW_, F16T); else CREID_WT_LAUNCH(OW_, Bf16T); } while (0)
+  if (g.OW == 8) CREID_WT_OW(8); else if (g.OW == 16) CREID_WT_OW(16); else CREID_WT_OW(32);
+#undef CREID_WT_OW
+#undef CREID_WT_LAUNCH
+  g_taps_launches.fetch_add(1, std::memory_order_relaxed);
+  return fin.partial != nullptr;
 }
 
 __global__ __launch_bounds__(256) void bn_bwd_finalize_job_kernel(BnBwdFinJob j) {
@@ -969,8 +1254,10 @@ static int run_wgrad(const IGemmGeom& g, const void* dy, const void* x, int NCO,
     static const int dma_on = [] { const char* e = getenv("CREID_WGRAD_DMA"); return e ? atoi(e) : 1; }();
     if (!dma_on) return CREID_E_DTYPE;
   }
-  const WgradPlan p = plan_wgrad(g.M, NCO, g.K, dtype, g.stride);
-  if (dtype == CREID_F16 && (phases & 1)) {
+  // (the tap-fused route needs the plain NHWC gather: the stem's packed kernel rows and pre-padded image stay on the tile kernels)
+  const WgradShape shp{(cpitch == cin && kw_taps == kw && g.check_bounds && (1 << g.log2span) == cin) ? kh : 0, kw, g.pad, cin, g.OH, g.OW, g.SH, g.SW};
+  const WgradPlan p = plan_wgrad_route(g.M, NCO, g.K, dtype, g.stride, shp);
+  if (dtype == CREID_F16 && (phases & 1) && !p.taps) {
     // (the same predicate launch_wgrad_t routes by, CREID_STEM_DMA included: with the stem's DMA path switched off an f16 stem has
     // no kernel at all -- refuse it here instead of summing an unwritten workspace into dw)
     static const int stem_dma = [] { const char* e = getenv("CREID_STEM_DMA"); return e ? atoi(e) : 1; }();
@@ -981,7 +1268,8 @@ static int run_wgrad(const IGemmGeom& g, const void* dy, const void* x, int NCO,
   if (ws_bytes < need) return CREID_E_WS;
   if (phases & 1) {
     bool carried;
-    if (p.tm == 128 && p.tn == 128) carried = launch_wgrad_t<128, 128>(g, dy, x, NCO, (float*)ws, p, dtype, s, fin);
+    if (p.taps) carried = launch_wgrad_taps(g, dy, x, NCO, (float*)ws, p, dtype, s, fin);
+    else if (p.tm == 128 && p.tn == 128) carried = launch_wgrad_t<128, 128>(g, dy, x, NCO, (float*)ws, p, dtype, s, fin);
     else if (p.tm == 128 && p.tn == 64) carried = launch_wgrad_t<128, 64>(g, dy, x, NCO, (float*)ws, p, dtype, s, fin);
     else if (p.tm == 64 && p.tn == 128) carried = launch_wgrad_t<64, 128>(g, dy, x, NCO, (float*)ws, p, dtype, s, fin);
     else carried = launch_wgrad_t<64, 64>(g, dy, x, NCO, (float*)ws, p, dtype, s, fin);
@@ -1023,7 +1311,7 @@ bool wgrad_make_reduce_job(const creid_conv_desc* d, int dtype, const void* ws, 
                            WRedJob& j) {
   if (!d || !ws || !dw) return false;
   const int M = (int)(d->batch * d->out_h * d->out_w), K = (int)(d->kh * d->kw * d->in_c), NCO = (int)d->out_c;
-  const WgradPlan p = plan_wgrad(M, NCO, K, dtype, d->stride);
+  const WgradPlan p = plan_wgrad_route(M, NCO, K, dtype, d->stride, wgrad_shape_of(d));
   if (ws_bytes < (size_t)p.splits * NCO * K * sizeof(float)) return false;
   const bool ok = wred_make_job(j, (const float*)ws, dw, p.splits, NCO, K, (int)d->in_c, d->kh, d->kw, accumulate);
   // timing experiments only: the carrier workgroups are launched but do nothing (gradients are then WRONG)
@@ -1037,12 +1325,14 @@ extern "C" {
 size_t creid_conv2d_wgrad_workspace_bytes(const creid_conv_desc* d, int dtype) {
   if (!d) return 0;
   const int M = (int)(d->batch * d->out_h * d->out_w), K = (int)(d->kh * d->kw * d->in_c);
-  const WgradPlan p = plan_wgrad(M, (int)d->out_c, K, dtype, d->stride);
+  const WgradPlan p = plan_wgrad_route(M, (int)d->out_c, K, dtype, d->stride, wgrad_shape_of(d));
   return (size_t)p.splits * d->out_c * K * sizeof(float);
 }
 
 static int conv_wgrad_phases(const creid_conv_desc* d, const void* x, const void* dy, float* dw_oihw, int accumulate,
                              void* ws, size_t ws_bytes, int dtype, void* stream, int phases, const BnBwdFinJob* fin = nullptr);
+
+int64_t creid_wgrad_taps_launches(void) { return (int64_t)g_taps_launches.load(std::memory_order_relaxed); }
 
 int creid_conv2d_wgrad_nhwc(const creid_conv_desc* d, const void* x, const void* dy, float* dw_oihw, int accumulate,
                             void* ws, size_t ws_bytes, int dtype, void* stream) {

@@ -511,6 +511,11 @@ int64_t creid_conv2d_bn_partial_rows(const creid_conv_desc* d);
 /* Launches so far (this process) of the resident-halo form of the producer/consumer kernel: stride-1 3x3 forward / data
  * gradient, 64 | 128 | 256 channels, 128-row tiles of whole image rows; CREID_IGEMM_HALO=0 turns it off.  Same bits either way. */
 int64_t creid_igemm_halo_launches(void);
+/* Launches so far (this process) of the tap-fused weight-gradient kernel (wgrad_bf16_taps_kernel): 16-bit stride-1 pad-1 3x3
+ * layers with in_c in {64, 128, 256, 512}, out_c % 64 == 0, out_w in {8, 16, 32} and out_h * out_w % 128 == 0 -- one workgroup
+ * per (64 co x 64 ci x nine taps) over its pixel range.  CREID_WGRAD_TAPS=0 (read per call) restores the per-tap tile launches
+ * with their split counts and workspace sizes. */
+int64_t creid_wgrad_taps_launches(void);
 int creid_conv2d_fwd_nhwc(const creid_conv_desc* d, const void* x, const void* w_krsc, void* y,
                           float* bn_partial, int dtype, void* stream);
 /* Eval-mode forward of conv -> BatchNorm -> (+ residual) -> (ReLU) in ONE launch (modelling/backbones/resnet.py:67-87 under
