@@ -23,7 +23,9 @@
 // What happens to a finished accumulator tile -- both epilogues, the LDS state they read, the histogram flush -- and the tail of
 // the positives kernel do not depend on the feature type: stream_consume.hpp, shared with stream_h16.hip (bf16 / f16 features on
 // the 16-bit MFMA).  The work split, a workgroup's run of it and the entry points' argument tests: stream_common.hpp.  This file
-// keeps what is fp32: the operand staging and LDS image, the k-loop on the f32 MFMA, and the fmaf chain of the positives.
+// keeps what is fp32: the operand staging and LDS image, the k-loop on the f32 MFMA, and the positives' use of the fmaf chain
+// (stream_chain.hpp, shared with the re-score of stream_prefilter.hip).
+#include "stream_chain.hpp"
 #include "stream_consume.hpp"
 #include "topk_tail.hpp"
 
@@ -87,31 +89,7 @@ __global__ __launch_bounds__(PL_MAXC) void stream_poslist_kernel(
   if (tid < nc) {
     const int gi = cand[tid];
     const float* __restrict__ grow = g + (int64_t)gi * D;
-    float acc = 0.f;
-    int k = 0;
-    const int kend = D & ~15;
-    // two 64-byte blocks of the row are in flight while a third is chained (the loop is bound by the load round trip
-    // to the Infinity Cache, not by the 16 dependent FMAs of a block)
-    float4 n0, n1, n2, n3, m0, m1, m2, m3;
-    if (kend > 0) {
-      n0 = *reinterpret_cast<const float4*>(grow); n1 = *reinterpret_cast<const float4*>(grow + 4);
-      n2 = *reinterpret_cast<const float4*>(grow + 8); n3 = *reinterpret_cast<const float4*>(grow + 12);
-      const int k1 = min(16, kend - 16);
-      m0 = *reinterpret_cast<const float4*>(grow + k1); m1 = *reinterpret_cast<const float4*>(grow + k1 + 4);
-      m2 = *reinterpret_cast<const float4*>(grow + k1 + 8); m3 = *reinterpret_cast<const float4*>(grow + k1 + 12);
-    }
-    for (; k < kend; k += 16) {                            // the MFMA's own k order: one sequential fmaf chain
-      const float4 v0 = n0, v1 = n1, v2 = n2, v3 = n3;
-      n0 = m0; n1 = m1; n2 = m2; n3 = m3;
-      const int kn = min(k + 32, kend - 16);
-      m0 = *reinterpret_cast<const float4*>(grow + kn); m1 = *reinterpret_cast<const float4*>(grow + kn + 4);
-      m2 = *reinterpret_cast<const float4*>(grow + kn + 8); m3 = *reinterpret_cast<const float4*>(grow + kn + 12);
-      acc = fmaf(qrow[k + 0], v0.x, acc); acc = fmaf(qrow[k + 1], v0.y, acc); acc = fmaf(qrow[k + 2], v0.z, acc); acc = fmaf(qrow[k + 3], v0.w, acc);
-      acc = fmaf(qrow[k + 4], v1.x, acc); acc = fmaf(qrow[k + 5], v1.y, acc); acc = fmaf(qrow[k + 6], v1.z, acc); acc = fmaf(qrow[k + 7], v1.w, acc);
-      acc = fmaf(qrow[k + 8], v2.x, acc); acc = fmaf(qrow[k + 9], v2.y, acc); acc = fmaf(qrow[k + 10], v2.z, acc); acc = fmaf(qrow[k + 11], v2.w, acc);
-      acc = fmaf(qrow[k + 12], v3.x, acc); acc = fmaf(qrow[k + 13], v3.y, acc); acc = fmaf(qrow[k + 14], v3.z, acc); acc = fmaf(qrow[k + 15], v3.w, acc);
-    }
-    for (; k < D; ++k) acc = fmaf(qrow[k], grow[k], acc);
+    STREAM_FMAF_CHAIN(acc, qrow, grow, D);                 // the MFMA's own k order: one sequential fmaf chain
     skey[tid] = mono_key(fmaf(-2.0f, acc, qq[qi] + gg[gi]));                          // sqdist epilogue, same bits
   }
   __syncthreads();

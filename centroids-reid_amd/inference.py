@@ -169,7 +169,8 @@ def _select_rows(distmat, topk):
 
 
 def get_similar(embeddings, paths, embeddings_gallery, paths_gallery, topk=0, normalize_features=True,
-                distance_func="euclidean", streamed="auto", stats=None, compute_dtype=torch.float32, reranking=False):
+                distance_func="euclidean", streamed="auto", stats=None, compute_dtype=torch.float32, reranking=False,
+                prefilter=None):
     """inference/get_similar.py:99-125 -> {query_path: {"indices", "paths", "distances"}} (numpy arrays).
 
     streamed: False -- the m x n distance matrix is written and every row selected from it (get_dist_func + topk_rows /
@@ -183,14 +184,23 @@ def get_similar(embeddings, paths, embeddings_gallery, paths_gallery, topk=0, no
     reranking: True (the defaults of reid_metric.re_ranking) or a dict of k1 / k2 / lambda_value -- the k-reciprocal re-ranked
     matrix is ranked in place of the distance matrix and the returned "distances" are its values; always the materialised path
     (CreidError with streamed=True, a 16-bit compute_dtype or the cosine distance).
-    stats (a dict) receives "path" ("materialised" | "streamed" | "chunked" | "reranked"), topk_stream's counters and
-    re_ranking's statistics."""
+    prefilter: torch.bfloat16 or torch.float16 -- reid_metric.topk_stream(prefilter=...): the fp32 result, bit for bit, with the
+    contraction on the 16-bit MFMA.  "auto" then streams whenever the call is streamable (squared L2, 1 <= k <= 1024), whatever
+    the matrix size; CreidError with streamed=False, a 16-bit compute_dtype, reranking, or a call that cannot stream.
+    stats (a dict) receives "path" ("materialised" | "streamed" | "chunked" | "reranked"), topk_stream's counters ("prefilter"
+    among them: what ran) and re_ranking's statistics."""
     rr = rm.rerank_options(reranking)
     if rr is not None and (streamed is True or compute_dtype != torch.float32 or distance_func != "euclidean"):
         raise L.CreidError("get_similar(reranking=...) re-ranks the materialised squared-L2 fp32 matrix: not with streamed=True, "
                            f"compute_dtype={compute_dtype} or distance_func={distance_func!r}")
     if streamed not in (True, False, "auto"):
         raise ValueError(f"streamed must be True, False or 'auto', got {streamed!r}")
+    if prefilter is not None:
+        if prefilter not in (torch.bfloat16, torch.float16):
+            raise L.CreidError(f"get_similar: prefilter must be torch.bfloat16, torch.float16 or None, got {prefilter}")
+        if streamed is False or compute_dtype != torch.float32 or rr is not None:
+            raise L.CreidError("get_similar(prefilter=...) pre-filters the streamed fp32 top-k: not with streamed=False, "
+                               f"compute_dtype={compute_dtype} or reranking")
     if compute_dtype not in (torch.float32, torch.bfloat16, torch.float16):
         raise L.CreidError(f"get_similar: compute_dtype must be torch.float32, torch.bfloat16 or torch.float16, got {compute_dtype}")
     q = torch.as_tensor(np.asarray(embeddings, np.float32)).cuda() if not isinstance(embeddings, torch.Tensor) else embeddings.float().cuda()
@@ -205,16 +215,17 @@ def get_similar(embeddings, paths, embeddings_gallery, paths_gallery, topk=0, no
     m, n = q.shape[0], g.shape[0]
     k = min(int(topk), n) if topk else 0
     streamable = distance_func == "euclidean" and 1 <= k <= 1024
-    if streamed is True and not streamable:
-        raise L.CreidError("get_similar(streamed=True) is squared-L2 top-k retrieval with 1 <= k <= 1024: "
-                           f"got distance_func={distance_func!r}, topk={topk}")
+    if (streamed is True or prefilter is not None) and not streamable:
+        raise L.CreidError("get_similar(streamed=True) and get_similar(prefilter=...) are squared-L2 top-k retrieval with "
+                           f"1 <= k <= 1024: got distance_func={distance_func!r}, topk={topk}")
     big = m * n * 4 > STREAM_MATRIX_BYTES
     info = {}
     if rr is not None:
         idx, dist_sel = _select_rows(rm.re_ranking(q, g, **rr, stats=info), topk)
         info["path"] = "reranked"
-    elif streamed is True or (streamed == "auto" and big and streamable and rm.topk_stream_sample(k, n) <= n // 4):
-        indices, dist_sel = rm.topk_stream(q, g, k, stats=info)
+    elif streamed is True or prefilter is not None or (streamed == "auto" and big and streamable and
+                                                       rm.topk_stream_sample(k, n) <= n // 4):
+        indices, dist_sel = rm.topk_stream(q, g, k, stats=info, prefilter=prefilter)
         idx, dist_sel = indices.cpu().numpy(), dist_sel.cpu().numpy()
         info["path"] = "streamed"
     elif streamed == "auto" and big:

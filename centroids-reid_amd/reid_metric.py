@@ -148,7 +148,8 @@ def topk_stream_sample(k: int, n: int) -> int:
     return max(k, min(n, max(-(-k * n // 1024), 1024)))
 
 
-def topk_stream(q: torch.Tensor, g: torch.Tensor, k: int, qq=None, gg=None, *, sample=None, capacity=None, stats=None):
+def topk_stream(q: torch.Tensor, g: torch.Tensor, k: int, qq=None, gg=None, *, sample=None, capacity=None, stats=None,
+                prefilter=None, g_pack=None):
     """topk_rows(get_euclidean(q, g, qq, gg), k) -- (indices int64 [m, k], squared-L2 distances fp32 [m, k]), the same indices
     and the same distance bits, ties by gallery index -- WITHOUT the m x n matrix (fp32, bf16 or f16 features, q and g of one
     dtype, k <= min(n, 1024); 16-bit features run the contraction on the 16-bit MFMA and the threshold sample, the repair and
@@ -160,18 +161,28 @@ def topk_stream(q: torch.Tensor, g: torch.Tensor, k: int, qq=None, gg=None, *, s
          row's candidate list (`capacity` slots);
       3. creid_stream_topk_select: sorts each list by (distance, index) and keeps the first k.
     Rows whose list overflowed (a loose threshold, massive ties) are flagged and redone through get_euclidean + topk_rows in
-    bounded row chunks.  `stats` (a dict) receives sample, capacity, fallback_rows and max_candidates."""
+    bounded row chunks.  `stats` (a dict) receives sample, capacity, fallback_rows and max_candidates.
+    prefilter = torch.bfloat16 | torch.float16 (fp32 q and g only; default None: everything above, untouched): the SAME result --
+    the indices and distance bits of the fp32 path -- with the contraction on the 16-bit MFMA: see _topk_stream_prefilter.
+    g_pack = prefilter_pack(g, prefilter) spares a gallery that is searched many times its rounding pass."""
     if q.dtype != g.dtype:
         raise L.CreidError(f"topk_stream needs q and g of one dtype (fp32, bf16 or f16), got {q.dtype} and {g.dtype}")
     L.require_gpu(q, g, qq, gg)
     if q.dtype not in (torch.float32,) + _H16 or q.dim() != 2 or g.dim() != 2 or q.shape[1] != g.shape[1]:
         raise L.CreidError("topk_stream needs [m, D] and [n, D] features of one dtype: fp32, bf16 or f16")
     h16 = q.dtype in _H16
+    if prefilter is None and g_pack is not None:
+        raise L.CreidError("topk_stream: g_pack needs prefilter=torch.bfloat16 or torch.float16")
+    if prefilter is not None and (prefilter not in _H16 or q.dtype != torch.float32):
+        raise L.CreidError(f"topk_stream: prefilter must be torch.bfloat16 or torch.float16 on fp32 features, got {prefilter} on "
+                           f"{q.dtype}")
     m, n, k = q.shape[0], g.shape[0], int(k)
     cap = STREAM_TOPK_CAPACITY if capacity is None else int(capacity)
     if not 1 <= k <= min(n, 1024, cap):
         raise L.CreidError(f"topk_stream: k = {k} outside 1 .. min(n = {n}, 1024, capacity = {cap})")
     S = topk_stream_sample(k, n) if sample is None else max(k, min(n, int(sample)))
+    if prefilter is not None:
+        return _topk_stream_prefilter(q, g, k, qq, gg, prefilter, g_pack, S, cap, stats)
     qq = row_sqnorm(q) if qq is None else qq
     gg = row_sqnorm(g) if gg is None else gg
     q, g = _pad_width(q, 8 if h16 else 4), _pad_width(g, 8 if h16 else 4)
@@ -198,16 +209,180 @@ def topk_stream(q: torch.Tensor, g: torch.Tensor, k: int, qq=None, gg=None, *, s
         L.check(lib.creid_stream_topk_select(L.ptr(cand), L.ptr(count[r0:r1]), r1 - r0, cap, k, L.ptr(idx[r0:r1]),
                                              L.ptr(dsel[r0:r1]), L.ptr(flags[r0:r1]), st), "creid_stream_topk_select")
         del tau, cand
-    bad = torch.nonzero(flags).flatten()
-    if bad.numel():                                         # overflowed lists (or NaN rows): the materialised kernels, row chunks
-        rows = max(1, _STREAM_TOPK_CHUNK_BYTES // (n * 4))
-        for b0 in range(0, bad.numel(), rows):
-            sel = bad[b0:b0 + rows]
-            ridx, rd = topk_rows(get_euclidean(q.index_select(0, sel), g, qq.index_select(0, sel), gg), k)
-            idx.index_copy_(0, sel, ridx)
-            dsel.index_copy_(0, sel, rd)
+    bad = _topk_stream_repair(q, g, k, qq, gg, flags, idx, dsel)
     if stats is not None:
-        stats.update(sample=S, capacity=cap, fallback_rows=int(bad.numel()), max_candidates=int(count.max().item()) if m else 0)
+        stats.update(sample=S, capacity=cap, fallback_rows=bad, max_candidates=int(count.max().item()) if m else 0)
+    return idx, dsel
+
+
+def _topk_stream_repair(q, g, k, qq, gg, flags, idx, dsel) -> int:
+    """The flagged rows of topk_stream (overflowed lists, NaN rows; with a pre-filter also rows that keep too many entries) redone
+    through the materialised kernels in bounded row chunks, into idx / dsel; returns their number."""
+    bad = torch.nonzero(flags).flatten()
+    rows = max(1, _STREAM_TOPK_CHUNK_BYTES // (g.shape[0] * 4))
+    for b0 in range(0, bad.numel(), rows):
+        sel = bad[b0:b0 + rows]
+        ridx, rd = topk_rows(get_euclidean(q.index_select(0, sel), g, qq.index_select(0, sel), gg), k)
+        idx.index_copy_(0, sel, ridx)
+        dsel.index_copy_(0, sel, rd)
+    return int(bad.numel())
+
+
+STREAM_RESCORE_CAPACITY = 1024        # entries of one query creid_stream_topk_rescore re-scores (RS_CAP, csrc/stream_prefilter.hip)
+_PREFILTER_INFLATE = 2.0 ** -20       # relative inflation of the margin: covers the float64 arithmetic it is computed with
+
+
+class PrefilterPack:
+    """prefilter_pack's result: `rounded` [r, D8] (the rows rounded once to `dtype`, the width zero-padded to a multiple of 8),
+    `stats` float64 [r, 3] = per row |x - xh|^2, |xh|^2, |x|^2, and the `width` of the fp32 rows it was made from."""
+
+    def __init__(self, rounded, stats, width):
+        self.rounded, self.stats, self.width, self._maxima = rounded, stats, width, None
+
+    @property
+    def dtype(self):
+        return self.rounded.dtype
+
+    def maxima(self):
+        """The gallery side of prefilter_margin: the column maxima of `stats` as three Python floats (NaN / inf when a row's
+        statistics are not finite); one device read, cached."""
+        if self._maxima is None:
+            self._maxima = tuple(self.stats.amax(dim=0).tolist()) if self.stats.shape[0] else (0.0, 0.0, 0.0)
+        return self._maxima
+
+
+def prefilter_pack(x: torch.Tensor, dtype) -> PrefilterPack:
+    """One pass over fp32 rows [r, D] (creid_prefilter_pack): the bf16 / f16 copy -- the bits of x.to(dtype) -- and the per-row sums
+    the margin of topk_stream(prefilter=dtype) is computed from, accumulated in double."""
+    L.require_gpu(x)
+    if dtype not in _H16 or x.dtype != torch.float32 or x.dim() != 2:
+        raise L.CreidError(f"prefilter_pack needs fp32 [r, D] rows and torch.bfloat16 or torch.float16, got {x.dtype} and {dtype}")
+    width = x.shape[1]
+    x = _pad_width(x, 8)
+    r, D = x.shape
+    y = torch.empty((r, D), dtype=dtype, device=x.device)
+    st = torch.empty((r, 3), dtype=torch.float64, device=x.device)
+    L.check(L.lib().creid_prefilter_pack(L.ptr(x), r, D, L._DT[dtype], L.ptr(y), L.ptr(st), L.stream()), "creid_prefilter_pack")
+    return PrefilterPack(y, st, width)
+
+
+def prefilter_margin(e2, h2, x2, g_e2, g_h2, g_x2, g_sq, D, parts=False):
+    """m_i with |dh_ij - d_ij| <= m_i for every gallery row j, where d is the fp32 distance kernels' value on rows (q_i, g_j) and
+    dh the 16-bit kernels' value on the rows rounded once to bf16 / f16 (qh, gh), both with the SAME norm arguments qq_i, gg_j.
+    A pure function (numpy arrays, tensors or floats; float64 expected):
+      e2, h2, x2        per query row |q - qh|^2, |qh|^2, |q|^2 (the columns of PrefilterPack.stats); x2 also stands for |qq_i|;
+      g_e2, g_h2, g_x2  the gallery's maxima of the same three sums;  g_sq >= every |gg_j|;  D the feature width.
+    With e = sqrt(e2), Qh = sqrt(h2), Q = sqrt(x2), E, Gh, G the gallery's, u = 2^-24:
+      data       = 2 (e G + Qh E)            the exact effect of rounding the operands: |q.g - qh.gh| <= |q - qh||g| + |qh||g - gh|
+                                             (Cauchy-Schwarz), doubled by the epilogue's -2;
+      arithmetic = 2 D u (Qh Gh + Q G)       the two accumulators: the rule 2 D u sum |q_k||g_k| of tests/eval_exact.py per kernel
+                 + 2 u (x2 + g_sq)           the rounding of qq + gg, once per kernel
+                 + u (x2 + g_sq + 2 Q G) + u (x2 + g_sq + 2 Qh Gh)      the final fma of either kernel, u |d|.
+    The data part comes from the rows themselves, so f16 subnormals, underflow to zero and un-normalised features are covered;
+    non-finite statistics give a non-finite margin.  Every term is non-negative and non-decreasing in every argument.
+    parts=True returns (data, arithmetic) instead of their sum."""
+    def sqrt(v):
+        return torch.sqrt(v) if isinstance(v, torch.Tensor) else np.sqrt(v)
+    u = 2.0 ** -24
+    e, Qh, Q = sqrt(e2), sqrt(h2), sqrt(x2)
+    E, Gh, G = sqrt(g_e2), sqrt(g_h2), sqrt(g_x2)
+    data = 2.0 * (e * G + Qh * E)
+    arith = 2.0 * D * u * (Qh * Gh + Q * G) + 2.0 * u * (x2 + g_sq) + u * (x2 + g_sq + 2.0 * Q * G) + u * (x2 + g_sq + 2.0 * Qh * Gh)
+    return (data, arith) if parts else data + arith
+
+
+def _round_up_f32(x64: torch.Tensor) -> torch.Tensor:
+    """fp32 values never below the float64 ones (inf and NaN stay)."""
+    f = x64.to(torch.float32)
+    return torch.where(f.double() < x64, torch.nextafter(f, torch.full_like(f, float("inf"))), f)
+
+
+def _topk_stream_prefilter(q, g, k, qq, gg, dtype, g_pack, S, cap, stats):
+    """topk_stream on fp32 features with the contraction on the 16-bit MFMA and the result of the fp32 path, bit for bit.
+    d: the fp32 distance; dh: the 16-bit streamed kernel's distance on the rows rounded once to `dtype`, given the fp32 rows' own
+    qq / gg, so that only the dot product differs; m_i = prefilter_margin >= |dh - d| over row i.
+      1. the k pairs of smallest dh have d <= dh_(k) + m_i, so the true k-th distance d_(k) <= dh_(k) + m_i;
+      2. every pair of the true top-k, those tied at d_(k) included, has d <= d_(k), hence dh <= dh_(k) + 2 m_i;
+      3. the pairs within that cut, re-scored with the fp32 bits and sorted by (d, j), give exactly the fp32 result.
+    Stages, in the bounded row chunks of the fp32 path: creid_prefilter_pack of the query chunk (the gallery's once, or the
+    caller's g_pack); tau_i = the k-th smallest dh over the strided gallery sample through the materialised 16-bit kernel with the
+    same norms (same bits as the streamed one, so tau_i >= dh_(k)); creid_stream_topk_collect_h16 with the threshold
+    tau_i + 2 m_i; creid_stream_topk_rescore, which finds dh_(k) in the list, keeps dh <= dh_(k) + 2 m_i and re-scores.
+    Roundings between the statistics and the two thresholds: the statistics are double sums of exact terms (relative error below
+    (D + 6) 2^-53) and prefilter_margin is a few dozen float64 operations on non-negative terms -- together far below the stated
+    inflation 1 + 2^-20; 2 m_i is then rounded UP to fp32 (margin2); the collect threshold is the fp32 sum tau_i + margin2_i moved
+    one step up, the kernel's cut the fp32 sum dh_(k) + margin2_i moved one step up: neither is below the real sum.
+    Rows the kernel flags (list overflow, fewer than k entries, more than STREAM_RESCORE_CAPACITY kept, a margin that is not
+    finite) are redone through get_euclidean + topk_rows on the fp32 tensors like the fp32 path's; a gallery whose statistics are
+    not finite (f16 overflow, Inf / NaN) sends the whole call down the fp32 path (stats["prefilter"] is then None).
+    stats receives sample, capacity, fallback_rows, max_candidates, prefilter (what ran), max_rescored (the most entries a row
+    kept), rescore_capacity, margin_max, kept (int32 [m] on the device: entries kept per row) and -- when it comes in holding
+    timing=True -- stage_ms (pack_g, pack_q, sample, collect, rescore, repair, between device events)."""
+    m, n = q.shape[0], g.shape[0]
+    width = g.shape[1]
+    clock = _StageClock(bool(stats) and bool(stats.get("timing")))
+    qq = row_sqnorm(q) if qq is None else qq
+    gg = row_sqnorm(g) if gg is None else gg
+    if g_pack is None:
+        g_pack = prefilter_pack(g, dtype)
+    elif not isinstance(g_pack, PrefilterPack) or g_pack.dtype != dtype or g_pack.rounded.shape[0] != n or g_pack.width != width:
+        raise L.CreidError(f"topk_stream: g_pack is not prefilter_pack(g, {dtype}) of this [{n}, {width}] gallery")
+    g_e2, g_h2, g_x2 = g_pack.maxima()
+    g_sq = max(g_x2, float(gg.abs().amax().item()))
+    if not all(np.isfinite(v) for v in (g_e2, g_h2, g_x2, g_sq)):
+        info = {}
+        out = topk_stream(q, g, k, qq, gg, sample=S, capacity=cap, stats=info)
+        if stats is not None:
+            stats.update(info, prefilter=None, max_rescored=0, rescore_capacity=STREAM_RESCORE_CAPACITY, margin_max=float("inf"))
+        return out
+    q, g = _pad_width(q, 8), _pad_width(g, 8)       # zero columns change neither a norm, a rounding nor an fmaf chain
+    gh = g_pack.rounded
+    D, dev, lib, st = q.shape[1], q.device, L.lib(), L.stream()
+    dt = L._DT[dtype]
+    clock.mark("pack_g")
+    stride = n // S
+    ghs, ggs = gh[::stride][:S].contiguous(), gg[::stride][:S].contiguous()
+    idx = torch.empty((m, k), dtype=torch.int64, device=dev)
+    dsel = torch.empty((m, k), dtype=torch.float32, device=dev)
+    flags = torch.zeros(m, dtype=torch.uint8, device=dev)
+    count = torch.zeros(m, dtype=torch.int32, device=dev)
+    kept = torch.zeros(m, dtype=torch.int32, device=dev)
+    margin = torch.empty(m, dtype=torch.float64, device=dev)
+    up = torch.tensor(float("inf"), dtype=torch.float32, device=dev)
+    step = max(64, _STREAM_TOPK_CHUNK_BYTES // (max(cap * 8, S * 4)) // 64 * 64)
+    for r0 in range(0, m, step):
+        r1 = min(m, r0 + step)
+        qc, qqc = q[r0:r1], qq[r0:r1]
+        qp = prefilter_pack(qc, dtype)
+        x2 = torch.maximum(qp.stats[:, 2], qqc.abs().double())
+        mc = prefilter_margin(qp.stats[:, 0], qp.stats[:, 1], x2, g_e2, g_h2, g_x2, g_sq, D)
+        margin[r0:r1] = mc
+        margin2 = _round_up_f32(2.0 * (1.0 + _PREFILTER_INFLATE) * mc)
+        clock.mark("pack_q")
+        tau = topk_rows(get_euclidean(qp.rounded, ghs, qqc, ggs), k)[1][:, k - 1]
+        thr = torch.nextafter(tau + margin2, up.expand_as(tau)).contiguous()
+        cand = torch.empty((r1 - r0, cap), dtype=torch.int64, device=dev)
+        clock.mark("sample")
+        L.check(lib.creid_stream_topk_collect_h16(L.ptr(qp.rounded), L.ptr(gh), L.ptr(qqc), L.ptr(gg), r1 - r0, n, D, dt, L.ptr(thr),
+                                                  cap, L.ptr(cand), L.ptr(count[r0:r1]), st), "creid_stream_topk_collect_h16")
+        clock.mark("collect")
+        L.check(lib.creid_stream_topk_rescore(L.ptr(cand), L.ptr(count[r0:r1]), r1 - r0, cap, k, L.ptr(qc), L.ptr(g), L.ptr(qqc),
+                                              L.ptr(gg), n, D, L.ptr(margin2), L.ptr(idx[r0:r1]), L.ptr(dsel[r0:r1]),
+                                              L.ptr(flags[r0:r1]), L.ptr(kept[r0:r1]), st), "creid_stream_topk_rescore")
+        clock.mark("rescore")
+        del qp, tau, thr, cand, margin2
+    bad = _topk_stream_repair(q, g, k, qq, gg, flags, idx, dsel)      # the fp32 path's repair, on the fp32 tensors
+    clock.mark("repair")
+    if stats is not None:
+        if clock.on:                                        # per stage, summed over the row chunks
+            stage_ms = {}
+            clock.marks[-1][1].synchronize()
+            for (_, prev), (name, ev) in zip(clock.marks, clock.marks[1:]):
+                stage_ms[name] = stage_ms.get(name, 0.0) + prev.elapsed_time(ev)
+            stats["stage_ms"] = stage_ms
+        stats.update(sample=S, capacity=cap, fallback_rows=bad, max_candidates=int(count.max().item()) if m else 0,
+                     prefilter=dtype, max_rescored=int(kept.max().item()) if m else 0, rescore_capacity=STREAM_RESCORE_CAPACITY,
+                     margin_max=float(margin.max().item()) if m else 0.0, kept=kept)
     return idx, dsel
 
 
@@ -260,7 +435,7 @@ class _StageClock:
 
 
 def re_ranking(q: torch.Tensor, g: torch.Tensor, k1: int = 20, k2: int = 6, lambda_value: float = 0.3, *, stats=None,
-               debug=None) -> torch.Tensor:
+               debug=None, prefilter=None) -> torch.Tensor:
     """k-reciprocal re-ranking (Zhong et al., CVPR 2017) of fp32 device features q [nq, D], g [ng, D]: the fp32 [nq, ng]
     matrix (1 - lambda) * Jaccard + lambda * d / max_row(d), to be ranked like a distance matrix -- with no N x N matrix
     (N = nq + ng) at any point: the only [nq, ng] tensors are the result and get_euclidean(q, g).
@@ -274,6 +449,8 @@ def re_ranking(q: torch.Tensor, g: torch.Tensor, k1: int = 20, k2: int = 6, lamb
       4. creid_rerank_expand (k2 > 1): V'(i) = mean of V over N_{k2}(i);
       5. creid_rerank_blend: J(i, j) = 1 - s / (2 - s), s = sum_c min(V'(i, c), V'(j, c)); pairs that share no column keep J = 1.
     The result does not depend on launch order: two calls return the same bits.
+    prefilter = torch.bfloat16 | torch.float16 goes to the neighbour search of stage 1 only (topk_stream(prefilter=...): the same
+    neighbour table with the contraction on the 16-bit MFMA), so the result keeps its bits.
     Limits (CreidError): CPU tensors; k1 + 1 > min(N, 1024); k2 < 1 or k2 > k1 + 1; lambda outside [0, 1]; and rows that do not
     fit the kernels' LDS (a worst-case R* row of (k1 + 1)(kh + 2) entries: k1 <= 125; the k2 merged rows of one V' row: 4096
     entries; D <= 16380).
@@ -308,7 +485,9 @@ def re_ranking(q: torch.Tensor, g: torch.Tensor, k1: int = 20, k2: int = 6, lamb
     xx = row_sqnorm(X)
     temp = {}
     # 1. neighbours and row maxima
-    nb, _ = topk_stream(X, X, K, xx, xx)
+    if prefilter is not None and prefilter not in _H16:
+        raise L.CreidError(f"re_ranking: prefilter must be torch.bfloat16, torch.float16 or None, got {prefilter}")
+    nb, _ = topk_stream(X, X, K, xx, xx, prefilter=prefilter)
     del _
     clock.mark("neighbours")
     rowmax = torch.empty(N, dtype=torch.float32, device=dev)

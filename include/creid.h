@@ -188,6 +188,31 @@ int creid_stream_topk_collect_h16(const void* q, const void* g, const float* qq,
                                   int64_t D, int dtype, const float* tau, int32_t cap, uint64_t* cand, int32_t* count,
                                   void* stream);
 
+/* ---- exact fp32 top-k with the contraction on the 16-bit MFMA (csrc/stream_prefilter.hip): the 16-bit streamed contraction
+ * only pre-filters, with a proven margin; the pairs it keeps are re-scored with the fp32 kernels' arithmetic, so the result has
+ * the indices and the distance bits of creid_stream_topk_collect + creid_stream_topk_select on the fp32 rows.
+ *  pack    : x fp32 [rows][D] -> y = x rounded once to dtype (CREID_BF16 | CREID_F16, round to nearest even; else
+ *            CREID_E_DTYPE) and stats float64 [rows][3] = { |x - y|^2, |y|^2, |x|^2 } per row, accumulated in double; a row
+ *            with an Inf / NaN element or one that overflows f16 has non-finite statistics.  D % 8 == 0, D <= 2^20, else
+ *            CREID_E_SHAPE; rows == 0 returns 0.
+ *  (collect: creid_stream_topk_collect_h16 on the packed rows with the FP32 rows' qq / gg and tau[i] >= dh_(k) + 2 m_i, where
+ *            dh_(k) is the row's k-th smallest 16-bit distance and m_i >= |16-bit distance - fp32 distance| over the row.)
+ *  rescore : in place of creid_stream_topk_select.  cand / count / cap / k / out_idx / out_dist as there; q fp32 [m][D],
+ *            g fp32 [n][D], qq / gg as given to the collect; margin2 fp32 [m] >= 2 m_i, rounded up by the caller.  Per row: the
+ *            entries with 16-bit distance <= (the list's k-th smallest + margin2[row], rounded up) are kept, each receives the
+ *            fp32 distance fmaf(-2, <q_i, g_j> as the k-ordered fmaf chain from zero, qq[i] + gg[j]) -- the bits of
+ *            creid_sqdist_matrix on fp32 -- and the k smallest (distance, index) are written.  kept int32 [m]: the number of
+ *            kept entries.  flags uint8 [m]: 0 = written; 1 = unwritten, use creid_sqdist_matrix + creid_topk_rows on the fp32
+ *            rows: the list overflowed or holds fewer than k entries, margin2[row] is not a finite number >= 0, more than 1024
+ *            entries (the re-score capacity) are kept, or a listed column is >= n.  D % 4 == 0, D <= 2^20, cap and k as for
+ *            select, else CREID_E_SHAPE; m == 0 returns 0.
+ * Every check happens before anything is launched. */
+int creid_prefilter_pack(const float* x, int64_t rows, int64_t D, int dtype, void* y, double* stats, void* stream);
+int creid_stream_topk_rescore(const uint64_t* cand, const int32_t* count, int64_t m, int32_t cap, int32_t k,
+                              const float* q, const float* g, const float* qq, const float* gg, int64_t n, int64_t D,
+                              const float* margin2, int64_t* out_idx, float* out_dist, uint8_t* flags, int32_t* kept,
+                              void* stream);
+
 /* ---- k-reciprocal re-ranking (Zhong et al., CVPR 2017; csrc/rerank.hip): the sparse stages between the streamed top-k and
  * the ranking kernels.  X = cat(q, g) fp32 [N][D], d = creid_sqdist_matrix's squared L2, every ordering by (d, index);
  * nb int64 [N][K], K = k1 + 1: row i's K nearest columns of X (creid_stream_topk_* on (X, X)); rowmax fp32 [N]:
