@@ -49,6 +49,9 @@ SIGNATURES = {
     "creid_stream_topk_collect_h16": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, C.c_int, _p, _i32, _p, _p, _p]),
     "creid_prefilter_pack": (C.c_int, [_p, _i64, _i64, C.c_int, _p, _p, _p]),
     "creid_stream_topk_rescore": (C.c_int, [_p, _p, _i64, _i32, _i32, _p, _p, _p, _p, _i64, _i64, _p, _p, _p, _p, _p, _p]),
+    "creid_stream_count_band_h16": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, C.c_int, _p, _p, _i32, _p, _p, _p, _p, _i32, _p, _p, _p,
+                                              _p]),
+    "creid_stream_count_rescore": (C.c_int, [_p, _p, _i64, _i32, _p, _p, _p, _p, _i64, _i64, _i32, _p, _p, _p, _p, _p, _p]),
     "creid_rerank_recip": (C.c_int, [_p, _i64, _i32, _i32, _p, _p, _p, _p]),
     "creid_rerank_weights": (C.c_int, [_p, _p, _p, _i64, _i64, _p, _p, _p, _p]),
     "creid_rerank_expand": (C.c_int, [_p, _i64, _i32, _i32, _p, _p, _p, _i32, _p, _p, _p, _p, _p]),

@@ -81,8 +81,11 @@ def load_checkpoint_file(path, map_location="cpu"):
 
 
 class ModelBase(_Base):
-    def __init__(self, cfg=None, test_dataloader=None, compute_dtype=None, eval_precision=None, **kwargs):
+    def __init__(self, cfg=None, test_dataloader=None, compute_dtype=None, eval_precision=None, eval_prefilter=None, **kwargs):
+        """eval_prefilter=torch.bfloat16 | torch.float16: get_val_metrics runs its streamed evaluation with the counting
+        contraction on the 16-bit MFMA and the fp32 results (R1_mAP(prefilter=...)); not with camera-aware centroids."""
         super().__init__()
+        self.eval_prefilter = eval_prefilter
         if cfg is None:
             hparams = {**kwargs}
         elif isinstance(cfg, dict):
@@ -311,9 +314,10 @@ class ModelBase(_Base):
 
     def get_val_metrics(self, embeddings, labels, camids):
         """modelling/bases.py:264-297."""
-        self.r1_map_func = R1_mAP(pl_module=self, num_query=self.hparams.num_query,
-                                  feat_norm=self.hparams.TEST.FEAT_NORM, streamed=True)   # only the metrics are used
         respect_camids = bool(self.hparams.MODEL.KEEP_CAMID_CENTROIDS and self.hparams.MODEL.USE_CENTROIDS)
+        self.r1_map_func = R1_mAP(pl_module=self, num_query=self.hparams.num_query,
+                                  feat_norm=self.hparams.TEST.FEAT_NORM, streamed=True,   # only the metrics are used
+                                  prefilter=None if respect_camids else self.eval_prefilter)
         cmc, mAP, all_topk = self.r1_map_func.compute(feats=embeddings.float(), pids=labels, camids=camids,
                                                       respect_camids=respect_camids)
         topks = {}

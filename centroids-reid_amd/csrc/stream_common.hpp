@@ -8,6 +8,7 @@
 
 constexpr int SQ_TM = 64, SQ_TN = 256;           // a tile: 64 query rows x 256 gallery columns (four units of 64 columns)
 constexpr int EPI_COUNT = 0, EPI_TOPK = 1;       // what a streamed contraction does with a finished tile
+constexpr int EPI_BAND = 2;                      // the count with a per-row error band (16-bit kernel only: stream_consume.hpp)
 constexpr int PL_MAXC = 128;                     // positive-list capacity of the count epilogue (LDS: [64][cap] keys + histogram)
 constexpr int TS_MIN_CAP = 64, TS_MAX_CAP = 8192;   // candidate-list capacity of the top-k epilogue
 
@@ -27,6 +28,26 @@ static int stream_log2cap(int cap) {
 __device__ __forceinline__ unsigned mono_key(float d) {
   const unsigned u = __float_as_uint(d);
   return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
+}
+
+// a + b rounded towards +inf or beyond: never below the real sum (round to nearest, then one step up; a zero sum steps to the
+// smallest positive number, past +0)
+__device__ __forceinline__ float add_up(float a, float b) {
+  const float s = a + b;
+  if (!(fabsf(s) <= 3.402823466e+38f)) return s;  // inf / NaN stay
+  const unsigned u = __float_as_uint(s);
+  if ((u << 1) == 0u) return __uint_as_float(1u);
+  return __uint_as_float((u >> 31) ? u - 1u : u + 1u);
+}
+
+// a - b rounded towards -inf or beyond: never above the real difference (the mirror of add_up; a zero difference steps to the
+// smallest negative number, past -0, so that its key is below the key of either zero)
+__device__ __forceinline__ float sub_down(float a, float b) {
+  const float s = a - b;
+  if (!(fabsf(s) <= 3.402823466e+38f)) return s;  // inf / NaN stay
+  const unsigned u = __float_as_uint(s);
+  if ((u << 1) == 0u) return __uint_as_float(0x80000001u);
+  return __uint_as_float((u >> 31) ? u + 1u : u - 1u);
 }
 
 /* The work split of a streamed contraction (both kernels, both epilogues).  elem_bytes: the size of a feature element (the
@@ -68,13 +89,13 @@ static StreamSplit stream_split(int64_t m, int64_t n, int64_t D, int64_t elem_by
 
 /* Launch of a count contraction (Kernel: an instantiation of either file's kernel, 256 threads): its dynamic LDS is the query
  * tile's positive keys and histogram, [64][cap] words each -- beyond the default limit at capacity 128, so every instantiation
- * raises its own limit once. */
-template <auto Kernel, class... Args>
+ * raises its own limit once.  EXTRA: words behind them (the banded count's row margins). */
+template <auto Kernel, int EXTRA = 0, class... Args>
 static int stream_count_launch(const StreamSplit& sp, int cap, void* stream, Args... args) {
   static const hipError_t attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                        2 * SQ_TM * PL_MAXC * (int)sizeof(unsigned));
+                                                        (2 * SQ_TM * PL_MAXC + EXTRA) * (int)sizeof(unsigned));
   if (attr_rc != hipSuccess) return (int)attr_rc;
-  hipLaunchKernelGGL(Kernel, dim3(sp.grid), dim3(256), (size_t)2 * SQ_TM * cap * sizeof(unsigned), as_stream(stream), args...);
+  hipLaunchKernelGGL(Kernel, dim3(sp.grid), dim3(256), (size_t)(2 * SQ_TM * cap + EXTRA) * sizeof(unsigned), as_stream(stream), args...);
   return (int)hipGetLastError();
 }
 

@@ -5,8 +5,8 @@
 // register r of lane (l31 = lane & 31, kh = lane >> 5) is row wm * 32 + 4 kh + (r & 3) + 8 (r >> 2), column l31 of its block.
 //
 //   stream_segment_begin<EPI>   per (query tile, run of columns): the LDS state the consumer reads
-//   stream_tile_consume<EPI, H, NJ>   one finished tile: the count or the top-k epilogue
-//   stream_segment_end          count: the LDS histogram leaves for global memory
+//   stream_tile_consume<EPI, H, NJ>   one finished tile: the count, the top-k or the banded-count epilogue
+//   stream_segment_end          count / banded count: the LDS histogram leaves for global memory
 //   STREAM_DISPATCH_NJ          the tile width as a compile-time constant
 //   poslist_pad / poslist_rank_emit   the tail of the two positives kernels
 //
@@ -17,7 +17,8 @@
 #include <type_traits>
 
 // The LDS state of a segment: per query row of the tile its norm, pid, number of positives and `kmax` (count: key of the row's last
-// positive; top-k: key of the row's threshold); count only: the rows' positive keys [64][cap] and the histogram [64][cap].
+// positive; top-k: key of the row's threshold); count only: the rows' positive keys [64][cap] and the histogram [64][cap];
+// banded count: the count's state and the rows' margins `mg`.
 struct StreamLds {
   float* qq;
   long long* qpid;
@@ -25,10 +26,12 @@ struct StreamLds {
   unsigned* kmax;
   unsigned* keys;
   unsigned* hist;
+  float* mg;
 };
 
 // The problem the consumers see: sizes, list capacity, and the global arrays they read or write (count: q_pids .. hist_out;
-// top-k: tau .. cand_count; the other group is unused and may be null).
+// top-k: tau .. cand_count; the other group is unused and may be null.  Banded count: the count's group, and tau = the rows'
+// margins, cand = the rows' lists of ambiguous columns -- [m][acap] 32-bit words --, cand_count = their lengths).
 struct StreamProblem {
   int m, n, cap, log2cap;
   const float* qq;
@@ -42,6 +45,7 @@ struct StreamProblem {
   const float* tau;
   unsigned long long* cand;
   int32_t* cand_count;
+  int acap;
 };
 
 // Every thread of the 256-thread workgroup calls it, behind a barrier after the previous segment's stream_segment_end; the
@@ -69,11 +73,12 @@ __device__ __forceinline__ void stream_segment_begin(const StreamLds& L, const S
       L.qq[ts] = rr < P.m ? P.qq[rr] : 0.f;
       L.qpid[ts] = rr < P.m ? (long long)P.q_pids[rr] : 0;
       L.kmax[ts] = np > 0 ? P.pos_key[(int64_t)rr * P.cap + np - 1] : 0u;
+      if constexpr (EPI == EPI_BAND) L.mg[ts] = rr < P.m ? P.tau[rr] : 0.f;
     }
   }
 }
 
-// count: flushes the segment's histogram (every thread of the workgroup, after the segment's last tile)
+// count / banded count: flushes the segment's histogram (every thread of the workgroup, after the segment's last tile)
 __device__ __forceinline__ void stream_segment_end(const StreamLds& L, const StreamProblem& P, int row0) {
   int ts = threadIdx.x;
   asm volatile("" : "+v"(ts));                     // opaque, as in stream_segment_begin
@@ -95,6 +100,14 @@ __device__ __forceinline__ void stream_segment_end(const StreamLds& L, const Str
 //              skip_count & 1: timing ablation, no row has positives (results wrong).
 //   EPI_TOPK : every element whose key is <= the row's threshold key takes a slot of its row's list with a global atomicAdd on
 //              cand_count[row] and, while the slot is below `cap`, stores key << 32 | col there.
+//   EPI_BAND : the count for a distance dh known to lie within mg = L.mg[row] of the exact one d (16-bit operands, fp32 positive
+//              keys: reid_metric.R1_mAP(prefilter=...)).  lo = sub_down(dh, mg) <= d <= hi = add_up(dh, mg).  key(lo) beyond the
+//              row's last positive: behind every positive, skipped.  l = #positives with key < key(lo): each of them ranks before
+//              the negative whatever d is.  K[l] <= key(hi): a positive lies inside the band, the pair is AMBIGUOUS and its
+//              column is appended to the row's list (one global atomicAdd per half-wave and row on cand_count[row]; stored while
+//              the slot is below `acap`) for creid_stream_count_rescore.  Otherwise every positive from l on ranks behind it and
+//              the slot is l, as the fp32 kernel finds it.  A pair whose dh, lo or hi is not finite is ambiguous.  key(hi) is
+//              formed again after the search instead of living through it: the search's registers are the count's.
 template <int EPI, int H, int NJ>
 __device__ __forceinline__ void stream_tile_consume(const f32x16 (&acc)[NJ], int wm, int wn, int l31, int kh, int row0, int col0,
                                                     int skip_count, const StreamLds& L, const StreamProblem& P) {
@@ -108,7 +121,7 @@ __device__ __forceinline__ void stream_tile_consume(const f32x16 (&acc)[NJ], int
     const int c = col0 + (wn + 2 * j) * 32 + l31;
     okc[j] = c < P.n;
     gv[j] = okc[j] ? P.gg[c] : 0.f;
-    if constexpr (EPI == EPI_COUNT) gp[j] = okc[j] ? (long long)P.g_pids[c] : 0;
+    if constexpr (EPI != EPI_TOPK) gp[j] = okc[j] ? (long long)P.g_pids[c] : 0;
   }
   if constexpr (EPI == EPI_TOPK) {
     // One accumulator row at a time: its threshold is one LDS read, a hit one global atomic.
@@ -126,6 +139,58 @@ __device__ __forceinline__ void stream_tile_consume(const f32x16 (&acc)[NJ], int
           const int slot = atomicAdd(&P.cand_count[rr], 1);
           if (slot < P.cap)
             P.cand[rr * P.cap + slot] = ((unsigned long long)key << 32) | (unsigned)(col0 + (wn + 2 * j) * 32 + l31);
+        }
+      }
+    }
+  } else if constexpr (EPI == EPI_BAND) {
+    static_assert(H == 1, "one accumulator row at a time");
+    unsigned* __restrict__ amb = reinterpret_cast<unsigned*>(P.cand);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int rl = rbase + (r & 3) + 8 * (r >> 2);
+      const int np = L.np[rl];
+      // Uniform per wave half (a half shares its row), so the halves may diverge here.  The ballot below then sees only the active
+      // lanes, every lane reads its own half of it, and the shuffle's source is the first ambiguous lane of that half: active.
+      if (np == 0) continue;
+      const long long qp = L.qpid[rl];
+      const float qv = L.qq[rl], mg = L.mg[rl];
+      const unsigned kmax = L.kmax[rl];
+      const unsigned* K = L.keys + (rl << P.log2cap);
+      int lo[NJ];
+      unsigned key[NJ];
+      bool live[NJ];
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        const float dlo = sub_down(fmaf(-2.0f, acc[j][r], qv + gv[j]), mg);
+        key[j] = mono_key(dlo);
+        // not finite (then dh or hi may be so too: the test after the search): ambiguous, searched with whatever key it has
+        live[j] = okc[j] && gp[j] != qp && (key[j] <= kmax || !(fabsf(dlo) <= 3.402823466e+38f));
+        lo[j] = 0;
+      }
+      for (int step = P.cap >> 1; step > 0; step >>= 1) {
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) lo[j] += (K[lo[j] + step - 1] < key[j]) ? step : 0;
+      }
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        int l = lo[j];
+        l += (K[l] < key[j]) ? 1 : 0;                                // l = #positives with key strictly below key(lo)
+        const float dh = fmaf(-2.0f, acc[j][r], qv + gv[j]);
+        const float dlo = sub_down(dh, mg), dhi = add_up(dh, mg);
+        const bool fin = fabsf(dh) <= 3.402823466e+38f && fabsf(dlo) <= 3.402823466e+38f && fabsf(dhi) <= 3.402823466e+38f;
+        const bool ambiguous = live[j] && (!fin || (l < np && K[l] <= mono_key(dhi)));
+        if (live[j] && !ambiguous && l < np) atomicAdd(&L.hist[(rl << P.log2cap) + l], 1u);
+        // the ambiguous lanes of this half-wave (one row) take their slots with one atomic
+        const unsigned long long bal = __ballot(ambiguous);
+        const unsigned half = kh ? (unsigned)(bal >> 32) : (unsigned)bal;
+        if (ambiguous) {
+          const int before = __popc(half & ((1u << l31) - 1u));
+          int64_t rr = row0 + rl;
+          int base = 0;
+          if (before == 0) base = atomicAdd(&P.cand_count[rr], __popc(half));
+          base = __shfl(base, 32 * kh + __ffs(half) - 1);
+          const int slot = base + before;
+          if (slot < P.acap) amb[rr * P.acap + slot] = (unsigned)(col0 + (wn + 2 * j) * 32 + l31);
         }
       }
     }

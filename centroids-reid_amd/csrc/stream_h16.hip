@@ -1,5 +1,6 @@
 // The streamed contraction of stream_eval.hip for bf16 / f16 features: the same two consumers -- the evaluation's count
-// (CMC / mAP with no m x n matrix) and the retrieval's candidate collection (top-k with no matrix) -- on
+// (CMC / mAP with no m x n matrix) and the retrieval's candidate collection (top-k with no matrix) -- and a third, the banded
+// count (the exact fp32 evaluation's pre-filter: the count where the 16-bit distance decides, a list of the pairs where not), on
 // v_mfma_f32_32x32x16_{bf16,f16}, the instruction of the materialised 16-bit distance kernel (sqdist_h16_kernel, dist.hip).
 //
 // Bit contract with sqdist_h16_kernel.  Every accumulator element starts at 0 and receives ONE MFMA per 16-deep k-step, steps
@@ -11,7 +12,7 @@
 // streamed results equal the materialised ones bit for bit.
 //
 //   sqdist_stream_h16_kernel<DT, EPI>   persistent: a workgroup walks a run of gallery tiles for one query tile and hands every
-//                                       finished 64 x 256 tile, in registers, to the count or the top-k epilogue.
+//                                       finished 64 x 256 tile, in registers, to the count, top-k or banded-count epilogue.
 //   stream_poslist_h16_kernel<DT>       the distances of a query to its <= 128 positives on the same MFMA (a 16-bit MFMA's
 //                                       internal summation cannot be reproduced with an fmaf chain).
 // This file keeps what is 16-bit: the operand staging and LDS image, the k-loop, and the positives' distances.  The epilogues, the
@@ -157,7 +158,7 @@ __global__ __launch_bounds__(256, 2) void sqdist_stream_h16_kernel(
     const float* __restrict__ gg, int m, int n, int D, const int64_t* __restrict__ q_pids, const int64_t* __restrict__ g_pids,
     int cap, int log2cap, const unsigned* __restrict__ pos_key, const int32_t* __restrict__ pos_idx,
     const int32_t* __restrict__ npos, unsigned* __restrict__ hist_out, int tiles_m, int U, int upw, int mode,
-    const float* __restrict__ tau, unsigned long long* __restrict__ cand, int32_t* __restrict__ cand_count) {
+    const float* __restrict__ tau, unsigned long long* __restrict__ cand, int32_t* __restrict__ cand_count, int acap) {
   __shared__ __attribute__((aligned(16))) unsigned short As[SQ_TM * H_BK];
   __shared__ __attribute__((aligned(16))) unsigned short Bs[SQ_TN * H_BK];
   __shared__ float s_qq[SQ_TM];
@@ -167,11 +168,12 @@ __global__ __launch_bounds__(256, 2) void sqdist_stream_h16_kernel(
   extern __shared__ __attribute__((aligned(16))) unsigned dyn[];
   unsigned* s_keys = dyn;                        // [64][cap]
   unsigned* s_hist = dyn + SQ_TM * cap;          // [64][cap]
+  float* s_mg = reinterpret_cast<float*>(dyn + 2 * SQ_TM * cap);     // [64], banded count only
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
   const int l31 = lane & 31, kh = lane >> 5;
-  const StreamLds L{s_qq, s_qpid, s_np, s_kmax, s_keys, s_hist};
-  const StreamProblem P{m, n, cap, log2cap, qq, gg, q_pids, g_pids, pos_key, pos_idx, npos, hist_out, tau, cand, cand_count};
+  const StreamLds L{s_qq, s_qpid, s_np, s_kmax, s_keys, s_hist, s_mg};
+  const StreamProblem P{m, n, cap, log2cap, qq, gg, q_pids, g_pids, pos_key, pos_idx, npos, hist_out, tau, cand, cand_count, acap};
   long long g0, g1;                              // this workgroup's run, in units of the rows laid end to end
   stream_run(tiles_m, U, upw, mode, g0, g1);
 
@@ -259,7 +261,7 @@ __global__ __launch_bounds__(256, 2) void sqdist_stream_h16_kernel(
     // One accumulator row at a time in the count (the fp32 kernel runs two): one row's NJ search chains keep this kernel inside
     // the 256 registers of two workgroups per CU, and the second workgroup fills the gaps of the chains.
     stream_tile_consume<EPI, 1, NJ>(acc, wm, wn, l31, kh, row0, col0, 0, L, P);
-    if constexpr (EPI == EPI_COUNT) { if (next >= 0) { set_tile(next); gload(0, 8); } }
+    if constexpr (EPI != EPI_TOPK) { if (next >= 0) { set_tile(next); gload(0, 8); } }
   };
 
   while (g0 < g1) {                               // the run's segments: one per row it touches
@@ -282,7 +284,7 @@ __global__ __launch_bounds__(256, 2) void sqdist_stream_h16_kernel(
       STREAM_DISPATCH_NJ(nj, tile, col, next);
       col += 256;
     }
-    if constexpr (EPI == EPI_COUNT) stream_segment_end(L, P, row0);
+    if constexpr (EPI != EPI_TOPK) stream_segment_end(L, P, row0);
   }
 }
 
@@ -329,7 +331,7 @@ int creid_stream_count_h16(const void* q, const void* g, const float* qq, const 
 #define CREID_COUNT_H16_LAUNCH(DT)                                                                                          \
   return stream_count_launch<sqdist_stream_h16_kernel<DT, EPI_COUNT>>(                                                       \
       sp, (int)cap, stream, qh, gh, qq, gg, (int)m, (int)n, (int)D, q_pids, g_pids, (int)cap, log2cap, pos_key, pos_idx, npos, hist, \
-      sp.tiles_m, sp.U, sp.upw, sp.mode, (const float*)nullptr, (unsigned long long*)nullptr, (int32_t*)nullptr)
+      sp.tiles_m, sp.U, sp.upw, sp.mode, (const float*)nullptr, (unsigned long long*)nullptr, (int32_t*)nullptr, 0)
   if (dtype == CREID_BF16) CREID_COUNT_H16_LAUNCH(CREID_BF16); else CREID_COUNT_H16_LAUNCH(CREID_F16);
 #undef CREID_COUNT_H16_LAUNCH
 }
@@ -350,10 +352,32 @@ int creid_stream_topk_collect_h16(const void* q, const void* g, const float* qq,
   hipLaunchKernelGGL((sqdist_stream_h16_kernel<DT, EPI_TOPK>), dim3(sp.grid), dim3(256), 0, as_stream(stream), qh, gh, qq,   \
                      gg, (int)m, (int)n, (int)D, (const int64_t*)nullptr, (const int64_t*)nullptr, (int)cap, 0,              \
                      (const unsigned*)nullptr, (const int32_t*)nullptr, (const int32_t*)nullptr, (unsigned*)nullptr,         \
-                     sp.tiles_m, sp.U, sp.upw, sp.mode, tau, reinterpret_cast<unsigned long long*>(cand), count)
+                     sp.tiles_m, sp.U, sp.upw, sp.mode, tau, reinterpret_cast<unsigned long long*>(cand), count, 0)
   if (dtype == CREID_BF16) CREID_TOPK_H16_LAUNCH(CREID_BF16); else CREID_TOPK_H16_LAUNCH(CREID_F16);
 #undef CREID_TOPK_H16_LAUNCH
   CREID_LAUNCH_RET();
+}
+
+int creid_stream_count_band_h16(const void* q, const void* g, const float* qq, const float* gg, int64_t m, int64_t n, int64_t D,
+                                int dtype, const int64_t* q_pids, const int64_t* g_pids, int32_t cap, const uint32_t* pos_key,
+                                const int32_t* pos_idx, const int32_t* npos, const float* margin, int32_t amb_cap, uint32_t* amb,
+                                int32_t* amb_count, uint32_t* hist, void* stream) {
+  CREID_CHECK_ARG(m >= 0 && n > 0 && D > 0);
+  if (m == 0) return 0;
+  CREID_CHECK_ARG(q && g && qq && gg && q_pids && g_pids && pos_key && pos_idx && npos && margin && amb && amb_count && hist);
+  if (!stream_count_cap_ok(cap) || !stream_topk_cap_ok(amb_cap) || D % 8 != 0 || D > H_MAX_D) return CREID_E_SHAPE;
+  if (!stream_mn_ok(m, n)) return CREID_E_SHAPE;
+  if (!creid_is16(dtype)) return CREID_E_DTYPE;
+  const int log2cap = stream_log2cap(cap);
+  const StreamSplit sp = stream_split(m, n, D, 2);
+  const unsigned short* qh = static_cast<const unsigned short*>(q);
+  const unsigned short* gh = static_cast<const unsigned short*>(g);
+#define CREID_BAND_H16_LAUNCH(DT)                                                                                           \
+  return stream_count_launch<sqdist_stream_h16_kernel<DT, EPI_BAND>, SQ_TM>(                                                 \
+      sp, (int)cap, stream, qh, gh, qq, gg, (int)m, (int)n, (int)D, q_pids, g_pids, (int)cap, log2cap, pos_key, pos_idx, npos, hist, \
+      sp.tiles_m, sp.U, sp.upw, sp.mode, margin, reinterpret_cast<unsigned long long*>(amb), amb_count, (int)amb_cap)
+  if (dtype == CREID_BF16) CREID_BAND_H16_LAUNCH(CREID_BF16); else CREID_BAND_H16_LAUNCH(CREID_F16);
+#undef CREID_BAND_H16_LAUNCH
 }
 
 }  // extern "C"

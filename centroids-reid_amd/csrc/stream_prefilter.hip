@@ -14,6 +14,12 @@
 //   (creid_stream_topk_collect_h16, unchanged, collects every dh <= tau_i + 2 m_i, tau_i >= dh_(k) from a gallery sample.)
 //   stream_topk_rescore_kernel    per query: sorts the list by dh, keeps the prefix within dh_(k) + 2 m_i, replaces each kept key
 //                                 with the fp32 distance (STREAM_FMAF_CHAIN + the sqdist epilogue) and sorts again.
+//
+// The exact fp32 evaluation (reid_metric.R1_mAP(streamed=True, prefilter=...)) is built the same way: the banded count of
+// stream_h16.hip (EPI_BAND, stream_consume.hpp) places every negative whose 16-bit distance, widened by m_i on both sides, falls
+// between two positives' fp32 keys, and lists the others;
+//   stream_count_rescore_kernel   per query: each listed pair receives the fp32 distance and goes through the fp32 count
+//                                 epilogue's own search.  The histogram is then creid_stream_count's, element for element.
 #include "stream_chain.hpp"
 #include "stream_common.hpp"
 #include "topk_tail.hpp"
@@ -22,15 +28,7 @@ namespace {
 constexpr int RS_T = 1024;                       // threads of a re-score workgroup: one fmaf chain each
 constexpr int RS_CAP = RS_T;                     // entries a row may keep (reid_metric.STREAM_RESCORE_CAPACITY)
 constexpr int64_t PF_MAX_D = 1 << 20;            // as the 16-bit streamed kernels
-
-// a + b rounded towards +inf or beyond: never below the real sum (round to nearest, then one step up)
-__device__ __forceinline__ float add_up(float a, float b) {
-  const float s = a + b;
-  if (!(fabsf(s) <= 3.402823466e+38f)) return s;  // inf / NaN stay
-  const unsigned u = __float_as_uint(s);
-  if ((u << 1) == 0u) return __uint_as_float(1u);
-  return __uint_as_float((u >> 31) ? u - 1u : u + 1u);
-}
+constexpr int CR_T = 256;                        // threads of a count re-score workgroup
 }  // namespace
 
 // ----------------------------------------------------------------------------------------
@@ -125,6 +123,55 @@ __global__ __launch_bounds__(RS_T) void stream_topk_rescore_kernel(
   if (tid == 0) { flags[row] = 0; kept[row] = nk; }
 }
 
+// ----------------------------------------------------------------------------------------
+// 3. count re-score.  One workgroup per query; the row's positive keys and gallery indices are staged once in LDS.  Thread t takes
+//    listed pairs t, t + 256, ..: the fmaf chain and the sqdist epilogue give the fp32 key, then the fp32 count epilogue
+//    (stream_tile_consume<EPI_COUNT>): nothing beyond the last positive's key, l = #positives with a smaller key by binary search
+//    over the padded list, ties walked by gallery index, one integer atomic on hist[row][l].  (Same-pid columns never reach a
+//    list: the banded count skips them.)
+//    Flagged, nothing written: the list overflowed or names a column outside the gallery.
+// ----------------------------------------------------------------------------------------
+__global__ __launch_bounds__(CR_T) void stream_count_rescore_kernel(
+    const unsigned* __restrict__ amb, const int32_t* __restrict__ amb_count, int acap, const float* __restrict__ q,
+    const float* __restrict__ g, const float* __restrict__ qq, const float* __restrict__ gg, int n, int D, int cap,
+    const unsigned* __restrict__ pos_key, const int32_t* __restrict__ pos_idx, const int32_t* __restrict__ npos,
+    unsigned* __restrict__ hist, uint8_t* __restrict__ flags) {
+  __shared__ unsigned s_key[PL_MAXC];
+  __shared__ int s_idx[PL_MAXC];
+  __shared__ int s_bad;
+  const int tid = threadIdx.x;
+  const int64_t row = blockIdx.x;
+  const int c = amb_count[row];                                                    // (uniform)
+  const int np = min(max(npos[row], 0), cap);
+  if (c > acap) { if (tid == 0) flags[row] = 1; return; }
+  if (c <= 0 || np == 0) { if (tid == 0) flags[row] = 0; return; }
+  const unsigned* __restrict__ list = amb + row * acap;
+  if (tid == 0) s_bad = 0;
+  for (int i = tid; i < cap; i += CR_T) { s_key[i] = pos_key[row * cap + i]; s_idx[i] = pos_idx[row * cap + i]; }
+  __syncthreads();
+  bool bad = false;
+  for (int i = tid; i < c; i += CR_T) bad |= list[i] >= (unsigned)n;
+  if (bad) s_bad = 1;
+  __syncthreads();
+  if (s_bad) { if (tid == 0) flags[row] = 1; return; }
+  if (tid == 0) flags[row] = 0;
+  const float* __restrict__ qrow = q + row * D;
+  const unsigned kmax = s_key[np - 1];
+  const float qv = qq[row];
+  for (int i = tid; i < c; i += CR_T) {
+    const int col = (int)list[i];
+    const float* __restrict__ grow = g + (int64_t)col * D;
+    STREAM_FMAF_CHAIN(acc, qrow, grow, D);
+    const unsigned key = mono_key(fmaf(-2.0f, acc, qv + gg[col]));                 // sqdist epilogue, same bits
+    if (key > kmax) continue;                                                      // behind every positive
+    int l = 0;
+    for (int step = cap >> 1; step > 0; step >>= 1) l += (s_key[l + step - 1] < key) ? step : 0;
+    l += (s_key[l] < key) ? 1 : 0;
+    while (l < np && s_key[l] == key && s_idx[l] < col) ++l;                       // ties: by gallery index
+    if (l < np) atomicAdd(&hist[row * cap + l], 1u);
+  }
+}
+
 extern "C" {
 
 int creid_prefilter_pack(const float* x, int64_t rows, int64_t D, int dtype, void* y, double* stats, void* stream) {
@@ -153,6 +200,20 @@ int creid_stream_topk_rescore(const uint64_t* cand, const int32_t* count, int64_
   hipLaunchKernelGGL(stream_topk_rescore_kernel, dim3((unsigned)m), dim3(RS_T), (size_t)cap * sizeof(unsigned long long),
                      as_stream(stream), reinterpret_cast<const unsigned long long*>(cand), count, (int)cap, (int)k, q, g, qq, gg,
                      (int)n, (int)D, margin2, out_idx, out_dist, flags, kept);
+  CREID_LAUNCH_RET();
+}
+
+int creid_stream_count_rescore(const uint32_t* amb, const int32_t* amb_count, int64_t m, int32_t amb_cap, const float* q,
+                               const float* g, const float* qq, const float* gg, int64_t n, int64_t D, int32_t cap,
+                               const uint32_t* pos_key, const int32_t* pos_idx, const int32_t* npos, uint32_t* hist,
+                               uint8_t* flags, void* stream) {
+  CREID_CHECK_ARG(m >= 0 && n > 0 && D > 0);
+  if (!stream_topk_cap_ok(amb_cap) || !stream_count_cap_ok(cap) || D % 4 != 0 || D > PF_MAX_D) return CREID_E_SHAPE;
+  if (!stream_mn_ok(m, n)) return CREID_E_SHAPE;
+  if (m == 0) return 0;
+  CREID_CHECK_ARG(amb && amb_count && q && g && qq && gg && pos_key && pos_idx && npos && hist && flags);
+  hipLaunchKernelGGL(stream_count_rescore_kernel, dim3((unsigned)m), dim3(CR_T), 0, as_stream(stream), amb, amb_count, (int)amb_cap,
+                     q, g, qq, gg, (int)n, (int)D, (int)cap, pos_key, pos_idx, npos, hist, flags);
   CREID_LAUNCH_RET();
 }
 

@@ -809,6 +809,87 @@ def _stream_eval(fq, fg, qq, gg, plan: StreamPlan):
     return valid, ap, first
 
 
+EVAL_PREFILTER_CAPACITY = 1024        # ambiguous pairs a query may list (creid_stream_count_band_h16: power of two, 64 .. 8192)
+
+
+def _stream_eval_prefilter(fq, fg, qq, gg, plan: StreamPlan, dtype, acap, clock):
+    """_stream_eval on fp32 features with the counting contraction on the 16-bit MFMA and the fp32 path's histogram, element for
+    element.  d: the fp32 kernels' distance; dh: the 16-bit streamed kernel's distance on the rows rounded once to `dtype`, given
+    the fp32 rows' own qq / gg; m_i = prefilter_margin >= |dh - d| over row i (query statistics against the gallery's maxima, as in
+    _topk_stream_prefilter; inflated by 1 + 2^-20 and rounded UP to fp32), so d_ij lies in [dh_ij - m_i, dh_ij + m_i].  The
+    positives' keys are the fp32 ones (creid_stream_poslist on the fp32 rows).  Per negative, with lo / hi the band's ends rounded
+    outwards: behind every positive when key(lo) is beyond the last positive's key; else l = #positives with key < key(lo), all
+    ranked before it whatever d is; if positive l lies inside the band (key <= key(hi)) the pair is ambiguous and listed, else
+    every positive from l on is behind it and hist[i][l] is bumped -- the slot the fp32 kernel finds.
+    creid_stream_count_rescore gives every listed pair its fp32 bits and the fp32 epilogue's search.
+    Everything is enqueued without a host read: the gallery's maxima stay on the device, so non-finite ones (f16 overflow, Inf /
+    NaN) flag every row with a positive list on the device, and the caller's repair runs the fp32 count on all of them; queries
+    with more positives than the list holds (npos < 0) are never flagged: their results come from the caller's general path.
+    Returns (valid, ap, first, state); state holds what the caller's read-back and repair need."""
+    L.require_gpu(fq, fg, qq, gg)
+    assert fq.dtype == fg.dtype == torch.float32 and fq.shape[1] % 8 == 0
+    m, n, D = fq.shape[0], fg.shape[0], fq.shape[1]
+    assert (m, n) == (plan.m, plan.n)
+    dev, lib, st = fq.device, L.lib(), L.stream()
+    cap, dt = plan.cap, L._DT[dtype]
+    qp, gp = prefilter_pack(fq, dtype), prefilter_pack(fg, dtype)
+    gmax = torch.cat([gp.stats.amax(dim=0), gg.abs().amax().double().reshape(1)]) if n else torch.zeros(4, dtype=torch.float64, device=dev)
+    x2 = torch.maximum(qp.stats[:, 2], qq.abs().double())
+    margin = prefilter_margin(qp.stats[:, 0], qp.stats[:, 1], x2, gmax[0], gmax[1], gmax[2], torch.maximum(gmax[2], gmax[3]), D)
+    margin32 = _round_up_f32((1.0 + _PREFILTER_INFLATE) * margin)
+    clock.mark("pack")
+    pos_key = torch.empty((m, cap), dtype=torch.int32, device=dev)
+    pos_idx = torch.empty((m, cap), dtype=torch.int32, device=dev)
+    npos = torch.empty(m, dtype=torch.int32, device=dev)
+    hist = torch.zeros((m, cap), dtype=torch.int32, device=dev)
+    amb = torch.empty((m, acap), dtype=torch.int32, device=dev)
+    amb_count = torch.zeros(m, dtype=torch.int32, device=dev)
+    flags = torch.zeros(m, dtype=torch.uint8, device=dev)
+    L.check(lib.creid_stream_poslist(L.ptr(fq), L.ptr(fg), L.ptr(qq), L.ptr(gg), m, n, D, L.ptr(plan.q_slot),
+                                     L.ptr(plan.csr_off), L.ptr(plan.g_order), L.ptr(plan.q_cams), L.ptr(plan.g_cams), cap,
+                                     L.ptr(pos_key), L.ptr(pos_idx), L.ptr(npos), st), "creid_stream_poslist")
+    clock.mark("poslist")
+    L.check(lib.creid_stream_count_band_h16(L.ptr(qp.rounded), L.ptr(gp.rounded), L.ptr(qq), L.ptr(gg), m, n, D, dt,
+                                            L.ptr(plan.q_pids), L.ptr(plan.g_pids), cap, L.ptr(pos_key), L.ptr(pos_idx),
+                                            L.ptr(npos), L.ptr(margin32), acap, L.ptr(amb), L.ptr(amb_count), L.ptr(hist), st),
+            "creid_stream_count_band_h16")
+    clock.mark("count")
+    L.check(lib.creid_stream_count_rescore(L.ptr(amb), L.ptr(amb_count), m, acap, L.ptr(fq), L.ptr(fg), L.ptr(qq), L.ptr(gg), n, D,
+                                           cap, L.ptr(pos_key), L.ptr(pos_idx), L.ptr(npos), L.ptr(hist), L.ptr(flags), st),
+            "creid_stream_count_rescore")
+    # a gallery out of range: every row to the fp32 count, except those that have no list and take the general path
+    flags = torch.where(torch.isfinite(gmax).all(), flags, (npos >= 0).to(torch.uint8))
+    valid = torch.empty(m, dtype=torch.uint8, device=dev)
+    ap = torch.empty(m, dtype=torch.float64, device=dev)
+    first = torch.empty(m, dtype=torch.int32, device=dev)
+    L.check(lib.creid_stream_finalize(L.ptr(npos), L.ptr(hist), m, cap, L.ptr(valid), L.ptr(ap), L.ptr(first), st),
+            "creid_stream_finalize")
+    clock.mark("rescore")
+    state = dict(flags=flags, ambiguous=amb_count, gmax=gmax, margin_max=margin.max().reshape(1) if m else gmax[:1] * 0,
+                 pos_key=pos_key, pos_idx=pos_idx, npos=npos)
+    return valid, ap, first, state
+
+
+def _stream_eval_prefilter_repair(fq, fg, qq, gg, plan: StreamPlan, state, rows, valid, ap, first):
+    """The rows creid_stream_count_rescore flagged, redone with the fp32 creid_stream_count on the gathered rows (their q, qq,
+    q_pids, positive lists and a fresh histogram) and merged into valid / ap / first."""
+    dev, lib, st = fq.device, L.lib(), L.stream()
+    sel = torch.as_tensor(rows, device=dev)
+    r, n, D, cap = len(rows), fg.shape[0], fq.shape[1], plan.cap
+    q, sq, qp = fq.index_select(0, sel), qq.index_select(0, sel), plan.q_pids.index_select(0, sel)
+    pos_key, pos_idx = state["pos_key"].index_select(0, sel), state["pos_idx"].index_select(0, sel)
+    npos = state["npos"].index_select(0, sel)
+    hist = torch.zeros((r, cap), dtype=torch.int32, device=dev)
+    L.check(lib.creid_stream_count(L.ptr(q), L.ptr(fg), L.ptr(sq), L.ptr(gg), r, n, D, L.ptr(qp), L.ptr(plan.g_pids), cap,
+                                   L.ptr(pos_key), L.ptr(pos_idx), L.ptr(npos), L.ptr(hist), st), "creid_stream_count")
+    v2 = torch.empty(r, dtype=torch.uint8, device=dev)
+    a2 = torch.empty(r, dtype=torch.float64, device=dev)
+    f2 = torch.empty(r, dtype=torch.int32, device=dev)
+    L.check(lib.creid_stream_finalize(L.ptr(npos), L.ptr(hist), r, cap, L.ptr(v2), L.ptr(a2), L.ptr(f2), st),
+            "creid_stream_finalize")
+    valid.index_copy_(0, sel, v2); ap.index_copy_(0, sel, a2); first.index_copy_(0, sel, f2)
+
+
 def eval_reduce_device(valid, ap, first, max_rank):
     """Means over valid queries (utils/eval_reid.py:86-90) on the device: (cmc f32[max_rank], mAP f64[1],
     topk f64[5], nvalid i64[1])."""
@@ -827,14 +908,23 @@ class R1_mAP:
     MODEL.USE_CENTROIDS); trainer/logger lookups of the reference are optional here."""
 
     def __init__(self, pl_module=None, num_query=0, max_rank=50, feat_norm=True, dist_func="euclidean",
-                 compute_dtype=torch.float32, streamed=False, reranking=False):
+                 compute_dtype=torch.float32, streamed=False, reranking=False, prefilter=None, prefilter_capacity=None):
         """streamed=True: metric-only evaluation that never materialises the distance / index matrices (euclidean,
         plain camera ids; compute_dtype fp32, bf16 or f16 -- the 16-bit modes run the 16-bit MFMA and return exactly what
         their materialised evaluation returns); `last` then holds the per-query results only.  streamed=False keeps
         `last["distmat"]` / `last["indices"]` (what the rank-index parity tests and get_similar read).
         reranking=True (the defaults of re_ranking) or a dict of k1 / k2 / lambda_value: on the materialised euclidean fp32 path
         the k-reciprocal re-ranked matrix takes the place of `distmat`; ranking and evaluation are unchanged.  CreidError with
-        streamed=True, a 16-bit compute_dtype, the cosine distance or compute_chunked."""
+        streamed=True, a 16-bit compute_dtype, the cosine distance or compute_chunked.
+        prefilter=torch.bfloat16 | torch.float16 (streamed=True, fp32, euclidean, plain camera ids): the streamed evaluation with
+        its counting contraction on the 16-bit MFMA and the results of the fp32 streamed evaluation -- valid and first bit for bit,
+        ap within the order of its float64 additions (_stream_eval_prefilter).  prefilter_capacity (default
+        EVAL_PREFILTER_CAPACITY; a power of two, 64 .. 8192): the ambiguous pairs a query may list; queries that list more are
+        redone on the fp32 kernel.  `last["prefilter"]` then holds dtype (None when the gallery's statistics were not finite and
+        every row took the fp32 kernel), capacity, margin_max, fallback_rows, ambiguous (int32 [m] on the device: pairs listed per
+        query) and -- when `last` came in holding {"prefilter": {"timing": True}} -- stage_ms (pack, poslist, count, rescore,
+        repair, between device events).  CreidError with streamed=False, another compute_dtype or distance, or reranking; and
+        from compute(respect_camids=True)."""
         self.reranking = rerank_options(reranking)
         self.streamed = streamed
         self.num_query = num_query
@@ -853,10 +943,23 @@ class R1_mAP:
         if self.reranking is not None and (streamed or compute_dtype != torch.float32 or dist_func != "euclidean"):
             raise L.CreidError("R1_mAP(reranking=...) re-ranks the materialised euclidean fp32 matrix: not with streamed=True, "
                                f"compute_dtype={compute_dtype} or dist_func={dist_func!r}")
+        self.prefilter = prefilter
+        self.prefilter_capacity = EVAL_PREFILTER_CAPACITY if prefilter_capacity is None else int(prefilter_capacity)
+        if prefilter is not None:
+            if prefilter not in _H16:
+                raise L.CreidError(f"R1_mAP(prefilter=...) must be torch.bfloat16 or torch.float16, got {prefilter}")
+            if not streamed or compute_dtype != torch.float32 or dist_func != "euclidean" or self.reranking is not None:
+                raise L.CreidError("R1_mAP(prefilter=...) is the streamed euclidean fp32 evaluation: not with streamed=False, "
+                                   f"compute_dtype={compute_dtype}, dist_func={dist_func!r} or reranking")
+            c = self.prefilter_capacity
+            if c < 64 or c > 8192 or c & (c - 1):
+                raise L.CreidError(f"R1_mAP(prefilter_capacity=...) must be a power of two, 64 .. 8192, got {c}")
 
     def compute(self, feats, pids, camids, respect_camids=False):
         if not isinstance(feats, torch.Tensor) or not feats.is_cuda:
             raise L.CreidError("R1_mAP.compute needs device features (no CPU fallback)")
+        if self.prefilter is not None and respect_camids:
+            raise L.CreidError("R1_mAP(prefilter=...) evaluates plain camera ids: not with respect_camids=True")
         feats = _pad_width(feats.float().contiguous())
         nq = self.num_query
         if (self.streamed and self.dist_name == "euclidean" and not respect_camids
@@ -898,7 +1001,7 @@ class R1_mAP:
         self.last = dict(distmat=distmat, indices=indices, single_performance=single, valid=valid, ap=ap, first=first)
         return pack[:max_rank].astype(np.float32), float(pack[max_rank]), pack[max_rank + 1:max_rank + 6].copy()
 
-    def _compute_streamed(self, feats, pids, camids, plan=None, _normed=None):
+    def _compute_streamed(self, feats, pids, camids, plan=None, _normed=None, _clock=None):
         nq = self.num_query
         if _normed is not None:                 # the redo of a failed speculation: rows already normalised, nothing printed twice
             f, sq = _normed
@@ -928,7 +1031,14 @@ class R1_mAP:
             plan.finish()
         fq, fg = f[:nq], f[nq:]
         qq, gg = sq[:nq].contiguous(), sq[nq:].contiguous()
-        valid, ap, first = _stream_eval(fq, fg, qq, gg, plan)
+        pf = None
+        if self.prefilter is not None:
+            # zero columns behind the normalised rows change neither a norm, a rounding nor an fmaf chain
+            fq, fg = _pad_width(fq, 8), _pad_width(fg, 8)
+            clock = _clock or _StageClock(bool((self.last.get("prefilter") or {}).get("timing")))
+            valid, ap, first, pf = _stream_eval_prefilter(fq, fg, qq, gg, plan, self.prefilter, self.prefilter_capacity, clock)
+        else:
+            valid, ap, first = _stream_eval(fq, fg, qq, gg, plan)
         if len(plan.overflow):
             # queries with more positives than the LDS list holds: the general path on just those rows
             rows = torch.as_tensor(plan.overflow, device=feats.device)
@@ -942,6 +1052,8 @@ class R1_mAP:
         # ONE read-back for everything the host needs (five separate .cpu() calls are five synchronisations):
         # [cmc (max_rank) | mAP | topk (5) | valid (m) | ap (m)] as float64 (exact for the f32 / u8 members)
         stats = plan._stats.double() if speculative else torch.zeros(2, dtype=torch.float64, device=feats.device)
+        if pf is not None:                       # [flags (m) | gallery maxima (4) | margin max] ride in front of the statistics
+            stats = torch.cat([pf["flags"].double(), pf["gmax"], pf["margin_max"], stats])
         pack = torch.cat([cmc.double(), mAP, topk, valid.double(), ap, stats]).cpu().numpy()
         if speculative:
             need = 2
@@ -954,10 +1066,31 @@ class R1_mAP:
             if need > plan.cap or nover > 0:                     # the assumed capacity was too small: redo, synchronously
                 plan.cap = None
                 plan.finish()
-                return self._compute_streamed(feats, pids, camids, plan=plan, _normed=(f, sq))
+                return self._compute_streamed(feats, pids, camids, plan=plan, _normed=(f, sq), _clock=clock if pf is not None else None)
         elif getattr(plan, "_stats", None) is not None:
             _CAP_HINT[(plan.m, plan.n)] = 0 if len(plan.overflow) else plan.cap
         pack = pack[:-2]
+        info = None
+        if pf is not None:
+            tail, pack = pack[-(nq + 5):], pack[:-(nq + 5)]
+            bad = np.setdiff1d(np.nonzero(tail[:nq] != 0)[0], plan.overflow)   # (the general path's rows keep their results)
+            if len(bad):
+                # rows whose list overflowed: the fp32 count on just those rows, merged and reduced again (a second read-back,
+                # only when it happens)
+                _stream_eval_prefilter_repair(fq, fg, qq, gg, plan, pf, bad, valid, ap, first)
+                cmc, mAP, topk, _ = eval_reduce_device(valid, ap, first, max_rank)
+                pack = torch.cat([cmc.double(), mAP, topk, valid.double(), ap]).cpu().numpy()
+            clock.mark("repair")
+            info = dict(dtype=self.prefilter if np.isfinite(tail[nq:nq + 4]).all() else None, capacity=self.prefilter_capacity,
+                        margin_max=float(tail[nq + 4]), fallback_rows=int(len(bad)), ambiguous=pf["ambiguous"])
+            # per stage, summed over a redone speculation: the failed attempt's read-back and plan.finish() lie between its
+            # `rescore` mark and the second attempt's `pack` mark, so they are billed to `pack`
+            if clock.on:
+                stage_ms = {}
+                clock.marks[-1][1].synchronize()
+                for (_, prev), (name, ev) in zip(clock.marks, clock.marks[1:]):
+                    stage_ms[name] = stage_ms.get(name, 0.0) + prev.elapsed_time(ev)
+                info["stage_ms"] = stage_ms
         cmc_h = pack[:max_rank].astype(np.float32)
         mAP_h = float(pack[max_rank])
         topk_h = pack[max_rank + 1:max_rank + 6].copy()
@@ -966,6 +1099,8 @@ class R1_mAP:
         vi = np.nonzero(valid_h)[0]
         single = np.stack([vi.astype(np.float64), pids[:nq][vi].astype(np.float64), ap_h[vi]], axis=1)
         self.last = dict(valid=valid, ap=ap, first=first, single_performance=single, plan=plan)
+        if info is not None:
+            self.last["prefilter"] = info
         return cmc_h, mAP_h, topk_h
 
     def compute_chunked(self, feats, pids, camids, query_chunk=4096):

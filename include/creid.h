@@ -213,6 +213,35 @@ int creid_stream_topk_rescore(const uint64_t* cand, const int32_t* count, int64_
                               const float* margin2, int64_t* out_idx, float* out_dist, uint8_t* flags, int32_t* kept,
                               void* stream);
 
+/* ---- exact fp32 CMC / mAP with the counting contraction on the 16-bit MFMA (csrc/stream_h16.hip, csrc/stream_prefilter.hip): in
+ * place of creid_stream_count on the fp32 rows.  hist ends as creid_stream_count's, element for element, for every row that is not
+ * flagged; creid_stream_plan, creid_stream_poslist (on the FP32 rows) and creid_stream_finalize are unchanged.
+ *  band    : q / g the rows rounded once to dtype (creid_prefilter_pack), qq / gg the FP32 rows' norms, so that only the dot product
+ *            differs from the fp32 distance d; margin fp32 [m]: m_i >= |16-bit distance dh - d| over row i, rounded up by the
+ *            caller; pos_key / pos_idx / npos: creid_stream_poslist's lists of the fp32 rows; everything else as
+ *            creid_stream_count_h16.  Per negative j of query i (same-pid columns are skipped), with lo = dh - m_i moved one fp32
+ *            step down and hi = dh + m_i moved one step up: key(lo) above the row's last positive key -- behind every positive,
+ *            nothing to count; else l = the number of positives with key < key(lo), each ranked before j whatever d is; if
+ *            l < npos and pos_key[l] <= key(hi), a positive lies inside the band: the pair is ambiguous, amb_count[i] is bumped
+ *            and, while the slot is below amb_cap, the column is stored in amb uint32 [m][amb_cap] (arrival order); otherwise
+ *            hist[i][l] is bumped, the slot the fp32 kernel finds.  A pair whose dh, lo or hi is not finite is ambiguous.
+ *            amb_cap = a power of two, 64..8192.  amb_count int32 [m] and hist must be ZERO on entry.
+ *  rescore : every listed pair receives the fp32 distance fmaf(-2, <q_i, g_j> as the k-ordered fmaf chain from zero,
+ *            qq[i] + gg[j]) -- the bits of creid_sqdist_matrix on fp32 -- and goes through creid_stream_count's search (ties
+ *            with a positive by gallery index): hist[i][l] += 1 when it ranks before a positive.  q fp32 [m][D], g fp32 [n][D],
+ *            D % 4 == 0, D <= 2^20.  flags uint8 [m]: 0 = the row's hist is complete; 1 = nothing was added for the row, use
+ *            creid_stream_count on the fp32 row with a zeroed hist: amb_count[i] > amb_cap or a listed column is >= n.
+ * CREID_E_SHAPE / CREID_E_DTYPE for a cap, amb_cap, D or dtype outside these limits; every check happens before anything is
+ * launched; m == 0 returns 0. */
+int creid_stream_count_band_h16(const void* q, const void* g, const float* qq, const float* gg, int64_t m, int64_t n,
+                                int64_t D, int dtype, const int64_t* q_pids, const int64_t* g_pids, int32_t cap,
+                                const uint32_t* pos_key, const int32_t* pos_idx, const int32_t* npos, const float* margin,
+                                int32_t amb_cap, uint32_t* amb, int32_t* amb_count, uint32_t* hist, void* stream);
+int creid_stream_count_rescore(const uint32_t* amb, const int32_t* amb_count, int64_t m, int32_t amb_cap, const float* q,
+                               const float* g, const float* qq, const float* gg, int64_t n, int64_t D, int32_t cap,
+                               const uint32_t* pos_key, const int32_t* pos_idx, const int32_t* npos, uint32_t* hist,
+                               uint8_t* flags, void* stream);
+
 /* ---- k-reciprocal re-ranking (Zhong et al., CVPR 2017; csrc/rerank.hip): the sparse stages between the streamed top-k and
  * the ranking kernels.  X = cat(q, g) fp32 [N][D], d = creid_sqdist_matrix's squared L2, every ordering by (d, index);
  * nb int64 [N][K], K = k1 + 1: row i's K nearest columns of X (creid_stream_topk_* on (X, X)); rowmax fp32 [N]:
