@@ -40,6 +40,12 @@ SIGNATURES = {
     "creid_eval_reduce": (C.c_int, [_p, _p, _p, _i64, _i32, _p, _p, _p, _p, _p]),
     "creid_stream_plan": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p]),
     "creid_stream_poslist": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _i32, _p, _p, _p, _p]),
+    "creid_stream_plan_camsets": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p]),
+    "creid_stream_poslist_camsets": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _i32, _p, _p, _p, _p]),
+    "creid_stream_poslist_h16_camsets": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, C.c_int, _p, _p, _p, _p, _p, _i32, _p, _p, _p, _p]),
+    "creid_centroid_index_ws_bytes": (_sz, [_i64, _i64]),
+    "creid_centroid_index_plan": (C.c_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _p]),
+    "creid_centroid_index_fill": (C.c_int, [_p, _i64, _i64, _i64, _i64, _p, _i64, _i64, _p, _p, _p, _p, _p]),
     "creid_stream_count": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _i32, _p, _p, _p, _p, _p]),
     "creid_stream_finalize": (C.c_int, [_p, _p, _i64, _i32, _p, _p, _p, _p]),
     "creid_stream_topk_collect": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, _p, _i32, _p, _p, _p]),

@@ -16,7 +16,7 @@ from . import _lib as L
 from .baseline import Baseline
 from .config import CfgNode
 from .losses import BatchNorm1d, CenterLoss, CrossEntropyLabelSmooth, Linear, TripletLoss
-from .reid_metric import R1_mAP
+from .reid_metric import CameraSets, R1_mAP, StreamPlan, _upload_labels
 from .solver import build_optimizer, build_scheduler
 
 try:  # optional
@@ -29,6 +29,71 @@ except Exception:  # noqa: BLE001
 
 class AttributeDict(CfgNode):
     pass
+
+
+def _camera_centroids_host(labels, camids, num_query):
+    """modelling/bases.py:205-236 as the reference writes it: for each gallery PID and each distinct camera of its QUERIES one
+    centroid of the gallery rows from other cameras, de-duplicated by camera set -> (groups: gallery-relative row indices per
+    centroid, centroid pids, centroid camera lists).  The reference looks the gallery cameras up as camids[inds] with
+    gallery-relative indices on the full vector (:214); that quirk is kept so results match.  The path for label sets the
+    device index (camera_centroid_index) does not take, and its checker in tests/test_camset_stream_gpu.py."""
+    labels, camids = np.asarray(labels), np.asarray(camids)
+    lq, lg = labels[:num_query], labels[num_query:]
+    groups, cent_labels, cent_cams = [], [], []
+    for u in np.unique(lg):
+        inds = np.nonzero(lg == u)[0]
+        cams_g = camids[inds]
+        seen = set()
+        for cur in np.unique(camids[np.nonzero(lq == u)[0]]):
+            sel = np.nonzero(cams_g != cur)[0]
+            if len(sel) == 0:
+                continue
+            used = tuple(sorted(np.unique(cams_g[cams_g != cur]).tolist()))
+            if used in seen:
+                continue
+            seen.add(used)
+            groups.append(inds[sel]); cent_labels.append(u); cent_cams.append(list(used))
+    return groups, cent_labels, cent_cams
+
+
+def camera_centroid_index(labels, camids, num_query, device):
+    """The same grouping on the device (csrc/centroid_index.hip): one upload of the [2, nq + ng] label tensor, a counting sort
+    over the dense gallery pid range, one 16-byte read-back {n_cent, rows} that sizes the outputs.  Returns device int64
+    tensors (order [rows]: full-vector row numbers, offsets [n_cent + 1], cent_labels [n_cent], cent_masks [n_cent]: bit c =
+    camera c) -- what creid_gather_mean_rows and StreamPlan(camsets=True) read -- or None when the label set is not one the
+    device build takes: a pid range beyond StreamPlan.MAX_DENSE_RANGE, a camera id outside 0..62, or no gallery."""
+    p = np.ascontiguousarray(np.asarray(labels), dtype=np.int64)
+    c = np.ascontiguousarray(np.asarray(camids), dtype=np.int64)
+    nq = int(num_query)
+    ng = len(p) - nq
+    if ng <= 0 or p.ndim != 1 or c.shape != p.shape:
+        return None
+    pmin = int(p[nq:].min())
+    R = int(p[nq:].max()) - pmin + 1
+    used = c[:max(nq, ng)]                      # (:214: a gallery row's camera is read at its gallery-relative index)
+    if R > StreamPlan.MAX_DENSE_RANGE or used.min() < 0 or used.max() > 62:
+        return None
+    lib, st = L.lib(), L.stream()
+    lab = _upload_labels(p, c, device)
+    ws = torch.empty(int(lib.creid_centroid_index_ws_bytes(ng, R)) // 8, dtype=torch.int64, device=device)
+    totals = torch.empty(2, dtype=torch.int64, device=device)
+    L.check(lib.creid_centroid_index_plan(L.ptr(lab), nq, ng, pmin, R, L.ptr(ws), L.ptr(totals), st), "creid_centroid_index_plan")
+    n_cent, rows = (int(v) for v in totals.cpu().tolist())
+    out = torch.empty(rows + 3 * n_cent + 1, dtype=torch.int64, device=device)
+    order, offsets = out[:rows], out[rows:rows + n_cent + 1]
+    cent_labels, cent_masks = out[rows + n_cent + 1:rows + 2 * n_cent + 1], out[rows + 2 * n_cent + 1:]
+    L.check(lib.creid_centroid_index_fill(L.ptr(lab), nq, ng, pmin, R, L.ptr(ws), n_cent, rows, L.ptr(order), L.ptr(offsets),
+                                          L.ptr(cent_labels), L.ptr(cent_masks), st), "creid_centroid_index_fill")
+    return order, offsets, cent_labels, cent_masks
+
+
+def _mask_camera_lists(masks):
+    """int64 bitmasks -> the reference's sorted camera-id lists, one per mask."""
+    m = np.asarray(masks, dtype=np.int64)
+    bits = ((m[:, None] >> np.arange(63, dtype=np.int64)) & 1).astype(bool)
+    flat = np.nonzero(bits)[1].tolist()
+    ends = np.cumsum(bits.sum(axis=1)).tolist()
+    return [flat[a:b] for a, b in zip([0] + ends[:-1], ends)]
 
 
 def _to_attr(d):
@@ -263,32 +328,24 @@ class ModelBase(_Base):
     def validation_create_centroids(self, embeddings, labels, camids, respect_camids=False):
         """modelling/bases.py:179-262 (respect_camids=False): gallery -> per-PID mean (device kernel);
         returns (embeddings [nq + n_centroids, D], labels, camids) with the reference's dummy camids
-        (including its nq-longer-than-needed camid vector, bases.py:255-260)."""
+        (including its nq-longer-than-needed camid vector, bases.py:255-260).
+        respect_camids=True (:205-236): one centroid per gallery PID and distinct camera of its queries, grouped on the
+        device (camera_centroid_index); camids comes back as `[[c], ...] + centroid camera lists`, a CameraSets that also
+        carries the centroids' masks on the device for R1_mAP(streamed=True).compute(respect_camids=True)."""
         num_query = self.hparams.num_query
         labels = np.asarray(labels)
         emb = embeddings.float().contiguous()
         L.require_gpu(emb)
         lq, lg = labels[:num_query], labels[num_query:]
         groups, cent_labels, cent_cams = [], [], []
+        dev = emb.device
+        index = None
         if respect_camids:
-            # modelling/bases.py:205-236.  For each gallery PID and each distinct camera of its QUERIES: one
-            # centroid of the gallery rows from other cameras, de-duplicated by camera set.  The reference looks
-            # the gallery cameras up as camids[inds] with gallery-relative indices on the full vector (:214);
-            # that quirk is kept so results match.
+            # modelling/bases.py:205-236: grouped on the device; the host loop for what the device build does not take
             camids = np.asarray(camids)
-            for u in np.unique(lg):
-                inds = np.nonzero(lg == u)[0]
-                cams_g = camids[inds]
-                seen = set()
-                for cur in np.unique(camids[np.nonzero(lq == u)[0]]):
-                    sel = np.nonzero(cams_g != cur)[0]
-                    if len(sel) == 0:
-                        continue
-                    used = tuple(sorted(np.unique(cams_g[cams_g != cur]).tolist()))
-                    if used in seen:
-                        continue
-                    seen.add(used)
-                    groups.append(inds[sel]); cent_labels.append(u); cent_cams.append(list(used))
+            index = camera_centroid_index(labels, camids, num_query, dev)
+            if index is None:
+                groups, cent_labels, cent_cams = _camera_centroids_host(labels, camids, num_query)
         else:
             uniq, inverse = np.unique(lg, return_inverse=True)
             order_all = np.argsort(inverse, kind="stable")        # gallery rows grouped by PID, original order kept
@@ -296,18 +353,30 @@ class ModelBase(_Base):
             bounds = np.concatenate([[0], np.cumsum(counts)])
             groups = [order_all[bounds[i]:bounds[i + 1]] for i in range(len(uniq))]
             cent_labels = list(uniq)
-        order = np.concatenate(groups).astype(np.int64) + num_query
-        offsets = np.concatenate([[0], np.cumsum([len(g) for g in groups])]).astype(np.int64)
-        dev = emb.device
-        order_t = torch.as_tensor(order, device=dev)
-        off_t = torch.as_tensor(offsets, device=dev)
-        cents = torch.empty((len(groups), emb.shape[1]), dtype=torch.float32, device=dev)
-        L.check(L.lib().creid_gather_mean_rows(L.ptr(emb), L.ptr(order_t), L.ptr(off_t), len(groups), emb.shape[1],
+        masks_t = None
+        if index is not None:
+            order_t, off_t, labels_t, masks_t = index
+            n_cent = labels_t.shape[0]
+        else:
+            order = np.concatenate(groups).astype(np.int64) + num_query
+            offsets = np.concatenate([[0], np.cumsum([len(g) for g in groups])]).astype(np.int64)
+            order_t = torch.as_tensor(order, device=dev)
+            off_t = torch.as_tensor(offsets, device=dev)
+            n_cent = len(groups)
+        cents = torch.empty((n_cent, emb.shape[1]), dtype=torch.float32, device=dev)
+        L.check(L.lib().creid_gather_mean_rows(L.ptr(emb), L.ptr(order_t), L.ptr(off_t), n_cent, emb.shape[1],
                                                L.ptr(cents), L.stream()), "creid_gather_mean_rows")
         out = torch.cat((emb[:num_query], cents), dim=0)
+        if index is not None:
+            # the return values are host objects (the reference's): one read-back of [labels | masks] behind the launches
+            lab_masks = torch.stack((labels_t, masks_t)).cpu().numpy()
+            cent_labels = lab_masks[0].astype(lg.dtype)
+            cent_cams = _mask_camera_lists(lab_masks[1])
         out_labels = np.hstack((lq, np.asarray(cent_labels)))
         if respect_camids:
             out_camids = [[c] for c in camids[:num_query]] + cent_cams             # :250-253
+            if masks_t is not None:         # the masks ride along: the streamed evaluation neither rebuilds nor uploads them
+                out_camids = CameraSets(out_camids, masks_t, camids[:num_query])
         else:
             out_camids = np.hstack((np.zeros_like(lq), np.ones_like(out_labels)))   # :255-260 (quirk kept)
         return out, out_labels, out_camids

@@ -30,6 +30,15 @@ __device__ __forceinline__ unsigned mono_key(float d) {
   return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
 }
 
+// Is a same-pid gallery entry removed for a query on camera qc (utils/eval_reid.py:51-57)?  Plain: the entry's camera is qc.
+// CAMSETS: the entry carries a bitmask of cameras (bit c = camera c) and is removed when qc (0..62, checked by the entry
+// points' callers) is in it -- the test of creid_cmc_ap_ranked_camsets.
+template <bool CAMSETS>
+__device__ __forceinline__ bool cam_removed(int64_t g_cam, int64_t qc) {
+  if constexpr (CAMSETS) return (((unsigned long long)g_cam >> (qc & 63)) & 1ull) != 0;
+  else return g_cam == qc;
+}
+
 // a + b rounded towards +inf or beyond: never below the real sum (round to nearest, then one step up; a zero sum steps to the
 // smallest positive number, past +0)
 __device__ __forceinline__ float add_up(float a, float b) {

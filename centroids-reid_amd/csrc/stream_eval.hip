@@ -46,6 +46,9 @@ constexpr int SQ_PA = SQ_TM * 2 + 8, SQ_PB = SQ_TN * 2 + 8;
 //    once and then served by the L1); the query row is wave-uniform, so its values arrive through the scalar cache.
 //    A chain is 2048 dependent FMAs (~5 us); thousands of them run side by side.
 // ----------------------------------------------------------------------------------------
+//    CAMSETS: g_cams holds camera-SET bitmasks (bit c = camera c; the centroids of modelling/bases.py:205-236) and a candidate is
+//    dropped when the query's camera (0..62) is in its set -- utils/eval_reid.py:51-55.
+template <bool CAMSETS>
 __global__ __launch_bounds__(PL_MAXC) void stream_poslist_kernel(
     const float* __restrict__ q, const float* __restrict__ g, const float* __restrict__ qq, const float* __restrict__ gg,
     int D, const int32_t* __restrict__ q_slot, const int64_t* __restrict__ csr_off, const int32_t* __restrict__ g_order,
@@ -68,7 +71,7 @@ __global__ __launch_bounds__(PL_MAXC) void stream_poslist_kernel(
   for (int64_t b = c0; b < c1; b += PL_MAXC) {
     const int64_t e = b + tid;
     int gi = -1;
-    if (e < c1) { gi = g_order[e]; if (g_cams[gi] == qc) gi = -1; }
+    if (e < c1) { gi = g_order[e]; if (cam_removed<CAMSETS>(g_cams[gi], qc)) gi = -1; }
     const unsigned long long bal = __ballot(gi >= 0);
     if (lane == 0) s_wcnt[wave] = __popcll(bal);
     __syncthreads();
@@ -404,6 +407,7 @@ __global__ __launch_bounds__(256) void plan_scatter_kernel(const int64_t* __rest
 }
 
 // one wave per query
+template <bool CAMSETS>
 __global__ __launch_bounds__(256) void plan_query_kernel(const int64_t* __restrict__ q_pids, const int64_t* __restrict__ q_cams,
                                                          const int64_t* __restrict__ g_cams, const int64_t* __restrict__ csr,
                                                          const int32_t* __restrict__ g_order, int64_t pmin, int R, int m,
@@ -419,7 +423,7 @@ __global__ __launch_bounds__(256) void plan_query_kernel(const int64_t* __restri
       slot = (int)s;
       const int64_t qc = q_cams[qi];
       int same = 0;
-      for (int64_t e = c0 + lane; e < c1; e += 64) same += g_cams[g_order[e]] == qc ? 1 : 0;
+      for (int64_t e = c0 + lane; e < c1; e += 64) same += cam_removed<CAMSETS>(g_cams[g_order[e]], qc) ? 1 : 0;
       same = wave_sum_i(same);
       np = (int)(c1 - c0) - same;
     }
@@ -454,16 +458,11 @@ __global__ __launch_bounds__(TS_T) void stream_topk_select_kernel(const unsigned
   if (tid == 0) flags[row] = 0;
 }
 
-extern "C" {
-
-/* Device-side index for the streamed evaluation.  g_pids / g_cams int64[n], q_pids / q_cams int64[m] on the device; the pid
- * range [pmin, pmin + R) must cover every gallery pid (the caller knows min / max from the host arrays it uploaded).
- * Outputs: csr_off int64[R + 1], g_order int32[n], q_slot int32[m] (pid - pmin, or -1 when the pid has no gallery entry),
- * n_pos int32[m] (same pid, other camera), stats int32[2] = {max n_pos among queries with n_pos <= 128, #queries beyond}.
- * scratch: int32[2 * R].  Five launches, no host synchronisation. */
-int creid_stream_plan(const int64_t* q_pids, const int64_t* g_pids, const int64_t* q_cams, const int64_t* g_cams, int64_t m,
-                      int64_t n, int64_t pmin, int64_t R, int64_t* csr_off, int32_t* g_order, int32_t* q_slot, int32_t* n_pos,
-                      int32_t* stats, int32_t* scratch, void* stream) {
+// the launches behind creid_stream_plan / creid_stream_poslist and their camera-set forms
+template <bool CAMSETS>
+static int stream_plan_launch(const int64_t* q_pids, const int64_t* g_pids, const int64_t* q_cams, const int64_t* g_cams, int64_t m,
+                              int64_t n, int64_t pmin, int64_t R, int64_t* csr_off, int32_t* g_order, int32_t* q_slot,
+                              int32_t* n_pos, int32_t* stats, int32_t* scratch, void* stream) {
   CREID_CHECK_ARG(m >= 0 && n > 0 && R > 0);
   CREID_CHECK_ARG(q_pids && g_pids && q_cams && g_cams && csr_off && g_order && q_slot && n_pos && stats && scratch);
   if (n > 0x7ffffff0LL || m > 0x7ffffff0LL || R > (1LL << 26)) return CREID_E_SHAPE;
@@ -477,23 +476,63 @@ int creid_stream_plan(const int64_t* q_pids, const int64_t* g_pids, const int64_
   hipLaunchKernelGGL(plan_scan_kernel, dim3(1), dim3(1024), 0, s, count, (int)R, csr_off, cursor, stats);
   hipLaunchKernelGGL(plan_scatter_kernel, dim3(gb), dim3(256), 0, s, g_pids, (int)n, pmin, (int)R, csr_off, cursor, g_order);
   if (m > 0)
-    hipLaunchKernelGGL(plan_query_kernel, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, s, q_pids, q_cams, g_cams, csr_off, g_order,
-                       pmin, (int)R, (int)m, q_slot, n_pos, stats);
+    hipLaunchKernelGGL(plan_query_kernel<CAMSETS>, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, s, q_pids, q_cams, g_cams, csr_off,
+                       g_order, pmin, (int)R, (int)m, q_slot, n_pos, stats);
   CREID_LAUNCH_RET();
+}
+
+template <bool CAMSETS>
+static int stream_poslist_launch(const float* q, const float* g, const float* qq, const float* gg, int64_t m, int64_t n,
+                                 int64_t D, const int32_t* q_slot, const int64_t* csr_off, const int32_t* g_order,
+                                 const int64_t* q_cams, const int64_t* g_cams, int32_t cap, uint32_t* pos_key, int32_t* pos_idx,
+                                 int32_t* npos, void* stream) {
+  CREID_CHECK_ARG(m >= 0 && n > 0 && D > 0);
+  if (m == 0) return 0;
+  CREID_CHECK_ARG(q && g && qq && gg && q_slot && csr_off && g_order && q_cams && g_cams && pos_key && pos_idx && npos);
+  if (!stream_count_cap_ok(cap)) return CREID_E_SHAPE;
+  if (!stream_mn_ok(m, n)) return CREID_E_SHAPE;
+  hipLaunchKernelGGL(stream_poslist_kernel<CAMSETS>, dim3((unsigned)m), dim3(PL_MAXC), 0, as_stream(stream), q, g, qq, gg, (int)D,
+                     q_slot, csr_off, g_order, q_cams, g_cams, (int)cap, pos_key, pos_idx, npos);
+  CREID_LAUNCH_RET();
+}
+
+extern "C" {
+
+/* Device-side index for the streamed evaluation.  g_pids / g_cams int64[n], q_pids / q_cams int64[m] on the device; the pid
+ * range [pmin, pmin + R) must cover every gallery pid (the caller knows min / max from the host arrays it uploaded).
+ * Outputs: csr_off int64[R + 1], g_order int32[n], q_slot int32[m] (pid - pmin, or -1 when the pid has no gallery entry),
+ * n_pos int32[m] (same pid, other camera), stats int32[2] = {max n_pos among queries with n_pos <= 128, #queries beyond}.
+ * scratch: int32[2 * R].  Five launches, no host synchronisation. */
+int creid_stream_plan(const int64_t* q_pids, const int64_t* g_pids, const int64_t* q_cams, const int64_t* g_cams, int64_t m,
+                      int64_t n, int64_t pmin, int64_t R, int64_t* csr_off, int32_t* g_order, int32_t* q_slot, int32_t* n_pos,
+                      int32_t* stats, int32_t* scratch, void* stream) {
+  return stream_plan_launch<false>(q_pids, g_pids, q_cams, g_cams, m, n, pmin, R, csr_off, g_order, q_slot, n_pos, stats, scratch,
+                                   stream);
+}
+
+/* The same index when the gallery entries carry camera SETS (g_cam_masks: bit c = camera c; q_cams plain ids 0..62, checked by
+ * the caller): n_pos counts the same-pid entries whose set does not hold the query's camera. */
+int creid_stream_plan_camsets(const int64_t* q_pids, const int64_t* g_pids, const int64_t* q_cams, const int64_t* g_cam_masks,
+                              int64_t m, int64_t n, int64_t pmin, int64_t R, int64_t* csr_off, int32_t* g_order, int32_t* q_slot,
+                              int32_t* n_pos, int32_t* stats, int32_t* scratch, void* stream) {
+  return stream_plan_launch<true>(q_pids, g_pids, q_cams, g_cam_masks, m, n, pmin, R, csr_off, g_order, q_slot, n_pos, stats,
+                                  scratch, stream);
 }
 
 int creid_stream_poslist(const float* q, const float* g, const float* qq, const float* gg, int64_t m, int64_t n,
                          int64_t D, const int32_t* q_slot, const int64_t* csr_off, const int32_t* g_order,
                          const int64_t* q_cams, const int64_t* g_cams, int32_t cap, uint32_t* pos_key, int32_t* pos_idx,
                          int32_t* npos, void* stream) {
-  CREID_CHECK_ARG(m >= 0 && n > 0 && D > 0);
-  if (m == 0) return 0;
-  CREID_CHECK_ARG(q && g && qq && gg && q_slot && csr_off && g_order && q_cams && g_cams && pos_key && pos_idx && npos);
-  if (!stream_count_cap_ok(cap)) return CREID_E_SHAPE;
-  if (!stream_mn_ok(m, n)) return CREID_E_SHAPE;
-  hipLaunchKernelGGL(stream_poslist_kernel, dim3((unsigned)m), dim3(PL_MAXC), 0, as_stream(stream), q, g, qq, gg, (int)D, q_slot,
-                     csr_off, g_order, q_cams, g_cams, (int)cap, pos_key, pos_idx, npos);
-  CREID_LAUNCH_RET();
+  return stream_poslist_launch<false>(q, g, qq, gg, m, n, D, q_slot, csr_off, g_order, q_cams, g_cams, cap, pos_key, pos_idx, npos,
+                                      stream);
+}
+
+int creid_stream_poslist_camsets(const float* q, const float* g, const float* qq, const float* gg, int64_t m, int64_t n,
+                                 int64_t D, const int32_t* q_slot, const int64_t* csr_off, const int32_t* g_order,
+                                 const int64_t* q_cams, const int64_t* g_cam_masks, int32_t cap, uint32_t* pos_key,
+                                 int32_t* pos_idx, int32_t* npos, void* stream) {
+  return stream_poslist_launch<true>(q, g, qq, gg, m, n, D, q_slot, csr_off, g_order, q_cams, g_cam_masks, cap, pos_key, pos_idx,
+                                     npos, stream);
 }
 
 int creid_stream_count(const float* q, const float* g, const float* qq, const float* gg, int64_t m, int64_t n, int64_t D,

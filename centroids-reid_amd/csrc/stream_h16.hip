@@ -37,9 +37,9 @@ __device__ __forceinline__ f32x16 mfma_h16(const uint4& a, const uint4& b, f32x1
 //    is one 32 x 32 MFMA tile whose A fragment is the query row in all 32 rows (every lane loads q[16 step + 8 kh ..]) and whose
 //    B fragment is 16 bytes of the gathered gallery row cand[32 b + l31], straight from global memory; the distance of
 //    candidate 32 b + l31 is accumulator register 0 of lane l31 (row 0).  A k-tile (four steps: one 128-byte line per gallery
-//    row) is in flight while the previous one is multiplied.
+//    row) is in flight while the previous one is multiplied.  CAMSETS: as in stream_poslist_kernel (cam_removed).
 // ----------------------------------------------------------------------------------------
-template <int DT>
+template <int DT, bool CAMSETS>
 __global__ __launch_bounds__(64) void stream_poslist_h16_kernel(
     const unsigned short* __restrict__ q, const unsigned short* __restrict__ g, const float* __restrict__ qq,
     const float* __restrict__ gg, int D, const int32_t* __restrict__ q_slot, const int64_t* __restrict__ csr_off,
@@ -59,7 +59,7 @@ __global__ __launch_bounds__(64) void stream_poslist_h16_kernel(
   for (int64_t b = c0; b < c1; b += 64) {
     const int64_t e = b + lane;
     int gi = -1;
-    if (e < c1) { gi = g_order[e]; if (g_cams[gi] == qc) gi = -1; }
+    if (e < c1) { gi = g_order[e]; if (cam_removed<CAMSETS>(g_cams[gi], qc)) gi = -1; }
     const unsigned long long bal = __ballot(gi >= 0);
     if (gi >= 0) {
       const int p = nc + __popcll(bal & lanemask_lt());
@@ -292,12 +292,11 @@ namespace {
 constexpr int64_t H_MAX_D = 1 << 20;             // the staging offsets are 32-bit byte offsets over 256 rows of D elements
 }
 
-extern "C" {
-
-int creid_stream_poslist_h16(const void* q, const void* g, const float* qq, const float* gg, int64_t m, int64_t n, int64_t D,
-                             int dtype, const int32_t* q_slot, const int64_t* csr_off, const int32_t* g_order,
-                             const int64_t* q_cams, const int64_t* g_cams, int32_t cap, uint32_t* pos_key, int32_t* pos_idx,
-                             int32_t* npos, void* stream) {
+template <bool CAMSETS>
+static int stream_poslist_h16_launch(const void* q, const void* g, const float* qq, const float* gg, int64_t m, int64_t n, int64_t D,
+                                     int dtype, const int32_t* q_slot, const int64_t* csr_off, const int32_t* g_order,
+                                     const int64_t* q_cams, const int64_t* g_cams, int32_t cap, uint32_t* pos_key,
+                                     int32_t* pos_idx, int32_t* npos, void* stream) {
   CREID_CHECK_ARG(m >= 0 && n > 0 && D > 0);
   if (m == 0) return 0;
   CREID_CHECK_ARG(q && g && qq && gg && q_slot && csr_off && g_order && q_cams && g_cams && pos_key && pos_idx && npos);
@@ -307,12 +306,31 @@ int creid_stream_poslist_h16(const void* q, const void* g, const float* qq, cons
   const unsigned short* qh = static_cast<const unsigned short*>(q);
   const unsigned short* gh = static_cast<const unsigned short*>(g);
   if (dtype == CREID_BF16)
-    hipLaunchKernelGGL(stream_poslist_h16_kernel<CREID_BF16>, dim3((unsigned)m), dim3(64), 0, as_stream(stream), qh, gh, qq, gg,
-                       (int)D, q_slot, csr_off, g_order, q_cams, g_cams, (int)cap, pos_key, pos_idx, npos);
+    hipLaunchKernelGGL((stream_poslist_h16_kernel<CREID_BF16, CAMSETS>), dim3((unsigned)m), dim3(64), 0, as_stream(stream), qh, gh,
+                       qq, gg, (int)D, q_slot, csr_off, g_order, q_cams, g_cams, (int)cap, pos_key, pos_idx, npos);
   else
-    hipLaunchKernelGGL(stream_poslist_h16_kernel<CREID_F16>, dim3((unsigned)m), dim3(64), 0, as_stream(stream), qh, gh, qq, gg,
-                       (int)D, q_slot, csr_off, g_order, q_cams, g_cams, (int)cap, pos_key, pos_idx, npos);
+    hipLaunchKernelGGL((stream_poslist_h16_kernel<CREID_F16, CAMSETS>), dim3((unsigned)m), dim3(64), 0, as_stream(stream), qh, gh,
+                       qq, gg, (int)D, q_slot, csr_off, g_order, q_cams, g_cams, (int)cap, pos_key, pos_idx, npos);
   CREID_LAUNCH_RET();
+}
+
+extern "C" {
+
+int creid_stream_poslist_h16(const void* q, const void* g, const float* qq, const float* gg, int64_t m, int64_t n, int64_t D,
+                             int dtype, const int32_t* q_slot, const int64_t* csr_off, const int32_t* g_order,
+                             const int64_t* q_cams, const int64_t* g_cams, int32_t cap, uint32_t* pos_key, int32_t* pos_idx,
+                             int32_t* npos, void* stream) {
+  return stream_poslist_h16_launch<false>(q, g, qq, gg, m, n, D, dtype, q_slot, csr_off, g_order, q_cams, g_cams, cap, pos_key,
+                                          pos_idx, npos, stream);
+}
+
+/* creid_stream_poslist_h16 for gallery entries that carry camera sets (see creid_stream_poslist_camsets) */
+int creid_stream_poslist_h16_camsets(const void* q, const void* g, const float* qq, const float* gg, int64_t m, int64_t n,
+                                     int64_t D, int dtype, const int32_t* q_slot, const int64_t* csr_off, const int32_t* g_order,
+                                     const int64_t* q_cams, const int64_t* g_cam_masks, int32_t cap, uint32_t* pos_key,
+                                     int32_t* pos_idx, int32_t* npos, void* stream) {
+  return stream_poslist_h16_launch<true>(q, g, qq, gg, m, n, D, dtype, q_slot, csr_off, g_order, q_cams, g_cam_masks, cap, pos_key,
+                                         pos_idx, npos, stream);
 }
 
 int creid_stream_count_h16(const void* q, const void* g, const float* qq, const float* gg, int64_t m, int64_t n, int64_t D,

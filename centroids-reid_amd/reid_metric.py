@@ -584,20 +584,49 @@ def _camset_masks(g_camids):
     return out
 
 
+class CameraSets(list):
+    """The camera-set list R1_mAP.compute(respect_camids=True) receives -- `[[c], ...]` for the queries, then one list of camera
+    ids per gallery entry (modelling/bases.py:250-253) -- together with what the camera-aware centroid index already holds of
+    it: `masks` (int64 device tensor, one bitmask per gallery entry, bit c = camera c) and `q_cams` (int64 numpy vector of the
+    queries' cameras).  A plain list: everything that reads the lists keeps working; the streamed evaluation reads the two
+    attributes instead and neither walks the lists nor uploads the masks again."""
+
+    def __init__(self, lists, masks, q_cams):
+        super().__init__(lists)
+        self.masks = masks
+        self.q_cams = np.ascontiguousarray(q_cams, dtype=np.int64)
+
+
+def _check_query_cams(qc):
+    if qc.size and (qc.min() < 0 or qc.max() >= 63):                              # the kernels shift a 64-bit mask by it
+        raise L.CreidError("camera-set evaluation supports camera ids 0..62")
+    return qc
+
+
+def _camset_split(camids, nq):
+    """respect_camids=True camera argument -> (query cameras int64 [nq] inside 0..62, gallery masks: the carrier's device tensor
+    or an int64 numpy vector)."""
+    if isinstance(camids, CameraSets):
+        return _check_query_cams(camids.q_cams), camids.masks
+    qc = np.asarray([int(np.atleast_1d(c)[0]) for c in camids[:nq]], np.int64)
+    return _check_query_cams(qc), _camset_masks(camids[nq:])
+
+
 def eval_func_device(indices: torch.Tensor, q_pids, g_pids, q_camids, g_camids, max_rank=50, camsets=False):
     """Device half of eval_func: returns device tensors (cmc f32[max_rank], mAP f64[1], topk f64[5],
-    nvalid i64[1], valid u8[m], ap f64[m], first i32[m]).  camsets: g_camids is a list of camera-id lists."""
+    nvalid i64[1], valid u8[m], ap f64[m], first i32[m]).  camsets: g_camids is a list of camera-id lists, or the int64
+    bitmasks themselves (tensor / numpy vector) next to a numpy vector of plain query cameras."""
     L.require_gpu(indices)
     dev = indices.device
     m, n = indices.shape
     if n < max_rank:  # utils/eval_reid.py:33-35
         max_rank = n
         print("Note: number of gallery samples is quite small, got {}".format(n))
-    if camsets:
+    if camsets and isinstance(g_camids, (torch.Tensor, np.ndarray)):
+        q_camids = _check_query_cams(np.asarray(q_camids, np.int64))
+    elif camsets:
         g_camids = _camset_masks(g_camids)
-        q_camids = np.asarray([int(np.atleast_1d(c)[0]) for c in q_camids], np.int64)
-        if q_camids.size and (q_camids.min() < 0 or q_camids.max() >= 63):       # the kernel shifts a 64-bit mask by it
-            raise L.CreidError("camera-set evaluation supports camera ids 0..62")
+        q_camids = _check_query_cams(np.asarray([int(np.atleast_1d(c)[0]) for c in q_camids], np.int64))
     qp, gp, qc, gc = (_dev_i64(a, dev) for a in (q_pids, g_pids, q_camids, g_camids))
     valid = torch.empty(m, dtype=torch.uint8, device=dev)
     ap = torch.empty(m, dtype=torch.float64, device=dev)
@@ -670,28 +699,49 @@ class StreamPlan:
     `StreamPlan.on_device(...)` (what R1_mAP uses) builds it with creid_stream_plan: one upload of the label vectors, a
     counting sort on the GPU, and an 8-byte read-back for `cap`.  The constructor is the host (numpy) construction of the
     same index -- kept for label sets whose pid range is too sparse for a dense counting sort, and as the checker of the
-    device build in tests/test_stream_eval_gpu.py."""
+    device build in tests/test_stream_eval_gpu.py.
+
+    camsets=True (both constructions): the gallery entries carry camera SETS as int64 bitmasks and a positive is a same-pid
+    entry whose set does not hold the query's camera (creid_stream_plan_camsets; tests/test_camset_stream_*)."""
 
     MAX_CAP = 128
     MAX_DENSE_RANGE = 1 << 24          # pid range the device counting sort accepts (2 x int32 scratch + int64 CSR per slot)
 
+    camsets = False
+
     @classmethod
-    def on_device(cls, pids, camids, num_query, device):
-        """pids / camids: host vectors [nq + ng] as R1_mAP.compute receives them (utils/reid_metric.py:112)."""
+    def on_device(cls, pids, camids, num_query, device, camsets=False, g_cam_masks=None):
+        """pids / camids: host vectors [nq + ng] as R1_mAP.compute receives them (utils/reid_metric.py:112).
+        camsets=True (respect_camids, utils/eval_reid.py:51-55): the gallery entries carry camera SETS -- camids[nq:] are int64
+        bitmasks (bit c = camera c), camids[:nq] the queries' plain cameras (0..62, else CreidError); a same-pid entry is a
+        positive iff the query's camera is not in its set.  g_cam_masks: the gallery masks as an int64 device tensor [ng]
+        (CameraSets.masks); camids may then hold the nq query cameras only, and no mask is uploaded."""
         p = np.ascontiguousarray(np.asarray(pids), dtype=np.int64)
         c = np.ascontiguousarray(np.asarray(camids), dtype=np.int64)
         nq = int(num_query)
         m, n = nq, len(p) - nq
+        if camsets:
+            _check_query_cams(c[:nq])
+            if g_cam_masks is not None and len(c) < len(p):
+                c = np.concatenate([c[:nq], np.zeros(n, np.int64)])
+            if len(c) != len(p):
+                raise L.CreidError(f"StreamPlan.on_device(camsets=True): {len(p)} pids but {len(c)} camera entries")
+        host_masks = lambda: c[nq:] if g_cam_masks is None else g_cam_masks.cpu().numpy()
         if n <= 0:
-            return cls(p[:nq], p[nq:], c[:nq], c[nq:], device)
+            return cls(p[:nq], p[nq:], c[:nq], host_masks(), device, camsets=camsets)
         pmin, pmax = int(p[nq:].min()), int(p[nq:].max())
         R = pmax - pmin + 1
         if R > cls.MAX_DENSE_RANGE:
-            return cls(p[:nq], p[nq:], c[:nq], c[nq:], device)
+            return cls(p[:nq], p[nq:], c[:nq], host_masks(), device, camsets=camsets)
         self = cls.__new__(cls)
         self.m, self.n = m, n
+        self.camsets = bool(camsets)
         lab = _upload_labels(p, c, device)                                        # ONE upload: [2, nq + ng] int64
         self.q_pids, self.g_pids, self.q_cams, self.g_cams = lab[0, :nq], lab[0, nq:], lab[1, :nq], lab[1, nq:]
+        if camsets and g_cam_masks is not None:
+            L.require_gpu(g_cam_masks)
+            assert g_cam_masks.dtype == torch.int64 and g_cam_masks.shape == (n,)
+            self.g_cams = g_cam_masks.contiguous()
         # one allocation for the index: [csr_off int64 (R + 1) | g_order | q_slot | n_pos | stats | scratch (2 R)] int32
         mm = max(m, 1)
         ws = torch.empty(2 * (R + 1) + n + 2 * mm + 2 + 2 * R, dtype=torch.int32, device=device)
@@ -702,9 +752,10 @@ class StreamPlan:
         self._n_pos_dev = ws[o:o + mm]; o += mm
         self._stats = ws[o:o + 2]; o += 2
         scratch = ws[o:o + 2 * R]
-        L.check(L.lib().creid_stream_plan(L.ptr(self.q_pids), L.ptr(self.g_pids), L.ptr(self.q_cams), L.ptr(self.g_cams), m, n,
-                                          pmin, R, L.ptr(self.csr_off), L.ptr(self.g_order), L.ptr(self.q_slot),
-                                          L.ptr(self._n_pos_dev), L.ptr(self._stats), L.ptr(scratch), L.stream()),
+        build = L.lib().creid_stream_plan_camsets if camsets else L.lib().creid_stream_plan
+        L.check(build(L.ptr(self.q_pids), L.ptr(self.g_pids), L.ptr(self.q_cams), L.ptr(self.g_cams), m, n,
+                      pmin, R, L.ptr(self.csr_off), L.ptr(self.g_order), L.ptr(self.q_slot),
+                      L.ptr(self._n_pos_dev), L.ptr(self._stats), L.ptr(scratch), L.stream()),
                 "creid_stream_plan")
         self._n_pos = None
         self.cap = None                      # resolved by finish(): the only host read, 8 bytes
@@ -728,12 +779,16 @@ class StreamPlan:
             self._n_pos = self._n_pos_dev[:self.m].cpu().numpy().astype(np.int64)
         return self._n_pos
 
-    def __init__(self, q_pids, g_pids, q_camids, g_camids, device):
+    def __init__(self, q_pids, g_pids, q_camids, g_camids, device, camsets=False):
+        """camsets=True: g_camids are int64 camera-set bitmasks, q_camids plain cameras 0..62 (see on_device)."""
         qp = np.ascontiguousarray(np.asarray(q_pids), dtype=np.int64)
         gp = np.ascontiguousarray(np.asarray(g_pids), dtype=np.int64)
         qc = np.ascontiguousarray(np.asarray(q_camids), dtype=np.int64)
         gc = np.ascontiguousarray(np.asarray(g_camids), dtype=np.int64)
         self.m, self.n = len(qp), len(gp)
+        self.camsets = bool(camsets)
+        if camsets:
+            _check_query_cams(qc)
         order = np.argsort(gp, kind="stable").astype(np.int32)            # by pid, gallery index ascending inside
         upid, start = np.unique(gp[order], return_index=True)
         csr = np.concatenate([start, [self.n]]).astype(np.int64)
@@ -741,16 +796,25 @@ class StreamPlan:
         slot_c = np.minimum(slot, max(len(upid) - 1, 0))
         hit = (slot < len(upid)) & (upid[slot_c] == qp) if len(upid) else np.zeros(self.m, bool)
         same_pid = np.where(hit, csr[slot_c + 1] - csr[slot_c], 0) if len(upid) else np.zeros(self.m, np.int64)
-        # same pid AND same camera (the removed entries): count through a combined key
-        cmin = int(min(gc.min(initial=0), qc.min(initial=0)))
-        span = int(max(gc.max(initial=0), qc.max(initial=0))) - cmin + 1
-        pmin = int(min(gp.min(initial=0), qp.min(initial=0)))
-        gk = (gp - pmin) * span + (gc - cmin)
-        qk = (qp - pmin) * span + (qc - cmin)
-        uk, cnt = np.unique(gk, return_counts=True)
-        ks = np.searchsorted(uk, qk)
-        ks_c = np.minimum(ks, max(len(uk) - 1, 0))
-        same_cam = np.where((ks < len(uk)) & (uk[ks_c] == qk), cnt[ks_c], 0) if len(uk) else np.zeros(self.m, np.int64)
+        if camsets:
+            # same pid AND the query's camera in the entry's set: per query camera, the set's members counted per pid group
+            same_cam = np.zeros(self.m, np.int64)
+            g_slot = np.searchsorted(upid, gp)
+            for cam in np.unique(qc):
+                per_pid = np.bincount(g_slot[((gc >> cam) & 1) != 0], minlength=max(len(upid), 1))
+                sel = hit & (qc == cam)
+                same_cam[sel] = per_pid[slot_c[sel]]
+        else:
+            # same pid AND same camera (the removed entries): count through a combined key
+            cmin = int(min(gc.min(initial=0), qc.min(initial=0)))
+            span = int(max(gc.max(initial=0), qc.max(initial=0))) - cmin + 1
+            pmin = int(min(gp.min(initial=0), qp.min(initial=0)))
+            gk = (gp - pmin) * span + (gc - cmin)
+            qk = (qp - pmin) * span + (qc - cmin)
+            uk, cnt = np.unique(gk, return_counts=True)
+            ks = np.searchsorted(uk, qk)
+            ks_c = np.minimum(ks, max(len(uk) - 1, 0))
+            same_cam = np.where((ks < len(uk)) & (uk[ks_c] == qk), cnt[ks_c], 0) if len(uk) else np.zeros(self.m, np.int64)
         self._n_pos = (same_pid - same_cam).astype(np.int64)
         self.overflow = np.nonzero(self._n_pos > self.MAX_CAP)[0]
         mx = int(self._n_pos[self._n_pos <= self.MAX_CAP].max(initial=1))
@@ -786,18 +850,22 @@ def _stream_eval(fq, fg, qq, gg, plan: StreamPlan):
     pos_idx = torch.empty((m, cap), dtype=torch.int32, device=dev)
     npos = torch.empty(m, dtype=torch.int32, device=dev)
     hist = torch.zeros((m, cap), dtype=torch.int32, device=dev)
+    # camera sets only change which same-pid entries are positives: another poslist, the same count and finalize
+    camsets = plan.camsets
     if h16:
         dt = L.dtype_code(fq)
-        L.check(lib.creid_stream_poslist_h16(L.ptr(fq), L.ptr(fg), L.ptr(qq), L.ptr(gg), m, n, D, dt, L.ptr(plan.q_slot),
-                                             L.ptr(plan.csr_off), L.ptr(plan.g_order), L.ptr(plan.q_cams), L.ptr(plan.g_cams),
-                                             cap, L.ptr(pos_key), L.ptr(pos_idx), L.ptr(npos), st), "creid_stream_poslist_h16")
+        poslist = lib.creid_stream_poslist_h16_camsets if camsets else lib.creid_stream_poslist_h16
+        L.check(poslist(L.ptr(fq), L.ptr(fg), L.ptr(qq), L.ptr(gg), m, n, D, dt, L.ptr(plan.q_slot),
+                        L.ptr(plan.csr_off), L.ptr(plan.g_order), L.ptr(plan.q_cams), L.ptr(plan.g_cams),
+                        cap, L.ptr(pos_key), L.ptr(pos_idx), L.ptr(npos), st), "creid_stream_poslist_h16")
         L.check(lib.creid_stream_count_h16(L.ptr(fq), L.ptr(fg), L.ptr(qq), L.ptr(gg), m, n, D, dt, L.ptr(plan.q_pids),
                                            L.ptr(plan.g_pids), cap, L.ptr(pos_key), L.ptr(pos_idx), L.ptr(npos), L.ptr(hist),
                                            st), "creid_stream_count_h16")
     else:
-        L.check(lib.creid_stream_poslist(L.ptr(fq), L.ptr(fg), L.ptr(qq), L.ptr(gg), m, n, D, L.ptr(plan.q_slot),
-                                         L.ptr(plan.csr_off), L.ptr(plan.g_order), L.ptr(plan.q_cams), L.ptr(plan.g_cams), cap,
-                                         L.ptr(pos_key), L.ptr(pos_idx), L.ptr(npos), st), "creid_stream_poslist")
+        poslist = lib.creid_stream_poslist_camsets if camsets else lib.creid_stream_poslist
+        L.check(poslist(L.ptr(fq), L.ptr(fg), L.ptr(qq), L.ptr(gg), m, n, D, L.ptr(plan.q_slot),
+                        L.ptr(plan.csr_off), L.ptr(plan.g_order), L.ptr(plan.q_cams), L.ptr(plan.g_cams), cap,
+                        L.ptr(pos_key), L.ptr(pos_idx), L.ptr(npos), st), "creid_stream_poslist")
         L.check(lib.creid_stream_count(L.ptr(fq), L.ptr(fg), L.ptr(qq), L.ptr(gg), m, n, D, L.ptr(plan.q_pids),
                                        L.ptr(plan.g_pids), cap, L.ptr(pos_key), L.ptr(pos_idx), L.ptr(npos), L.ptr(hist), st),
                 "creid_stream_count")
@@ -909,9 +977,10 @@ class R1_mAP:
 
     def __init__(self, pl_module=None, num_query=0, max_rank=50, feat_norm=True, dist_func="euclidean",
                  compute_dtype=torch.float32, streamed=False, reranking=False, prefilter=None, prefilter_capacity=None):
-        """streamed=True: metric-only evaluation that never materialises the distance / index matrices (euclidean,
-        plain camera ids; compute_dtype fp32, bf16 or f16 -- the 16-bit modes run the 16-bit MFMA and return exactly what
-        their materialised evaluation returns); `last` then holds the per-query results only.  streamed=False keeps
+        """streamed=True: metric-only evaluation that never materialises the distance / index matrices (euclidean; plain
+        camera ids or, with compute(respect_camids=True), camera sets; compute_dtype fp32, bf16 or f16 -- the 16-bit modes
+        run the 16-bit MFMA and return exactly what their materialised evaluation returns); `last` then holds the per-query
+        results only.  streamed=False keeps
         `last["distmat"]` / `last["indices"]` (what the rank-index parity tests and get_similar read).
         reranking=True (the defaults of re_ranking) or a dict of k1 / k2 / lambda_value: on the materialised euclidean fp32 path
         the k-reciprocal re-ranked matrix takes the place of `distmat`; ranking and evaluation are unchanged.  CreidError with
@@ -962,9 +1031,8 @@ class R1_mAP:
             raise L.CreidError("R1_mAP(prefilter=...) evaluates plain camera ids: not with respect_camids=True")
         feats = _pad_width(feats.float().contiguous())
         nq = self.num_query
-        if (self.streamed and self.dist_name == "euclidean" and not respect_camids
-                and self.compute_dtype in (torch.float32,) + _H16):
-            return self._compute_streamed(feats, pids, camids)
+        if self.streamed and self.dist_name == "euclidean" and self.compute_dtype in (torch.float32,) + _H16:
+            return self._compute_streamed(feats, pids, camids, camsets=bool(respect_camids))
         if self.dist_name == "euclidean":
             if self.feat_norm:
                 print("The test feature is normalized")
@@ -1001,8 +1069,13 @@ class R1_mAP:
         self.last = dict(distmat=distmat, indices=indices, single_performance=single, valid=valid, ap=ap, first=first)
         return pack[:max_rank].astype(np.float32), float(pack[max_rank]), pack[max_rank + 1:max_rank + 6].copy()
 
-    def _compute_streamed(self, feats, pids, camids, plan=None, _normed=None, _clock=None):
+    def _compute_streamed(self, feats, pids, camids, plan=None, _normed=None, _clock=None, camsets=False):
+        """camsets: `camids` is the respect_camids=True argument (a list of camera-id lists, or a CameraSets); the gallery
+        entries' sets become bitmasks and the same three launches run on them (StreamPlan(camsets=True))."""
         nq = self.num_query
+        camids_arg, g_masks = camids, None
+        if camsets:
+            q_cams, g_masks = _camset_split(camids, nq)           # (raises before anything is launched)
         if _normed is not None:                 # the redo of a failed speculation: rows already normalised, nothing printed twice
             f, sq = _normed
         else:
@@ -1015,7 +1088,15 @@ class R1_mAP:
             else:
                 f = feats if self.compute_dtype == torch.float32 else feats.to(self.compute_dtype)
                 sq = row_sqnorm(f)
-        pids = np.asarray(pids); camids = np.asarray(camids)
+        pids = np.asarray(pids)
+        hint_key = (nq, len(pids) - nq) + (("camsets",) if camsets else ())       # (a capacity learnt on sets is no guide for ids)
+        plan_kw = {}
+        if camsets:
+            on_dev = isinstance(g_masks, torch.Tensor)
+            camids = q_cams if on_dev else np.concatenate([q_cams, g_masks])      # plain query cameras, then the masks
+            plan_kw = dict(camsets=True, g_cam_masks=g_masks if on_dev else None)
+        else:
+            camids = np.asarray(camids)
         speculative = False
         if plan is None:
             # index built on the device BEHIND the normalisation launch.  Its 8-byte read-back (finish: the positive-list
@@ -1023,8 +1104,8 @@ class R1_mAP:
             # earlier one instead ASSUMES that call's capacity, enqueues everything, and checks the assumption against the
             # plan's statistics in the final read-back (wrong -> the contraction is redone with the right capacity; a capacity
             # larger than needed gives identical results)
-            plan = StreamPlan.on_device(pids, camids, nq, feats.device)
-            hint = _CAP_HINT.get((plan.m, plan.n)) if os.environ.get("CREID_EVAL_SPECULATE", "1") == "1" else None
+            plan = StreamPlan.on_device(pids, camids, nq, feats.device, **plan_kw)
+            hint = _CAP_HINT.get(hint_key) if os.environ.get("CREID_EVAL_SPECULATE", "1") == "1" else None
             if plan.cap is None and hint:        # 0 = "do not speculate": the last label set of this shape had overflow queries
                 plan.cap, plan.overflow, speculative = hint, np.zeros(0, np.int64), True
         if plan.cap is None:
@@ -1045,7 +1126,7 @@ class R1_mAP:
             d = get_euclidean(fq.index_select(0, rows), fg, qq.index_select(0, rows), gg)
             idx = rank_rows(d)
             _, _, _, _, v2, a2, f2 = eval_func_device(idx, pids[:nq][plan.overflow], plan.g_pids, camids[:nq][plan.overflow],
-                                                      plan.g_cams, self.max_rank)
+                                                      plan.g_cams, self.max_rank, camsets=camsets)
             valid.index_copy_(0, rows, v2); ap.index_copy_(0, rows, a2); first.index_copy_(0, rows, f2)
         max_rank = min(self.max_rank, fg.shape[0])
         cmc, mAP, topk, _ = eval_reduce_device(valid, ap, first, max_rank)
@@ -1062,13 +1143,14 @@ class R1_mAP:
             nover = int(pack[-1])
             # a label set with overflow queries (> 128 positives) cannot be speculated on (their list is only known to the
             # synchronous plan): remember that instead of a capacity, so that evaluations of this shape stop redoing
-            _CAP_HINT[(plan.m, plan.n)] = 0 if nover > 0 else need
+            _CAP_HINT[hint_key] = 0 if nover > 0 else need
             if need > plan.cap or nover > 0:                     # the assumed capacity was too small: redo, synchronously
                 plan.cap = None
                 plan.finish()
-                return self._compute_streamed(feats, pids, camids, plan=plan, _normed=(f, sq), _clock=clock if pf is not None else None)
+                return self._compute_streamed(feats, pids, camids_arg, plan=plan, _normed=(f, sq),
+                                              _clock=clock if pf is not None else None, camsets=camsets)
         elif getattr(plan, "_stats", None) is not None:
-            _CAP_HINT[(plan.m, plan.n)] = 0 if len(plan.overflow) else plan.cap
+            _CAP_HINT[hint_key] = 0 if len(plan.overflow) else plan.cap
         pack = pack[:-2]
         info = None
         if pf is not None:
@@ -1103,20 +1185,26 @@ class R1_mAP:
             self.last["prefilter"] = info
         return cmc_h, mAP_h, topk_h
 
-    def compute_chunked(self, feats, pids, camids, query_chunk=4096):
+    def compute_chunked(self, feats, pids, camids, query_chunk=4096, respect_camids=False):
         """Galleries whose m x n matrix must not be materialised (the reference's `_commpute_batches_double` path,
         utils/reid_metric.py:93-110,126-129, chunks the gallery on the host): the euclidean distance (fp32, bf16 or f16
         compute dtype) goes through the streamed kernels in ONE pass with no matrix at all; the cosine distance processes
-        `query_chunk` query rows at a time (distance tile, rank, CMC/AP scan on the device, only per-query results kept)."""
+        `query_chunk` query rows at a time (distance tile, rank, CMC/AP scan on the device, only per-query results kept).
+        respect_camids=True (camera sets, as in compute()): the streamed kernels only -- CreidError with the cosine distance."""
         if not isinstance(feats, torch.Tensor) or not feats.is_cuda:
             raise L.CreidError("R1_mAP.compute_chunked needs device features (no CPU fallback)")
         if self.reranking is not None:
             raise L.CreidError("R1_mAP.compute_chunked never holds the [nq, ng] matrix that reranking replaces: use compute()")
+        if self.prefilter is not None and respect_camids:
+            raise L.CreidError("R1_mAP(prefilter=...) evaluates plain camera ids: not with respect_camids=True")
         from .parallel import merge_eval_results
         euclid = self.dist_name == "euclidean"
         feats = _pad_width(feats.float().contiguous())
         if euclid and self.compute_dtype in (torch.float32,) + _H16:
-            return self._compute_streamed(feats, pids, camids)
+            return self._compute_streamed(feats, pids, camids, camsets=bool(respect_camids))
+        if respect_camids:
+            raise L.CreidError("R1_mAP.compute_chunked(respect_camids=True) runs the streamed euclidean kernels only "
+                               f"(dist_func={self.dist_name!r}, compute_dtype={self.compute_dtype})")
         nq = self.num_query
         if not euclid:
             # SOLVER.DISTANCE_FUNC = cosine (utils/reid_metric.py:51-59,93-110 works with either function): the same

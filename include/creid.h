@@ -146,6 +146,44 @@ int creid_stream_count(const float* q, const float* g, const float* qq, const fl
 int creid_stream_finalize(const int32_t* npos, const uint32_t* hist, int64_t m, int32_t cap, uint8_t* valid,
                           double* ap, int32_t* first, void* stream);
 
+/* The streamed evaluation for gallery entries that carry camera SETS (respect_camids=True: the camera-aware centroids of
+ * modelling/bases.py:205-236, or any gallery of camera sets): g_cam_masks int64 [n], bit c set = camera c in the entry's
+ * set; q_cams plain camera ids, which the CALLER keeps inside 0..62 (the kernels shift a 64-bit mask by them).  A same-pid
+ * entry is removed for a query iff the query's camera is in its set (utils/eval_reid.py:51-55, the test of
+ * creid_cmc_ap_ranked_camsets); everything else -- arguments, limits, outputs -- is creid_stream_plan / creid_stream_poslist.
+ * Camera sets only change which same-pid entries are positives, so creid_stream_count and creid_stream_finalize (and
+ * creid_stream_count_h16) serve both forms unchanged. */
+int creid_stream_plan_camsets(const int64_t* q_pids, const int64_t* g_pids, const int64_t* q_cams,
+                              const int64_t* g_cam_masks, int64_t m, int64_t n, int64_t pmin, int64_t R, int64_t* csr_off,
+                              int32_t* g_order, int32_t* q_slot, int32_t* n_pos, int32_t* stats, int32_t* scratch,
+                              void* stream);
+int creid_stream_poslist_camsets(const float* q, const float* g, const float* qq, const float* gg, int64_t m, int64_t n,
+                                 int64_t D, const int32_t* q_slot, const int64_t* csr_off, const int32_t* g_order,
+                                 const int64_t* q_cams, const int64_t* g_cam_masks, int32_t cap, uint32_t* pos_key,
+                                 int32_t* pos_idx, int32_t* npos, void* stream);
+
+/* ---- camera-aware centroid index on the device (csrc/centroid_index.hip): the grouping loop of modelling/bases.py:205-236.
+ * labels int64 [2][num_query + num_gallery] on the device: row 0 the pids, row 1 the camera ids, queries first.  The camera of
+ * gallery row j is labels[1][j] (the reference indexes the full vector with the gallery-relative index, :214 -- kept), a
+ * query's is labels[1][i]; the CALLER keeps labels[1][0 .. max(num_query, num_gallery)) inside 0..62.  [pmin, pmin + R) must
+ * cover every gallery pid.  Per gallery pid (ascending) that has a query, with gmask / qmask the OR of its rows' / queries'
+ * cameras, for cur over the bits of qmask (ascending): cur in gmask -> one centroid of the rows whose camera is not cur, with
+ * set gmask & ~(1 << cur), nothing when that set is empty; cur not in gmask -> the first such cur gives one centroid of all
+ * the pid's rows with set gmask, later ones nothing.
+ *  ws_bytes: size of the workspace `ws` (0 for an empty gallery or range).
+ *  plan    : counting sort + sizes; totals int64 [2] on the device = {n_cent, rows}: the one read-back, which sizes:
+ *  fill    : order int64 [rows] (full-vector row numbers = gallery index + num_query, ascending inside a centroid: the order
+ *            creid_gather_mean_rows sums in), offsets int64 [n_cent + 1], cent_labels int64 [n_cent] (the pid), cent_masks
+ *            int64 [n_cent] (bit c = camera c).  ws, labels and the sizes as given to / read from `plan`.
+ * Integer atomics only: the arrays do not depend on the run.  CREID_E_SHAPE when num_query + num_gallery >= 2^31 - 16 or
+ * R > 2^26. */
+size_t creid_centroid_index_ws_bytes(int64_t num_gallery, int64_t R);
+int creid_centroid_index_plan(const int64_t* labels, int64_t num_query, int64_t num_gallery, int64_t pmin, int64_t R,
+                              void* ws, int64_t* totals, void* stream);
+int creid_centroid_index_fill(const int64_t* labels, int64_t num_query, int64_t num_gallery, int64_t pmin, int64_t R,
+                              const void* ws, int64_t n_cent, int64_t rows, int64_t* order, int64_t* offsets,
+                              int64_t* cent_labels, int64_t* cent_masks, void* stream);
+
 /* ---- top-k retrieval with NO m x n matrix (csrc/stream_eval.hip): what creid_sqdist_matrix (fp32) + creid_topk_rows
  * return -- the same indices and the same distance bits, ties by gallery index -- from the streamed contraction.
  *  collect : q fp32 [m][D], g fp32 [n][D], qq / gg their row square norms, D % 4 == 0.  tau fp32 [m]: ANY upper bound
@@ -180,6 +218,11 @@ int creid_stream_poslist_h16(const void* q, const void* g, const float* qq, cons
                              int64_t D, int dtype, const int32_t* q_slot, const int64_t* csr_off, const int32_t* g_order,
                              const int64_t* q_cams, const int64_t* g_cams, int32_t cap, uint32_t* pos_key,
                              int32_t* pos_idx, int32_t* npos, void* stream);
+/* (camera-set gallery entries: see creid_stream_poslist_camsets) */
+int creid_stream_poslist_h16_camsets(const void* q, const void* g, const float* qq, const float* gg, int64_t m, int64_t n,
+                                     int64_t D, int dtype, const int32_t* q_slot, const int64_t* csr_off,
+                                     const int32_t* g_order, const int64_t* q_cams, const int64_t* g_cam_masks, int32_t cap,
+                                     uint32_t* pos_key, int32_t* pos_idx, int32_t* npos, void* stream);
 int creid_stream_count_h16(const void* q, const void* g, const float* qq, const float* gg, int64_t m, int64_t n,
                            int64_t D, int dtype, const int64_t* q_pids, const int64_t* g_pids, int32_t cap,
                            const uint32_t* pos_key, const int32_t* pos_idx, const int32_t* npos, uint32_t* hist,
