@@ -62,6 +62,7 @@ SIGNATURES = {
     "creid_rerank_weights": (C.c_int, [_p, _p, _p, _i64, _i64, _p, _p, _p, _p]),
     "creid_rerank_expand": (C.c_int, [_p, _i64, _i32, _i32, _p, _p, _p, _i32, _p, _p, _p, _p, _p]),
     "creid_rerank_blend": (C.c_int, [_p, _p, _i64, _i64, _f32, _p, _p, _p, _p, _p, _i32, _p, _p]),
+    "creid_neighbour_expand": (C.c_int, [_p, _i64, _p, _p, _p, _i64, _i32, _i64, _f32, _p, _p]),
     "creid_tune_set": (C.c_int, [_i32, _i64, _i64, _i64, _i64, _i32, _i32, _i32]),
     "creid_tune_clear": (C.c_int, []),
     "creid_tune_count": (_i64, [_i32, _i64, _i64, _i64, _i64, _i32]),

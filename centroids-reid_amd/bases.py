@@ -146,11 +146,15 @@ def load_checkpoint_file(path, map_location="cpu"):
 
 
 class ModelBase(_Base):
-    def __init__(self, cfg=None, test_dataloader=None, compute_dtype=None, eval_precision=None, eval_prefilter=None, **kwargs):
+    def __init__(self, cfg=None, test_dataloader=None, compute_dtype=None, eval_precision=None, eval_prefilter=None,
+                 eval_query_expansion=None, **kwargs):
         """eval_prefilter=torch.bfloat16 | torch.float16: get_val_metrics runs its streamed evaluation with the counting
-        contraction on the 16-bit MFMA and the fp32 results (R1_mAP(prefilter=...)); not with camera-aware centroids."""
+        contraction on the 16-bit MFMA and the fp32 results (R1_mAP(prefilter=...)); not with camera-aware centroids.
+        eval_query_expansion=True | a dict of k / alpha / rounds / scope: get_val_metrics expands the normalised rows by their
+        nearest neighbours before ranking (R1_mAP(query_expansion=...); needs TEST.FEAT_NORM)."""
         super().__init__()
         self.eval_prefilter = eval_prefilter
+        self.eval_query_expansion = eval_query_expansion
         if cfg is None:
             hparams = {**kwargs}
         elif isinstance(cfg, dict):
@@ -386,7 +390,8 @@ class ModelBase(_Base):
         respect_camids = bool(self.hparams.MODEL.KEEP_CAMID_CENTROIDS and self.hparams.MODEL.USE_CENTROIDS)
         self.r1_map_func = R1_mAP(pl_module=self, num_query=self.hparams.num_query,
                                   feat_norm=self.hparams.TEST.FEAT_NORM, streamed=True,   # only the metrics are used
-                                  prefilter=None if respect_camids else self.eval_prefilter)
+                                  prefilter=None if respect_camids else self.eval_prefilter,
+                                  query_expansion=getattr(self, "eval_query_expansion", None))
         cmc, mAP, all_topk = self.r1_map_func.compute(feats=embeddings.float(), pids=labels, camids=camids,
                                                       respect_camids=respect_camids)
         topks = {}

@@ -170,7 +170,7 @@ def _select_rows(distmat, topk):
 
 def get_similar(embeddings, paths, embeddings_gallery, paths_gallery, topk=0, normalize_features=True,
                 distance_func="euclidean", streamed="auto", stats=None, compute_dtype=torch.float32, reranking=False,
-                prefilter=None):
+                prefilter=None, query_expansion=False):
     """inference/get_similar.py:99-125 -> {query_path: {"indices", "paths", "distances"}} (numpy arrays).
 
     streamed: False -- the m x n distance matrix is written and every row selected from it (get_dist_func + topk_rows /
@@ -187,12 +187,20 @@ def get_similar(embeddings, paths, embeddings_gallery, paths_gallery, topk=0, no
     prefilter: torch.bfloat16 or torch.float16 -- reid_metric.topk_stream(prefilter=...): the fp32 result, bit for bit, with the
     contraction on the 16-bit MFMA.  "auto" then streams whenever the call is streamable (squared L2, 1 <= k <= 1024), whatever
     the matrix size; CreidError with streamed=False, a 16-bit compute_dtype, reranking, or a call that cannot stream.
+    query_expansion: True (the defaults of reid_metric.query_expansion) or a dict of k / alpha / rounds / scope -- the normalised
+    rows are expanded by their nearest neighbours before the search (fp32 arithmetic, the last normalisation into compute_dtype;
+    blind to labels; `prefilter` also goes to its neighbour search) and every path then runs on the expanded rows, as it would on
+    reid_metric.query_expansion's result with normalize_features=False.  CreidError, before any upload, with
+    normalize_features=False: expansion is defined on unit rows.  stats["query_expansion"] holds the options and its stats.
     stats (a dict) receives "path" ("materialised" | "streamed" | "chunked" | "reranked"), topk_stream's counters ("prefilter"
     among them: what ran) and re_ranking's statistics."""
     rr = rm.rerank_options(reranking)
     if rr is not None and (streamed is True or compute_dtype != torch.float32 or distance_func != "euclidean"):
         raise L.CreidError("get_similar(reranking=...) re-ranks the materialised squared-L2 fp32 matrix: not with streamed=True, "
                            f"compute_dtype={compute_dtype} or distance_func={distance_func!r}")
+    qe = rm.expansion_options(query_expansion)
+    if qe is not None and not normalize_features:
+        raise L.CreidError("get_similar(query_expansion=...) expands unit rows: not with normalize_features=False")
     if streamed not in (True, False, "auto"):
         raise ValueError(f"streamed must be True, False or 'auto', got {streamed!r}")
     if prefilter is not None:
@@ -205,7 +213,10 @@ def get_similar(embeddings, paths, embeddings_gallery, paths_gallery, topk=0, no
         raise L.CreidError(f"get_similar: compute_dtype must be torch.float32, torch.bfloat16 or torch.float16, got {compute_dtype}")
     q = torch.as_tensor(np.asarray(embeddings, np.float32)).cuda() if not isinstance(embeddings, torch.Tensor) else embeddings.float().cuda()
     g = torch.as_tensor(np.asarray(embeddings_gallery, np.float32)).cuda() if not isinstance(embeddings_gallery, torch.Tensor) else embeddings_gallery.float().cuda()
-    if normalize_features:
+    qe_info = {}
+    if qe is not None:
+        q, g = rm.query_expansion(q.contiguous(), g.contiguous(), **qe, prefilter=prefilter, out_dtype=compute_dtype, stats=qe_info)
+    elif normalize_features:
         q, g = rm.l2_normalize(q.contiguous(), out_dtype=compute_dtype), rm.l2_normalize(g.contiguous(), out_dtype=compute_dtype)
     elif compute_dtype != torch.float32:
         q, g = q.to(compute_dtype), g.to(compute_dtype)
@@ -236,6 +247,8 @@ def get_similar(embeddings, paths, embeddings_gallery, paths_gallery, topk=0, no
     else:
         idx, dist_sel = _similar_materialised(q, g, topk, distance_func)
         info["path"] = "materialised"
+    if qe is not None:
+        info["query_expansion"] = {**qe, **qe_info}
     if stats is not None:
         stats.update(info)
     paths_gallery = np.asarray(paths_gallery)

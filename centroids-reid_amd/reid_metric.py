@@ -566,6 +566,191 @@ def re_ranking(q: torch.Tensor, g: torch.Tensor, k1: int = 20, k2: int = 6, lamb
     return out
 
 
+QE_DEFAULTS = dict(k=10, alpha=3.0, rounds=1, scope="all")
+QE_SCOPES = ("all", "query")
+
+
+def expansion_options(query_expansion):
+    """The `query_expansion=` argument of R1_mAP / get_similar: False / None -> None; True -> the defaults of query_expansion; a
+    dict of k / alpha / rounds / scope -> those over the defaults (their values are checked, shapes apart, so that a constructor
+    refuses them before any device work)."""
+    if query_expansion is None or query_expansion is False:
+        return None
+    if query_expansion is True:
+        return dict(QE_DEFAULTS)
+    if isinstance(query_expansion, dict) and set(query_expansion) <= set(QE_DEFAULTS):
+        opts = {**QE_DEFAULTS, **query_expansion}
+        _check_expansion(opts["k"], opts["alpha"], opts["rounds"], opts["scope"])
+        return opts
+    raise L.CreidError(f"query_expansion must be False, True or a dict of k / alpha / rounds / scope, got {query_expansion!r}")
+
+
+def _is_int(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+
+def _check_expansion(k, alpha, rounds, scope):
+    """The limits of query_expansion that do not depend on the features -> (k, alpha, rounds) as Python numbers."""
+    if scope not in QE_SCOPES:
+        raise L.CreidError(f"query_expansion: scope must be 'all' or 'query', got {scope!r}")
+    if not _is_int(k) or k < 1 or k - (scope == "query") > 1024:
+        raise L.CreidError(f"query_expansion: k = {k!r} must be an integer, 1 .. {1024 + (scope == 'query')} for scope={scope!r}")
+    if not _is_int(rounds) or rounds < 1:
+        raise L.CreidError(f"query_expansion: rounds = {rounds!r} must be an integer >= 1")
+    if isinstance(alpha, bool) or not isinstance(alpha, (int, float, np.integer, np.floating)) or not np.isfinite(alpha) or alpha < 0:
+        raise L.CreidError(f"query_expansion: alpha = {alpha!r} must be a finite number >= 0")
+    return int(k), float(alpha), int(rounds)
+
+
+def _neighbour_expand(x, idx, dist, alpha, self_rows):
+    """creid_neighbour_expand on checked arguments (x and self_rows of one width, a multiple of 4)."""
+    m, k = idx.shape
+    out = torch.empty((m, x.shape[1]), dtype=torch.float32, device=x.device)
+    L.check(L.lib().creid_neighbour_expand(L.ptr(x), x.shape[0], L.ptr(idx), L.ptr(dist), L.ptr(self_rows), m, k, x.shape[1],
+                                           alpha, L.ptr(out), L.stream()), "creid_neighbour_expand")
+    return out
+
+
+def neighbour_expand(x: torch.Tensor, idx: torch.Tensor, dist, alpha: float, self_rows=None) -> torch.Tensor:
+    """S [m, D] fp32, S[i] = [self_rows[i] +] sum_t w[i, t] x[idx[i, t]] (creid_neighbour_expand, csrc/neighbour_expand.hip):
+    x fp32 [n_src, D], idx int64 [m, k] (k may be 0), dist fp32 [m, k] -- squared L2 of unit rows as topk_stream returns it --
+    self_rows fp32 [m, D] or None.  sim = min(max(fmaf(-0.5, dist, 1), 0), 1); w = 1 for alpha == 0 (dist may then be None),
+    sim for alpha == 1, else (float) pow((double) sim, (double) alpha).  Each element is an fp32 fmaf chain from 0 in the order
+    self row, t = 0, 1, ...: two calls give the same bits, and a row's bits do not depend on the other rows of the call.
+    CreidError, before anything is launched: CPU or non-contiguous tensors, other dtypes or shapes, alpha negative or not
+    finite, an index outside [0, n_src) (one 16-byte read-back)."""
+    if not all(isinstance(t, torch.Tensor) for t in (x, idx)) or not all(t is None or isinstance(t, torch.Tensor) for t in (dist, self_rows)):
+        raise L.CreidError("neighbour_expand needs device tensors (no CPU fallback)")
+    L.require_gpu(x, idx, dist, self_rows)
+    alpha = _check_expansion(1, alpha, 1, "all")[1]
+    if x.dtype != torch.float32 or x.dim() != 2 or idx.dtype != torch.int64 or idx.dim() != 2 or x.shape[1] < 1:
+        raise L.CreidError("neighbour_expand needs fp32 rows [n_src, D] and int64 indices [m, k]")
+    if dist is None and alpha != 0.0:
+        raise L.CreidError("neighbour_expand: dist may be None only with alpha == 0")
+    if dist is not None and (dist.dtype != torch.float32 or dist.shape != idx.shape):
+        raise L.CreidError("neighbour_expand needs fp32 distances of the indices' shape")
+    m, k = idx.shape
+    if self_rows is not None and (self_rows.dtype != torch.float32 or self_rows.shape != (m, x.shape[1])):
+        raise L.CreidError("neighbour_expand needs fp32 self_rows [m, D] of the rows' width")
+    if m and k:
+        lo, hi = (int(v) for v in torch.stack(torch.aminmax(idx)).tolist())
+        if lo < 0 or hi >= x.shape[0]:
+            raise L.CreidError(f"neighbour_expand: indices {lo} .. {hi} outside [0, n_src = {x.shape[0]})")
+    D = x.shape[1]
+    out = _neighbour_expand(_pad_width(x), idx, dist, alpha, None if self_rows is None else _pad_width(self_rows))
+    return out if out.shape[1] == D else out[:, :D].contiguous()
+
+
+def _expanded_rows(X, nq, k, alpha, rounds, scope, prefilter, out_dtype, stats):
+    """query_expansion on X = cat(q, g), fp32 [N, D] with D % 4 == 0 and checked options -> (rows [N, D] in out_dtype, their
+    square norms fp32 [N] as l2_normalize returns them).  A round is the whole step, its first normalisation included, so that
+    rounds = 2 returns the bits of two calls; only the last round's last normalisation writes out_dtype."""
+    timing = bool(stats) and bool(stats.get("timing"))
+    per_round, stage_ms = [], []
+    for r in range(rounds):
+        dt = out_dtype if r == rounds - 1 else torch.float32
+        clock = _StageClock(timing)
+        info = {}
+        if scope == "all":
+            U = l2_normalize(X)
+            clock.mark("normalise")
+            idx, d = topk_stream(U, U, k, prefilter=prefilter, stats=info)
+            clock.mark("search")
+            S = _neighbour_expand(U, idx, d, alpha, None)
+            clock.mark("expand")
+            del U, idx, d
+            X, sq = l2_normalize(S, out_dtype=dt, return_sqnorm=True)
+        else:
+            # the gallery's rows are final after the normalisation (rounded once when dt is 16-bit); the search reads the fp32 ones
+            Uq, (Ug, gg) = l2_normalize(X[:nq]), l2_normalize(X[nq:], return_sqnorm=True)
+            g_out = Ug
+            if dt != torch.float32:
+                g_out, gg = l2_normalize(X[nq:], out_dtype=dt, return_sqnorm=True)
+            clock.mark("normalise")
+            if k > 1:
+                idx, d = topk_stream(Uq, Ug, k - 1, prefilter=prefilter, stats=info)
+            else:
+                idx = torch.empty((nq, 0), dtype=torch.int64, device=X.device)
+                d = torch.empty((nq, 0), dtype=torch.float32, device=X.device)
+            clock.mark("search")
+            S = _neighbour_expand(Ug, idx, d, alpha, Uq)
+            clock.mark("expand")
+            del Uq, Ug, idx, d
+            q_out, qq = l2_normalize(S, out_dtype=dt, return_sqnorm=True)
+            X, sq = torch.cat([q_out, g_out]), torch.cat([qq, gg])
+            del q_out, g_out
+        del S
+        clock.mark("normalise")
+        info.pop("kept", None)                              # (a device tensor of the pre-filtered search; the counters stay)
+        per_round.append(info)
+        if timing:
+            clock.marks[-1][1].synchronize()
+            ms = {}
+            for (_, prev), (name, ev) in zip(clock.marks, clock.marks[1:]):         # both normalisations under one name
+                ms[name] = ms.get(name, 0.0) + prev.elapsed_time(ev)
+            stage_ms.append(ms)
+    if stats is not None:
+        stats.update(per_round[-1], rounds_stats=per_round)
+        if timing:
+            stats["stage_ms"] = stage_ms
+    return X, sq
+
+
+def query_expansion(q: torch.Tensor, g: torch.Tensor, k: int = 10, alpha: float = 3.0, rounds: int = 1, scope: str = "all", *,
+                    prefilter=None, out_dtype=torch.float32, return_sqnorm=False, stats=None):
+    """Neighbour-based feature expansion of fp32 device features q [nq, D], g [ng, D] -> (q', g'), unit rows: average query
+    expansion (Chum et al., ICCV 2007) with the alpha weighting of Radenovic et al. (TPAMI 2019), and -- scope="all" -- the
+    database-side augmentation of Arandjelovic and Zisserman (CVPR 2012) with it.  Every row is replaced by the
+    similarity-weighted sum of its nearest neighbours, normalised again; rank the result like any other features.
+
+    U = l2_normalize(cat(q, g)); d = topk_stream's squared L2, every ordering by (d, index);
+    sim = min(max(fmaf(-0.5, d, 1), 0), 1) (the cosine of unit rows); w = 1 for alpha == 0, sim for alpha == 1, else
+    (float) pow((double) sim, (double) alpha).
+      scope="all":   (idx, d) = topk_stream(U, U, k) over all N = nq + ng rows -- a row's own entry is one of its neighbours like
+                     any other --; S[i] = sum_t w[i, t] U[idx[i, t]].
+      scope="query": (idx, d) = topk_stream(Uq, Ug, k - 1); S[i] = Uq[i] + sum_t w[i, t] Ug[idx[i, t]]; the gallery rows are
+                     l2_normalize(g) and nothing else (k = 1: no search, S = Uq).
+    U' = l2_normalize(S); rounds = r repeats the whole step on U', its first normalisation included: the bits of r calls.
+    S is an fp32 fmaf chain in the order of t (neighbour_expand), so the result does not depend on launch order: two calls
+    return the same bits.
+    Expansion is blind to labels: it sees neither pids nor cameras, so the neighbours it averages include gallery rows of the
+    query's own identity taken by the query's own camera -- the entries the evaluation later removes from the ranking.
+    prefilter = torch.bfloat16 | torch.float16 goes to topk_stream only (the same neighbour table with the contraction on the
+    16-bit MFMA), so the result keeps its bits.  out_dtype: the dtype of the LAST normalisation (bf16 / f16: the rows the 16-bit
+    evaluation modes use, rounded once; all expansion arithmetic stays fp32).  return_sqnorm=True -> (q', g', qq, gg), the square
+    norms l2_normalize returns with the rows.
+    Temporaries: the [N, k] neighbour tables, topk_stream's bounded chunks, and [N, D] fp32 buffers for the rows and their sums.
+    stats (a dict) receives topk_stream's counters of the last round, rounds_stats (one dict per round) and -- when it comes in
+    holding timing=True -- stage_ms: one dict per round (search, expand, normalise; between device events).
+    Limits (CreidError, before anything is launched): CPU tensors; not fp32 [nq, D] / [ng, D] of one width; scope="all":
+    k outside 1 .. min(N, 1024); scope="query": k < 1 or k - 1 > min(ng, 1024); alpha negative or not finite; rounds < 1."""
+    if not isinstance(q, torch.Tensor) or not isinstance(g, torch.Tensor):
+        raise L.CreidError("query_expansion needs device tensors (no CPU fallback)")
+    k, alpha, rounds = _check_expansion(k, alpha, rounds, scope)
+    L.require_gpu(q, g)
+    if q.dtype != torch.float32 or g.dtype != torch.float32 or q.dim() != 2 or g.dim() != 2 or q.shape[1] != g.shape[1]:
+        raise L.CreidError("query_expansion needs fp32 [nq, D] and [ng, D] features of one width")
+    if prefilter is not None and prefilter not in _H16:
+        raise L.CreidError(f"query_expansion: prefilter must be torch.bfloat16, torch.float16 or None, got {prefilter}")
+    if out_dtype not in (torch.float32,) + _H16:
+        raise L.CreidError(f"query_expansion: out_dtype must be torch.float32, torch.bfloat16 or torch.float16, got {out_dtype}")
+    nq, D = q.shape
+    _check_expansion_shape(k, scope, nq, g.shape[0])
+    X = _pad_width(torch.cat([q, g]).contiguous())
+    U, sq = _expanded_rows(X, nq, k, alpha, rounds, scope, prefilter, out_dtype, stats)
+    if U.shape[1] != D:
+        U = U[:, :D]
+    qo, go = U[:nq].contiguous(), U[nq:].contiguous()
+    return (qo, go, sq[:nq].contiguous(), sq[nq:].contiguous()) if return_sqnorm else (qo, go)
+
+
+def _check_expansion_shape(k, scope, nq, ng):
+    if scope == "all" and k > min(nq + ng, 1024):
+        raise L.CreidError(f"query_expansion(scope='all'): k = {k} outside 1 .. min(N = {nq + ng}, 1024)")
+    if scope == "query" and k - 1 > min(ng, 1024):
+        raise L.CreidError(f"query_expansion(scope='query'): k - 1 = {k - 1} outside 0 .. min(ng = {ng}, 1024)")
+
+
 def _dev_i64(a, device):
     if isinstance(a, torch.Tensor):
         return a.to(device=device, dtype=torch.int64).contiguous()
@@ -976,7 +1161,8 @@ class R1_mAP:
     MODEL.USE_CENTROIDS); trainer/logger lookups of the reference are optional here."""
 
     def __init__(self, pl_module=None, num_query=0, max_rank=50, feat_norm=True, dist_func="euclidean",
-                 compute_dtype=torch.float32, streamed=False, reranking=False, prefilter=None, prefilter_capacity=None):
+                 compute_dtype=torch.float32, streamed=False, reranking=False, prefilter=None, prefilter_capacity=None,
+                 query_expansion=False):
         """streamed=True: metric-only evaluation that never materialises the distance / index matrices (euclidean; plain
         camera ids or, with compute(respect_camids=True), camera sets; compute_dtype fp32, bf16 or f16 -- the 16-bit modes
         run the 16-bit MFMA and return exactly what their materialised evaluation returns); `last` then holds the per-query
@@ -993,8 +1179,19 @@ class R1_mAP:
         every row took the fp32 kernel), capacity, margin_max, fallback_rows, ambiguous (int32 [m] on the device: pairs listed per
         query) and -- when `last` came in holding {"prefilter": {"timing": True}} -- stage_ms (pack, poslist, count, rescore,
         repair, between device events).  CreidError with streamed=False, another compute_dtype or distance, or reranking; and
-        from compute(respect_camids=True)."""
+        from compute(respect_camids=True).
+        query_expansion=True (the defaults of query_expansion) or a dict of k / alpha / rounds / scope: the rows are normalised
+        to fp32, expanded by their nearest neighbours (reid_metric.query_expansion: blind to pids and cameras) and the sums
+        normalised into compute_dtype; everything behind the normalisation -- either distance, streamed or not, compute_chunked,
+        re-ranking, camera sets -- then runs on the expanded rows, exactly as R1_mAP(feat_norm=False) runs on the rows
+        query_expansion returns.  `prefilter` also goes to the expansion's neighbour search.  `last["query_expansion"]` holds the
+        options and query_expansion's stats (stage_ms when `last` came in holding {"query_expansion": {"timing": True}}).
+        CreidError with feat_norm=False: expansion is defined on unit rows."""
         self.reranking = rerank_options(reranking)
+        self.query_expansion = expansion_options(query_expansion)
+        if self.query_expansion is not None and not feat_norm:
+            raise L.CreidError("R1_mAP(query_expansion=...) expands unit rows: not with feat_norm=False")
+        self._qe_info = None
         self.streamed = streamed
         self.num_query = num_query
         self.max_rank = max_rank
@@ -1024,6 +1221,25 @@ class R1_mAP:
             if c < 64 or c > 8192 or c & (c - 1):
                 raise L.CreidError(f"R1_mAP(prefilter_capacity=...) must be a power of two, 64 .. 8192, got {c}")
 
+    def _normalised(self, feats, out_dtype=None):
+        """The feat_norm=True rows of every path and their square norms: l2_normalize, or -- query_expansion -- the expanded rows
+        with the norms row_sqnorm gives them, the ones a feat_norm=False evaluation of these rows works with."""
+        out_dtype = self.compute_dtype if out_dtype is None else out_dtype
+        if self.query_expansion is None:
+            return l2_normalize(feats, out_dtype=out_dtype, return_sqnorm=True)
+        o = self.query_expansion
+        _check_expansion_shape(o["k"], o["scope"], self.num_query, feats.shape[0] - self.num_query)
+        info = {"timing": True} if (self.last.get("query_expansion") or {}).get("timing") else {}
+        f, _ = _expanded_rows(feats, self.num_query, o["k"], float(o["alpha"]), o["rounds"], o["scope"], self.prefilter, out_dtype,
+                              info)
+        info.pop("timing", None)
+        self._qe_info = {**o, **info}
+        return f, row_sqnorm(f)
+
+    def _keep_expansion_info(self):
+        if self._qe_info is not None:
+            self.last["query_expansion"] = self._qe_info
+
     def compute(self, feats, pids, camids, respect_camids=False):
         if not isinstance(feats, torch.Tensor) or not feats.is_cuda:
             raise L.CreidError("R1_mAP.compute needs device features (no CPU fallback)")
@@ -1036,7 +1252,7 @@ class R1_mAP:
         if self.dist_name == "euclidean":
             if self.feat_norm:
                 print("The test feature is normalized")
-                f, sq = l2_normalize(feats, out_dtype=self.compute_dtype, return_sqnorm=True)
+                f, sq = self._normalised(feats)
             else:
                 f = feats if self.compute_dtype == torch.float32 else feats.to(self.compute_dtype)
                 sq = row_sqnorm(f)
@@ -1045,7 +1261,7 @@ class R1_mAP:
             else:
                 distmat = get_euclidean(f[:nq], f[nq:], sq[:nq].contiguous(), sq[nq:].contiguous())
         else:
-            f = l2_normalize(feats) if self.feat_norm else feats
+            f = self._normalised(feats, torch.float32)[0] if self.feat_norm else feats
             distmat = self.dist_func(f[:nq].contiguous(), f[nq:].contiguous())
         pids = np.asarray(pids)
         if respect_camids:                      # (ragged list-of-lists of camera sets: keep as a list)
@@ -1053,6 +1269,7 @@ class R1_mAP:
             cmc, mAP, all_topk, single = eval_func(indices, pids[:nq], pids[nq:], camids[:nq], camids[nq:],
                                                    self.max_rank, respect_camids)
             self.last = dict(distmat=distmat, indices=indices, single_performance=single)
+            self._keep_expansion_info()
             return cmc, mAP, all_topk
         # np.argsort + eval_func's per-query loop in ONE pass: the ranked rows are evaluated while they are still in LDS
         camids = np.asarray(camids)
@@ -1067,6 +1284,7 @@ class R1_mAP:
         vi = np.nonzero(valid_h)[0]
         single = np.stack([vi.astype(np.float64), pids[:nq][vi].astype(np.float64), pack[max_rank + 6 + nq:][vi]], axis=1)
         self.last = dict(distmat=distmat, indices=indices, single_performance=single, valid=valid, ap=ap, first=first)
+        self._keep_expansion_info()
         return pack[:max_rank].astype(np.float32), float(pack[max_rank]), pack[max_rank + 1:max_rank + 6].copy()
 
     def _compute_streamed(self, feats, pids, camids, plan=None, _normed=None, _clock=None, camsets=False):
@@ -1084,7 +1302,7 @@ class R1_mAP:
                 feats = _pad_width(feats, 8)
             if self.feat_norm:
                 print("The test feature is normalized")
-                f, sq = l2_normalize(feats, out_dtype=self.compute_dtype, return_sqnorm=True)
+                f, sq = self._normalised(feats)
             else:
                 f = feats if self.compute_dtype == torch.float32 else feats.to(self.compute_dtype)
                 sq = row_sqnorm(f)
@@ -1183,6 +1401,7 @@ class R1_mAP:
         self.last = dict(valid=valid, ap=ap, first=first, single_performance=single, plan=plan)
         if info is not None:
             self.last["prefilter"] = info
+        self._keep_expansion_info()
         return cmc_h, mAP_h, topk_h
 
     def compute_chunked(self, feats, pids, camids, query_chunk=4096, respect_camids=False):
@@ -1209,10 +1428,10 @@ class R1_mAP:
         if not euclid:
             # SOLVER.DISTANCE_FUNC = cosine (utils/reid_metric.py:51-59,93-110 works with either function): the same
             # query-chunk loop on the cosine matrix
-            f = l2_normalize(feats) if self.feat_norm else feats
+            f = self._normalised(feats, torch.float32)[0] if self.feat_norm else feats
             sq = None
         elif self.feat_norm:
-            f, sq = l2_normalize(feats, out_dtype=self.compute_dtype, return_sqnorm=True)
+            f, sq = self._normalised(feats)
         else:
             f = feats if self.compute_dtype == torch.float32 else feats.to(self.compute_dtype)
             sq = row_sqnorm(f)
@@ -1230,4 +1449,5 @@ class R1_mAP:
             vs.append(v); aps.append(a); firsts.append(fr)
             del idx
         v = torch.cat(vs).cpu().numpy() > 0; a = torch.cat(aps).cpu().numpy(); fr = torch.cat(firsts).cpu().numpy()
+        self._keep_expansion_info()
         return merge_eval_results(v, a, fr, min(self.max_rank, g.shape[0]))

@@ -318,6 +318,20 @@ int creid_rerank_blend(const float* dist, const float* rowmax, int64_t nq, int64
                        const int64_t* rowptr, const int32_t* cols, const float* vals, const int64_t* colptr,
                        const int32_t* colrows, int32_t max_row, float* out, void* stream);
 
+/* ---- neighbour expansion (query expansion / database-side augmentation; csrc/neighbour_expand.hip): the weighted sum of the
+ * rows a neighbour table names.  x fp32 [n_src][D]; idx int64 [m][k] with every entry in [0, n_src) (the caller's duty: the
+ * kernel does not check it); dist fp32 [m][k], the squared L2 of unit rows as creid_stream_topk_* returns it.
+ *   sim = min(max(fmaf(-0.5, dist, 1), 0), 1);  w = 1 when alpha == 0 (dist is then never read and may be NULL), sim when
+ *   alpha == 1, else (float)pow((double)sim, (double)alpha);
+ *   out[i][c] = sum_t w[i][t] x[idx[i][t]][c]: an fp32 fmaf chain from 0 in the order of t, so a row's bits depend neither on
+ *   the launch geometry nor on the other rows of the call.  self_rows fp32 [m][D] (or NULL): row i is the chain's first
+ *   addend, at weight 1, before t = 0.
+ * out fp32 [m][D] must not overlap x or self_rows.  m == 0 returns 0; CREID_E_ARG for a null pointer, k < 0, n_src < 1 with
+ * k > 0, or an alpha that is negative or not finite; CREID_E_SHAPE for D < 4 or D % 4 != 0 (16-byte column chunks) -- all
+ * before anything is launched. */
+int creid_neighbour_expand(const float* x, int64_t n_src, const int64_t* idx, const float* dist, const float* self_rows,
+                           int64_t m, int32_t k, int64_t D, float alpha, float* out, void* stream);
+
 /* Measured launch plans (optional).  kind 0 = weight gradient: key (M = batch*out_h*out_w, out_c, K = kh*kw*in_c, 0) ->
  * (tile rows 64|128, tile cols 64|128, pixel splits | ring depth << 16 | producer/consumer waves << 20 | two k-groups << 21);
  * kind 1 = implicit-GEMM forward / data gradient: key (GEMM rows M, GEMM cols N, K, transposed 0|1 | stride << 1) ->
