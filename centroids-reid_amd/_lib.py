@@ -53,6 +53,11 @@ SIGNATURES = {
     "creid_stream_poslist_h16": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, C.c_int, _p, _p, _p, _p, _p, _i32, _p, _p, _p, _p]),
     "creid_stream_count_h16": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, C.c_int, _p, _p, _i32, _p, _p, _p, _p, _p]),
     "creid_stream_topk_collect_h16": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, C.c_int, _p, _i32, _p, _p, _p]),
+    "creid_stream_topk_collect_keep": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _i32, _i32, _p, _p, _p]),
+    "creid_stream_topk_collect_keep_h16": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, C.c_int, _p, _p, _p, _p, _p, _i32, _i32, _p, _p,
+                                                     _p]),
+    "creid_rank_keep_topk": (C.c_int, [_p, _i64, _i64, _i64, _i32, _p, _p, _p, _p, _i32, _p, _p, _p, _p]),
+    "creid_junk_mask_rows": (C.c_int, [_p, _i64, _i64, _i64, _p, _p, _p, _p, _i32, _p]),
     "creid_prefilter_pack": (C.c_int, [_p, _i64, _i64, C.c_int, _p, _p, _p]),
     "creid_stream_topk_rescore": (C.c_int, [_p, _p, _i64, _i32, _i32, _p, _p, _p, _p, _i64, _i64, _p, _p, _p, _p, _p, _p]),
     "creid_stream_count_band_h16": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, C.c_int, _p, _p, _i32, _p, _p, _p, _p, _i32, _p, _p, _p,

@@ -386,14 +386,22 @@ class ModelBase(_Base):
         return out, out_labels, out_camids
 
     def get_val_metrics(self, embeddings, labels, camids):
-        """modelling/bases.py:264-297."""
+        """modelling/bases.py:264-297.  TEST.VISUALIZE == "yes" (:281-293 hands the ranking to utils/visrank.py): the lists that
+        function draws are kept as data in `self.last_ranked` -- numpy indices / distances / matched / count (R1_mAP(ranked_topk=
+        TEST.VISUALIZE_TOPK)) of the first min(num_query, TEST.VISUALIZE_MAX_NUMBER + 1) queries; nothing is drawn or written."""
         respect_camids = bool(self.hparams.MODEL.KEEP_CAMID_CENTROIDS and self.hparams.MODEL.USE_CENTROIDS)
+        visualize = self.hparams.TEST.VISUALIZE == "yes"
         self.r1_map_func = R1_mAP(pl_module=self, num_query=self.hparams.num_query,
                                   feat_norm=self.hparams.TEST.FEAT_NORM, streamed=True,   # only the metrics are used
                                   prefilter=None if respect_camids else self.eval_prefilter,
-                                  query_expansion=getattr(self, "eval_query_expansion", None))
+                                  query_expansion=getattr(self, "eval_query_expansion", None),
+                                  ranked_topk=int(self.hparams.TEST.VISUALIZE_TOPK) if visualize else None)
         cmc, mAP, all_topk = self.r1_map_func.compute(feats=embeddings.float(), pids=labels, camids=camids,
                                                       respect_camids=respect_camids)
+        if visualize:
+            # the data utils/visrank.py:161-242 draws: its query loop stops after index VISUALIZE_MAX_NUMBER
+            keep = min(int(self.hparams.num_query), int(self.hparams.TEST.VISUALIZE_MAX_NUMBER) + 1)
+            self.last_ranked = {key: v[:keep].cpu().numpy() for key, v in self.r1_map_func.last["ranked"].items()}
         topks = {}
         for top_k, kk in zip(all_topk, [1, 5, 10, 20, 50]):
             print("top-k, Rank-{:<3}:{:.1%}".format(kk, top_k))

@@ -571,6 +571,70 @@ __global__ __launch_bounds__(TK_T) void topk_rows_kernel(const float* __restrict
   if (tid == 0) flags[blockIdx.x] = 0;
 }
 
+// ----------------------------------------------------------------------------------------
+// Ranked lists under the evaluation protocol (utils/eval_reid.py:49-58, utils/visrank.py:193-232): the first k entries of a
+// ranked row that are not junk -- the query's pid seen by the query's camera (CAMSETS: by a camera set that holds it).  One wave
+// per query walks the row in chunks of 64; a ballot and a prefix popcount place the kept entries in order, and the wave leaves
+// as soon as k are written.  No atomics: the output does not depend on the run.  A ranked index outside [0, ng) is dropped.
+// ----------------------------------------------------------------------------------------
+template <bool CAMSETS>
+__device__ __forceinline__ bool junk_removed(int64_t g_cam, int64_t qc) {      // cam_removed of stream_common.hpp
+  if constexpr (CAMSETS) return (((unsigned long long)g_cam >> (qc & 63)) & 1ull) != 0;
+  else return g_cam == qc;
+}
+
+template <bool CAMSETS>
+__global__ __launch_bounds__(256) void rank_keep_topk_kernel(const int64_t* __restrict__ idx, int64_t m, int64_t n, int64_t ng,
+                                                             int k, const int64_t* __restrict__ q_pids,
+                                                             const int64_t* __restrict__ g_pids,
+                                                             const int64_t* __restrict__ q_cams,
+                                                             const int64_t* __restrict__ g_cams, int64_t* __restrict__ out_idx,
+                                                             uint8_t* __restrict__ out_matched, int32_t* __restrict__ out_count) {
+  const int lane = threadIdx.x & 63;
+  const int64_t qi = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (qi >= m) return;                                              // (wave-uniform)
+  const int64_t qp = q_pids[qi], qc = q_cams[qi];
+  const int64_t* row = idx + qi * n;
+  int64_t* oi = out_idx + qi * k;
+  uint8_t* om = out_matched + qi * k;
+  const unsigned long long lt = lanemask_lt();
+  int written = 0;
+  for (int64_t b = 0; b < n && written < k; b += 64) {
+    const int64_t i = b + lane;
+    bool keep = false, match = false;
+    int64_t gi = -1;
+    if (i < n) {
+      gi = row[i];
+      if (gi >= 0 && gi < ng) {
+        match = g_pids[gi] == qp;
+        keep = !(match && junk_removed<CAMSETS>(g_cams[gi], qc));   // camera fetched for the rare matches only
+      }
+    }
+    const unsigned long long bal = __ballot(keep);
+    const int p = written + __popcll(bal & lt);
+    if (keep && p < k) { oi[p] = gi; om[p] = match ? 1 : 0; }
+    written += __popcll(bal);
+  }
+  written = min(written, k);
+  for (int p = written + lane; p < k; p += 64) { oi[p] = -1; om[p] = 0; }
+  if (lane == 0) out_count[qi] = written;
+}
+
+// The junk cells of a distance slice [m, n] (leading dimension ld) become +inf: the threshold sample of the junk-free streamed
+// top-k ranks what is left.  Column j of the slice is gallery entry j of the label vectors given.
+template <bool CAMSETS>
+__global__ __launch_bounds__(256) void junk_mask_rows_kernel(float* __restrict__ dist, int64_t m, int64_t n, int64_t ld,
+                                                             const int64_t* __restrict__ q_pids,
+                                                             const int64_t* __restrict__ g_pids,
+                                                             const int64_t* __restrict__ q_cams,
+                                                             const int64_t* __restrict__ g_cams) {
+  const int64_t total = m * n;
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+    const int64_t i = e / n, j = e - i * n;
+    if (g_pids[j] == q_pids[i] && junk_removed<CAMSETS>(g_cams[j], q_cams[i])) dist[i * ld + j] = __uint_as_float(0x7f800000u);
+  }
+}
+
 // means over valid queries: single workgroup
 __global__ __launch_bounds__(256) void eval_reduce_kernel(const uint8_t* __restrict__ valid,
                                                           const double* __restrict__ ap,
@@ -741,6 +805,40 @@ int creid_topk_rows(const float* dist, int64_t m, int64_t n, int64_t ld, int32_t
   if (k > n || k > 1024 || n > 0x7ffffff0LL || m > 0x7fffffffLL) return CREID_E_SHAPE;
   hipLaunchKernelGGL(topk_rows_kernel, dim3((unsigned)m), dim3(TK_T), 0, as_stream(stream), dist, (int)n, ld, (int)k, out_idx,
                      out_dist, flags);
+  CREID_LAUNCH_RET();
+}
+
+int creid_rank_keep_topk(const int64_t* idx, int64_t m, int64_t n, int64_t ng, int32_t k, const int64_t* q_pids,
+                         const int64_t* g_pids, const int64_t* q_cams, const int64_t* g_cams, int32_t camsets,
+                         int64_t* out_idx, uint8_t* out_matched, int32_t* out_count, void* stream) {
+  CREID_CHECK_ARG(m >= 0 && n >= 0 && ng >= 0 && k >= 1);
+  if (k > 1024 || m > 0x7ffffff0LL) return CREID_E_SHAPE;
+  if (m == 0) return 0;
+  CREID_CHECK_ARG((idx || n == 0) && q_pids && g_pids && q_cams && g_cams && out_idx && out_matched && out_count);
+  const dim3 grid((unsigned)((m + 3) / 4));
+  if (camsets)
+    hipLaunchKernelGGL(rank_keep_topk_kernel<true>, grid, dim3(256), 0, as_stream(stream), idx, m, n, ng, (int)k, q_pids, g_pids,
+                       q_cams, g_cams, out_idx, out_matched, out_count);
+  else
+    hipLaunchKernelGGL(rank_keep_topk_kernel<false>, grid, dim3(256), 0, as_stream(stream), idx, m, n, ng, (int)k, q_pids, g_pids,
+                       q_cams, g_cams, out_idx, out_matched, out_count);
+  CREID_LAUNCH_RET();
+}
+
+int creid_junk_mask_rows(float* dist, int64_t m, int64_t n, int64_t ld, const int64_t* q_pids, const int64_t* g_pids,
+                         const int64_t* q_cams, const int64_t* g_cams, int32_t camsets, void* stream) {
+  CREID_CHECK_ARG(m >= 0 && n >= 0 && ld >= n);
+  if (m == 0 || n == 0) return 0;
+  CREID_CHECK_ARG(dist && q_pids && g_pids && q_cams && g_cams);
+  if (m > 0x7ffffff0LL || n > 0x7ffffff0LL) return CREID_E_SHAPE;
+  const int64_t blocks = (m * n + 255) / 256;
+  const dim3 grid((unsigned)(blocks < 8192 ? blocks : 8192));
+  if (camsets)
+    hipLaunchKernelGGL(junk_mask_rows_kernel<true>, grid, dim3(256), 0, as_stream(stream), dist, m, n, ld, q_pids, g_pids, q_cams,
+                       g_cams);
+  else
+    hipLaunchKernelGGL(junk_mask_rows_kernel<false>, grid, dim3(256), 0, as_stream(stream), dist, m, n, ld, q_pids, g_pids, q_cams,
+                       g_cams);
   CREID_LAUNCH_RET();
 }
 

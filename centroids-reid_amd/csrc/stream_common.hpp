@@ -9,6 +9,8 @@
 constexpr int SQ_TM = 64, SQ_TN = 256;           // a tile: 64 query rows x 256 gallery columns (four units of 64 columns)
 constexpr int EPI_COUNT = 0, EPI_TOPK = 1;       // what a streamed contraction does with a finished tile
 constexpr int EPI_BAND = 2;                      // the count with a per-row error band (16-bit kernel only: stream_consume.hpp)
+constexpr int EPI_TOPK_KEEP = 3;                 // the top-k that lists only the entries the evaluation protocol keeps (no junk)
+constexpr bool epi_is_topk(int epi) { return epi == EPI_TOPK || epi == EPI_TOPK_KEEP; }
 constexpr int PL_MAXC = 128;                     // positive-list capacity of the count epilogue (LDS: [64][cap] keys + histogram)
 constexpr int TS_MIN_CAP = 64, TS_MAX_CAP = 8192;   // candidate-list capacity of the top-k epilogue
 

@@ -5,7 +5,7 @@
 // register r of lane (l31 = lane & 31, kh = lane >> 5) is row wm * 32 + 4 kh + (r & 3) + 8 (r >> 2), column l31 of its block.
 //
 //   stream_segment_begin<EPI>   per (query tile, run of columns): the LDS state the consumer reads
-//   stream_tile_consume<EPI, H, NJ>   one finished tile: the count, the top-k or the banded-count epilogue
+//   stream_tile_consume<EPI, H, NJ>   one finished tile: the count, the top-k, the banded-count or the junk-free top-k epilogue
 //   stream_segment_end          count / banded count: the LDS histogram leaves for global memory
 //   STREAM_DISPATCH_NJ          the tile width as a compile-time constant
 //   poslist_pad / poslist_rank_emit   the tail of the two positives kernels
@@ -18,7 +18,7 @@
 
 // The LDS state of a segment: per query row of the tile its norm, pid, number of positives and `kmax` (count: key of the row's last
 // positive; top-k: key of the row's threshold); count only: the rows' positive keys [64][cap] and the histogram [64][cap];
-// banded count: the count's state and the rows' margins `mg`.
+// banded count: the count's state and the rows' margins `mg`; junk-free top-k: the top-k's state and the rows' pid and camera.
 struct StreamLds {
   float* qq;
   long long* qpid;
@@ -27,11 +27,13 @@ struct StreamLds {
   unsigned* keys;
   unsigned* hist;
   float* mg;
+  long long* qcam;
 };
 
 // The problem the consumers see: sizes, list capacity, and the global arrays they read or write (count: q_pids .. hist_out;
 // top-k: tau .. cand_count; the other group is unused and may be null.  Banded count: the count's group, and tau = the rows'
-// margins, cand = the rows' lists of ambiguous columns -- [m][acap] 32-bit words --, cand_count = their lengths).
+// margins, cand = the rows' lists of ambiguous columns -- [m][acap] 32-bit words --, cand_count = their lengths.  Junk-free
+// top-k: the top-k's group, the pids, and the cameras: q_cams plain ids; g_cams plain ids, or -- camsets != 0 -- bitmasks).
 struct StreamProblem {
   int m, n, cap, log2cap;
   const float* qq;
@@ -46,6 +48,9 @@ struct StreamProblem {
   unsigned long long* cand;
   int32_t* cand_count;
   int acap;
+  const int64_t* q_cams;
+  const int64_t* g_cams;
+  int camsets;
 };
 
 // Every thread of the 256-thread workgroup calls it, behind a barrier after the previous segment's stream_segment_end; the
@@ -54,11 +59,15 @@ template <int EPI>
 __device__ __forceinline__ void stream_segment_begin(const StreamLds& L, const StreamProblem& P, int row0) {
   int ts = threadIdx.x;                            // opaque: the set-up's LDS addresses are recomputed per segment instead of
   asm volatile("" : "+v"(ts));                     // occupying registers (or scratch) across the k-loops
-  if constexpr (EPI == EPI_TOPK) {
+  if constexpr (epi_is_topk(EPI)) {
     if (ts < SQ_TM) {
       const int rr = row0 + ts;
       L.qq[ts] = rr < P.m ? P.qq[rr] : 0.f;
       L.kmax[ts] = rr < P.m ? mono_key(P.tau[rr]) : 0u;
+      if constexpr (EPI == EPI_TOPK_KEEP) {
+        L.qpid[ts] = rr < P.m ? (long long)P.q_pids[rr] : 0;
+        L.qcam[ts] = rr < P.m ? (long long)P.q_cams[rr] : 0;
+      }
     }
   } else {
     for (int i = ts; i < SQ_TM * P.cap; i += 256) {
@@ -100,6 +109,10 @@ __device__ __forceinline__ void stream_segment_end(const StreamLds& L, const Str
 //              skip_count & 1: timing ablation, no row has positives (results wrong).
 //   EPI_TOPK : every element whose key is <= the row's threshold key takes a slot of its row's list with a global atomicAdd on
 //              cand_count[row] and, while the slot is below `cap`, stores key << 32 | col there.
+//   EPI_TOPK_KEEP: EPI_TOPK for the ranked lists of the evaluation protocol (utils/eval_reid.py:49-58): an element inside the
+//              threshold takes its slot only if it is not junk -- the row's pid AND cam_removed for the row's camera.  The few
+//              elements that pass the threshold fetch their pid, the fewer of the row's pid their camera word: the walk over
+//              the other elements is EPI_TOPK's, instruction for instruction, and so are its registers.
 //   EPI_BAND : the count for a distance dh known to lie within mg = L.mg[row] of the exact one d (16-bit operands, fp32 positive
 //              keys: reid_metric.R1_mAP(prefilter=...)).  lo = sub_down(dh, mg) <= d <= hi = add_up(dh, mg).  key(lo) beyond the
 //              row's last positive: behind every positive, skipped.  l = #positives with key < key(lo): each of them ranks before
@@ -121,9 +134,9 @@ __device__ __forceinline__ void stream_tile_consume(const f32x16 (&acc)[NJ], int
     const int c = col0 + (wn + 2 * j) * 32 + l31;
     okc[j] = c < P.n;
     gv[j] = okc[j] ? P.gg[c] : 0.f;
-    if constexpr (EPI != EPI_TOPK) gp[j] = okc[j] ? (long long)P.g_pids[c] : 0;
+    if constexpr (!epi_is_topk(EPI)) gp[j] = okc[j] ? (long long)P.g_pids[c] : 0;
   }
-  if constexpr (EPI == EPI_TOPK) {
+  if constexpr (epi_is_topk(EPI)) {
     // One accumulator row at a time: its threshold is one LDS read, a hit one global atomic.
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
@@ -135,6 +148,13 @@ __device__ __forceinline__ void stream_tile_consume(const f32x16 (&acc)[NJ], int
       for (int j = 0; j < NJ; ++j) {
         const unsigned key = mono_key(fmaf(-2.0f, acc[j][r], qv + gv[j]));
         if (okr && okc[j] && key <= kt) {
+          if constexpr (EPI == EPI_TOPK_KEEP) {
+            const int c = col0 + (wn + 2 * j) * 32 + l31;
+            if ((long long)P.g_pids[c] == L.qpid[rl]) {              // rare: the camera word is fetched for the row's pid only
+              const int64_t gc = P.g_cams[c], qc = L.qcam[rl];
+              if (P.camsets ? cam_removed<true>(gc, qc) : cam_removed<false>(gc, qc)) continue;
+            }
+          }
           const int64_t rr = row0 + rl;
           const int slot = atomicAdd(&P.cand_count[rr], 1);
           if (slot < P.cap)

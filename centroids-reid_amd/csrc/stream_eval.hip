@@ -125,17 +125,21 @@ __global__ __launch_bounds__(PL_MAXC) void stream_poslist_kernel(
 //              cand_count unused).
 //   EPI_TOPK : retrieval: the candidate collection (tau, cand, cand_count; cap is the list capacity).  LDS state per tile: the 64
 //              threshold keys (s_kmax) next to s_qq; no dynamic LDS; the label / list arguments of the count are unused.
+//   EPI_TOPK_KEEP: the collection without the evaluation protocol's junk (EPI_TOPK's arguments, and q_pids, g_pids, q_cams,
+//              g_cams, camsets; s_qpid / s_qcam next to s_kmax).
 template <int ABL, bool FULLK, int EPI = EPI_COUNT>
 __global__ __launch_bounds__(256, FULLK ? 2 : 1) void sqdist_count_f32_kernel(
     const float* __restrict__ q, const float* __restrict__ g, const float* __restrict__ qq, const float* __restrict__ gg,
     int m, int n, int D, const int64_t* __restrict__ q_pids, const int64_t* __restrict__ g_pids, int cap, int log2cap,
     const unsigned* __restrict__ pos_key, const int32_t* __restrict__ pos_idx, const int32_t* __restrict__ npos,
     unsigned* __restrict__ hist_out, int tiles_m, int U, int upw, int mode, int skip_count,
-    const float* __restrict__ tau, unsigned long long* __restrict__ cand, int32_t* __restrict__ cand_count) {
+    const float* __restrict__ tau, unsigned long long* __restrict__ cand, int32_t* __restrict__ cand_count,
+    const int64_t* __restrict__ q_cams, const int64_t* __restrict__ g_cams, int camsets) {
   __shared__ __attribute__((aligned(16))) float As[2][2][4][SQ_PA];
   __shared__ __attribute__((aligned(16))) float Bs[2][2][4][SQ_PB];
   __shared__ float s_qq[SQ_TM];
   __shared__ long long s_qpid[SQ_TM];
+  __shared__ long long s_qcam[SQ_TM];            // EPI_TOPK_KEEP only (no other instantiation names it: no LDS there)
   __shared__ int s_np[SQ_TM];
   __shared__ unsigned s_kmax[SQ_TM];             // count: key of the row's last positive; top-k: key of the row's threshold
   extern __shared__ __attribute__((aligned(16))) unsigned dyn[];
@@ -144,8 +148,9 @@ __global__ __launch_bounds__(256, FULLK ? 2 : 1) void sqdist_count_f32_kernel(
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
   const int l31 = lane & 31, kh = lane >> 5;
-  const StreamLds L{s_qq, s_qpid, s_np, s_kmax, s_keys, s_hist};
-  const StreamProblem P{m, n, cap, log2cap, qq, gg, q_pids, g_pids, pos_key, pos_idx, npos, hist_out, tau, cand, cand_count};
+  const StreamLds L{s_qq, s_qpid, s_np, s_kmax, s_keys, s_hist, nullptr, s_qcam};
+  const StreamProblem P{m, n, cap, log2cap, qq, gg, q_pids, g_pids, pos_key, pos_idx, npos, hist_out, tau, cand, cand_count, 0,
+                        q_cams, g_cams, camsets};
   long long g0, g1;                              // this workgroup's run, in units of the rows laid end to end
   stream_run(tiles_m, U, upw, mode, g0, g1);
 
@@ -550,7 +555,8 @@ int creid_stream_count(const float* q, const float* g, const float* qq, const fl
 #define CREID_COUNT_LAUNCH_(A, F)                                                                                     \
   return stream_count_launch<sqdist_count_f32_kernel<A, F>>(                                                           \
       sp, (int)cap, stream, q, g, qq, gg, (int)m, (int)n, (int)D, q_pids, g_pids, (int)cap, log2cap, pos_key, pos_idx, npos, hist, \
-      sp.tiles_m, sp.U, sp.upw, sp.mode, skip_count & 1, (const float*)nullptr, (unsigned long long*)nullptr, (int32_t*)nullptr)
+      sp.tiles_m, sp.U, sp.upw, sp.mode, skip_count & 1, (const float*)nullptr, (unsigned long long*)nullptr, (int32_t*)nullptr, \
+      (const int64_t*)nullptr, (const int64_t*)nullptr, 0)
 #define CREID_COUNT_LAUNCH(A)                                                                                          \
   do { if (D % SQ_BK == 0) CREID_COUNT_LAUNCH_(A, true); else CREID_COUNT_LAUNCH_(0, false); } while (0)
 #ifdef CREID_ABL_BUILD
@@ -595,9 +601,31 @@ int creid_stream_topk_collect(const float* q, const float* g, const float* qq, c
   hipLaunchKernelGGL((sqdist_count_f32_kernel<0, F, EPI_TOPK>), dim3(sp.grid), dim3(256), 0, as_stream(stream),         \
                      q, g, qq, gg, (int)m, (int)n, (int)D, (const int64_t*)nullptr, (const int64_t*)nullptr, (int)cap, 0, \
                      (const unsigned*)nullptr, (const int32_t*)nullptr, (const int32_t*)nullptr, (unsigned*)nullptr,    \
-                     sp.tiles_m, sp.U, sp.upw, sp.mode, 0, tau, reinterpret_cast<unsigned long long*>(cand), count)
+                     sp.tiles_m, sp.U, sp.upw, sp.mode, 0, tau, reinterpret_cast<unsigned long long*>(cand), count,     \
+                     (const int64_t*)nullptr, (const int64_t*)nullptr, 0)
   if (D % SQ_BK == 0) CREID_TOPK_LAUNCH(true); else CREID_TOPK_LAUNCH(false);
 #undef CREID_TOPK_LAUNCH
+  CREID_LAUNCH_RET();
+}
+
+int creid_stream_topk_collect_keep(const float* q, const float* g, const float* qq, const float* gg, int64_t m, int64_t n,
+                                   int64_t D, const float* tau, const int64_t* q_pids, const int64_t* g_pids,
+                                   const int64_t* q_cams, const int64_t* g_cams, int32_t camsets, int32_t cap, uint64_t* cand,
+                                   int32_t* count, void* stream) {
+  CREID_CHECK_ARG(m >= 0 && n > 0 && D > 0);
+  if (!stream_topk_cap_ok(cap) || D % 4 != 0) return CREID_E_SHAPE;
+  if (!stream_mn_ok(m, n)) return CREID_E_SHAPE;
+  if (m == 0) return 0;
+  CREID_CHECK_ARG(q && g && qq && gg && tau && q_pids && g_pids && q_cams && g_cams && cand && count);
+  const StreamSplit sp = stream_split(m, n, D);
+#define CREID_TOPK_KEEP_LAUNCH(F)                                                                                       \
+  hipLaunchKernelGGL((sqdist_count_f32_kernel<0, F, EPI_TOPK_KEEP>), dim3(sp.grid), dim3(256), 0, as_stream(stream),    \
+                     q, g, qq, gg, (int)m, (int)n, (int)D, q_pids, g_pids, (int)cap, 0,                                 \
+                     (const unsigned*)nullptr, (const int32_t*)nullptr, (const int32_t*)nullptr, (unsigned*)nullptr,    \
+                     sp.tiles_m, sp.U, sp.upw, sp.mode, 0, tau, reinterpret_cast<unsigned long long*>(cand), count,     \
+                     q_cams, g_cams, camsets != 0 ? 1 : 0)
+  if (D % SQ_BK == 0) CREID_TOPK_KEEP_LAUNCH(true); else CREID_TOPK_KEEP_LAUNCH(false);
+#undef CREID_TOPK_KEEP_LAUNCH
   CREID_LAUNCH_RET();
 }
 

@@ -158,11 +158,13 @@ __global__ __launch_bounds__(256, 2) void sqdist_stream_h16_kernel(
     const float* __restrict__ gg, int m, int n, int D, const int64_t* __restrict__ q_pids, const int64_t* __restrict__ g_pids,
     int cap, int log2cap, const unsigned* __restrict__ pos_key, const int32_t* __restrict__ pos_idx,
     const int32_t* __restrict__ npos, unsigned* __restrict__ hist_out, int tiles_m, int U, int upw, int mode,
-    const float* __restrict__ tau, unsigned long long* __restrict__ cand, int32_t* __restrict__ cand_count, int acap) {
+    const float* __restrict__ tau, unsigned long long* __restrict__ cand, int32_t* __restrict__ cand_count, int acap,
+    const int64_t* __restrict__ q_cams, const int64_t* __restrict__ g_cams, int camsets) {
   __shared__ __attribute__((aligned(16))) unsigned short As[SQ_TM * H_BK];
   __shared__ __attribute__((aligned(16))) unsigned short Bs[SQ_TN * H_BK];
   __shared__ float s_qq[SQ_TM];
   __shared__ long long s_qpid[SQ_TM];
+  __shared__ long long s_qcam[SQ_TM];            // EPI_TOPK_KEEP only (no other instantiation names it: no LDS there)
   __shared__ int s_np[SQ_TM];
   __shared__ unsigned s_kmax[SQ_TM];             // count: key of the row's last positive; top-k: key of the row's threshold
   extern __shared__ __attribute__((aligned(16))) unsigned dyn[];
@@ -172,8 +174,9 @@ __global__ __launch_bounds__(256, 2) void sqdist_stream_h16_kernel(
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
   const int l31 = lane & 31, kh = lane >> 5;
-  const StreamLds L{s_qq, s_qpid, s_np, s_kmax, s_keys, s_hist, s_mg};
-  const StreamProblem P{m, n, cap, log2cap, qq, gg, q_pids, g_pids, pos_key, pos_idx, npos, hist_out, tau, cand, cand_count, acap};
+  const StreamLds L{s_qq, s_qpid, s_np, s_kmax, s_keys, s_hist, s_mg, s_qcam};
+  const StreamProblem P{m, n, cap, log2cap, qq, gg, q_pids, g_pids, pos_key, pos_idx, npos, hist_out, tau, cand, cand_count, acap,
+                        q_cams, g_cams, camsets};
   long long g0, g1;                              // this workgroup's run, in units of the rows laid end to end
   stream_run(tiles_m, U, upw, mode, g0, g1);
 
@@ -256,7 +259,8 @@ __global__ __launch_bounds__(256, 2) void sqdist_stream_h16_kernel(
         __syncthreads();
       }
     }
-    // the next tile's k-tile 0: under the (light) top-k epilogue; behind the count epilogue, whose searches need the registers
+    // the next tile's k-tile 0: under the (light) top-k epilogue; behind the count epilogue, whose searches need the registers,
+    // and behind the junk-free top-k's, whose label test needs one register more than the 256 leave under the staged tile
     if constexpr (EPI == EPI_TOPK) { if (next >= 0) { set_tile(next); gload(0, 8); } }
     // One accumulator row at a time in the count (the fp32 kernel runs two): one row's NJ search chains keep this kernel inside
     // the 256 registers of two workgroups per CU, and the second workgroup fills the gaps of the chains.
@@ -284,7 +288,7 @@ __global__ __launch_bounds__(256, 2) void sqdist_stream_h16_kernel(
       STREAM_DISPATCH_NJ(nj, tile, col, next);
       col += 256;
     }
-    if constexpr (EPI != EPI_TOPK) stream_segment_end(L, P, row0);
+    if constexpr (!epi_is_topk(EPI)) stream_segment_end(L, P, row0);
   }
 }
 
@@ -349,7 +353,8 @@ int creid_stream_count_h16(const void* q, const void* g, const float* qq, const 
 #define CREID_COUNT_H16_LAUNCH(DT)                                                                                          \
   return stream_count_launch<sqdist_stream_h16_kernel<DT, EPI_COUNT>>(                                                       \
       sp, (int)cap, stream, qh, gh, qq, gg, (int)m, (int)n, (int)D, q_pids, g_pids, (int)cap, log2cap, pos_key, pos_idx, npos, hist, \
-      sp.tiles_m, sp.U, sp.upw, sp.mode, (const float*)nullptr, (unsigned long long*)nullptr, (int32_t*)nullptr, 0)
+      sp.tiles_m, sp.U, sp.upw, sp.mode, (const float*)nullptr, (unsigned long long*)nullptr, (int32_t*)nullptr, 0,               \
+      (const int64_t*)nullptr, (const int64_t*)nullptr, 0)
   if (dtype == CREID_BF16) CREID_COUNT_H16_LAUNCH(CREID_BF16); else CREID_COUNT_H16_LAUNCH(CREID_F16);
 #undef CREID_COUNT_H16_LAUNCH
 }
@@ -370,9 +375,34 @@ int creid_stream_topk_collect_h16(const void* q, const void* g, const float* qq,
   hipLaunchKernelGGL((sqdist_stream_h16_kernel<DT, EPI_TOPK>), dim3(sp.grid), dim3(256), 0, as_stream(stream), qh, gh, qq,   \
                      gg, (int)m, (int)n, (int)D, (const int64_t*)nullptr, (const int64_t*)nullptr, (int)cap, 0,              \
                      (const unsigned*)nullptr, (const int32_t*)nullptr, (const int32_t*)nullptr, (unsigned*)nullptr,         \
-                     sp.tiles_m, sp.U, sp.upw, sp.mode, tau, reinterpret_cast<unsigned long long*>(cand), count, 0)
+                     sp.tiles_m, sp.U, sp.upw, sp.mode, tau, reinterpret_cast<unsigned long long*>(cand), count, 0,          \
+                     (const int64_t*)nullptr, (const int64_t*)nullptr, 0)
   if (dtype == CREID_BF16) CREID_TOPK_H16_LAUNCH(CREID_BF16); else CREID_TOPK_H16_LAUNCH(CREID_F16);
 #undef CREID_TOPK_H16_LAUNCH
+  CREID_LAUNCH_RET();
+}
+
+int creid_stream_topk_collect_keep_h16(const void* q, const void* g, const float* qq, const float* gg, int64_t m, int64_t n,
+                                       int64_t D, int dtype, const float* tau, const int64_t* q_pids, const int64_t* g_pids,
+                                       const int64_t* q_cams, const int64_t* g_cams, int32_t camsets, int32_t cap,
+                                       uint64_t* cand, int32_t* count, void* stream) {
+  CREID_CHECK_ARG(m >= 0 && n > 0 && D > 0);
+  if (!stream_topk_cap_ok(cap) || D % 8 != 0 || D > H_MAX_D) return CREID_E_SHAPE;
+  if (!stream_mn_ok(m, n)) return CREID_E_SHAPE;
+  if (!creid_is16(dtype)) return CREID_E_DTYPE;
+  if (m == 0) return 0;
+  CREID_CHECK_ARG(q && g && qq && gg && tau && q_pids && g_pids && q_cams && g_cams && cand && count);
+  const StreamSplit sp = stream_split(m, n, D, 2);
+  const unsigned short* qh = static_cast<const unsigned short*>(q);
+  const unsigned short* gh = static_cast<const unsigned short*>(g);
+#define CREID_TOPK_KEEP_H16_LAUNCH(DT)                                                                                      \
+  hipLaunchKernelGGL((sqdist_stream_h16_kernel<DT, EPI_TOPK_KEEP>), dim3(sp.grid), dim3(256), 0, as_stream(stream), qh, gh,  \
+                     qq, gg, (int)m, (int)n, (int)D, q_pids, g_pids, (int)cap, 0,                                            \
+                     (const unsigned*)nullptr, (const int32_t*)nullptr, (const int32_t*)nullptr, (unsigned*)nullptr,         \
+                     sp.tiles_m, sp.U, sp.upw, sp.mode, tau, reinterpret_cast<unsigned long long*>(cand), count, 0,          \
+                     q_cams, g_cams, camsets != 0 ? 1 : 0)
+  if (dtype == CREID_BF16) CREID_TOPK_KEEP_H16_LAUNCH(CREID_BF16); else CREID_TOPK_KEEP_H16_LAUNCH(CREID_F16);
+#undef CREID_TOPK_KEEP_H16_LAUNCH
   CREID_LAUNCH_RET();
 }
 
@@ -393,7 +423,8 @@ int creid_stream_count_band_h16(const void* q, const void* g, const float* qq, c
 #define CREID_BAND_H16_LAUNCH(DT)                                                                                           \
   return stream_count_launch<sqdist_stream_h16_kernel<DT, EPI_BAND>, SQ_TM>(                                                 \
       sp, (int)cap, stream, qh, gh, qq, gg, (int)m, (int)n, (int)D, q_pids, g_pids, (int)cap, log2cap, pos_key, pos_idx, npos, hist, \
-      sp.tiles_m, sp.U, sp.upw, sp.mode, margin, reinterpret_cast<unsigned long long*>(amb), amb_count, (int)amb_cap)
+      sp.tiles_m, sp.U, sp.upw, sp.mode, margin, reinterpret_cast<unsigned long long*>(amb), amb_count, (int)amb_cap,             \
+      (const int64_t*)nullptr, (const int64_t*)nullptr, 0)
   if (dtype == CREID_BF16) CREID_BAND_H16_LAUNCH(CREID_BF16); else CREID_BAND_H16_LAUNCH(CREID_F16);
 #undef CREID_BAND_H16_LAUNCH
 }

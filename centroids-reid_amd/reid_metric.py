@@ -149,7 +149,7 @@ def topk_stream_sample(k: int, n: int) -> int:
 
 
 def topk_stream(q: torch.Tensor, g: torch.Tensor, k: int, qq=None, gg=None, *, sample=None, capacity=None, stats=None,
-                prefilter=None, g_pack=None):
+                prefilter=None, g_pack=None, junk=None):
     """topk_rows(get_euclidean(q, g, qq, gg), k) -- (indices int64 [m, k], squared-L2 distances fp32 [m, k]), the same indices
     and the same distance bits, ties by gallery index -- WITHOUT the m x n matrix (fp32, bf16 or f16 features, q and g of one
     dtype, k <= min(n, 1024); 16-bit features run the contraction on the 16-bit MFMA and the threshold sample, the repair and
@@ -164,7 +164,20 @@ def topk_stream(q: torch.Tensor, g: torch.Tensor, k: int, qq=None, gg=None, *, s
     bounded row chunks.  `stats` (a dict) receives sample, capacity, fallback_rows and max_candidates.
     prefilter = torch.bfloat16 | torch.float16 (fp32 q and g only; default None: everything above, untouched): the SAME result --
     the indices and distance bits of the fp32 path -- with the contraction on the 16-bit MFMA: see _topk_stream_prefilter.
-    g_pack = prefilter_pack(g, prefilter) spares a gallery that is searched many times its rounding pass."""
+    g_pack = prefilter_pack(g, prefilter) spares a gallery that is searched many times its rounding pass.
+    junk = a JunkFilter over the m queries and the n gallery entries (default None: everything above, untouched): the ranked
+    lists of the evaluation protocol -- per query the first k entries that are NOT junk (its own pid seen by its own camera, or
+    by a camera set that holds it), in distance order, ties by gallery index: rank_keep_topk(rank_rows(get_euclidean(q, g)), k,
+    junk) with the distances gathered, the same bits.  The same three stages: the junk cells of the sample slice are masked to
+    +inf before the threshold is taken (a k-th value over junk columns could be too small), the contraction lists an entry
+    only if it is not junk (creid_stream_topk_collect_keep), the select is unchanged.  A query with fewer than k non-junk
+    entries gets those it has, then index -1 and distance +inf; such rows, like overflowed ones, are flagged and redone through
+    get_euclidean + rank_rows + rank_keep_topk in bounded chunks, and count as fallback_rows.  CreidError with prefilter."""
+    if junk is not None:
+        if not isinstance(junk, JunkFilter):
+            raise L.CreidError(f"topk_stream: junk must be a JunkFilter, got {type(junk).__name__}")
+        if prefilter is not None or g_pack is not None:
+            raise L.CreidError("topk_stream: junk= runs the plain streamed kernels: not with prefilter= (no banded junk test)")
     if q.dtype != g.dtype:
         raise L.CreidError(f"topk_stream needs q and g of one dtype (fp32, bf16 or f16), got {q.dtype} and {g.dtype}")
     L.require_gpu(q, g, qq, gg)
@@ -181,6 +194,9 @@ def topk_stream(q: torch.Tensor, g: torch.Tensor, k: int, qq=None, gg=None, *, s
     if not 1 <= k <= min(n, 1024, cap):
         raise L.CreidError(f"topk_stream: k = {k} outside 1 .. min(n = {n}, 1024, capacity = {cap})")
     S = topk_stream_sample(k, n) if sample is None else max(k, min(n, int(sample)))
+    if junk is not None:
+        junk.check_shape(m, n)
+        L.require_gpu(junk.q_pids, junk.g_pids, junk.q_cams, junk.g_cams)
     if prefilter is not None:
         return _topk_stream_prefilter(q, g, k, qq, gg, prefilter, g_pack, S, cap, stats)
     qq = row_sqnorm(q) if qq is None else qq
@@ -190,6 +206,9 @@ def topk_stream(q: torch.Tensor, g: torch.Tensor, k: int, qq=None, gg=None, *, s
     dt = L.dtype_code(q)
     stride = n // S
     gs, ggs = g[::stride][:S].contiguous(), gg[::stride][:S].contiguous()
+    if junk is not None:
+        js = junk.gallery_slice(stride, S)
+        camsets = 1 if junk.camsets else 0
     idx = torch.empty((m, k), dtype=torch.int64, device=dev)
     dsel = torch.empty((m, k), dtype=torch.float32, device=dev)
     flags = torch.zeros(m, dtype=torch.uint8, device=dev)
@@ -198,9 +217,25 @@ def topk_stream(q: torch.Tensor, g: torch.Tensor, k: int, qq=None, gg=None, *, s
     for r0 in range(0, m, step):
         r1 = min(m, r0 + step)
         qc, qqc = q[r0:r1], qq[r0:r1]
-        tau = topk_rows(get_euclidean(qc, gs, qqc, ggs), k)[1][:, k - 1].contiguous()
+        ds = get_euclidean(qc, gs, qqc, ggs)
+        if junk is not None:
+            # the k-th smallest over the sample's NON-junk columns: an upper bound of the k-th smallest non-junk distance
+            L.check(lib.creid_junk_mask_rows(L.ptr(ds), r1 - r0, S, S, L.ptr(junk.q_pids[r0:r1]), L.ptr(js.g_pids),
+                                             L.ptr(junk.q_cams[r0:r1]), L.ptr(js.g_cams), camsets, st), "creid_junk_mask_rows")
+        tau = topk_rows(ds, k)[1][:, k - 1].contiguous()
+        del ds
         cand = torch.empty((r1 - r0, cap), dtype=torch.int64, device=dev)
-        if h16:
+        if junk is not None and h16:
+            L.check(lib.creid_stream_topk_collect_keep_h16(
+                L.ptr(qc), L.ptr(g), L.ptr(qqc), L.ptr(gg), r1 - r0, n, D, dt, L.ptr(tau), L.ptr(junk.q_pids[r0:r1]),
+                L.ptr(junk.g_pids), L.ptr(junk.q_cams[r0:r1]), L.ptr(junk.g_cams), camsets, cap, L.ptr(cand), L.ptr(count[r0:r1]),
+                st), "creid_stream_topk_collect_keep_h16")
+        elif junk is not None:
+            L.check(lib.creid_stream_topk_collect_keep(
+                L.ptr(qc), L.ptr(g), L.ptr(qqc), L.ptr(gg), r1 - r0, n, D, L.ptr(tau), L.ptr(junk.q_pids[r0:r1]),
+                L.ptr(junk.g_pids), L.ptr(junk.q_cams[r0:r1]), L.ptr(junk.g_cams), camsets, cap, L.ptr(cand), L.ptr(count[r0:r1]),
+                st), "creid_stream_topk_collect_keep")
+        elif h16:
             L.check(lib.creid_stream_topk_collect_h16(L.ptr(qc), L.ptr(g), L.ptr(qqc), L.ptr(gg), r1 - r0, n, D, dt, L.ptr(tau),
                                                       cap, L.ptr(cand), L.ptr(count[r0:r1]), st), "creid_stream_topk_collect_h16")
         else:
@@ -209,7 +244,10 @@ def topk_stream(q: torch.Tensor, g: torch.Tensor, k: int, qq=None, gg=None, *, s
         L.check(lib.creid_stream_topk_select(L.ptr(cand), L.ptr(count[r0:r1]), r1 - r0, cap, k, L.ptr(idx[r0:r1]),
                                              L.ptr(dsel[r0:r1]), L.ptr(flags[r0:r1]), st), "creid_stream_topk_select")
         del tau, cand
-    bad = _topk_stream_repair(q, g, k, qq, gg, flags, idx, dsel)
+    if junk is not None:
+        bad = _topk_stream_repair_keep(q, g, k, qq, gg, flags, idx, dsel, junk)
+    else:
+        bad = _topk_stream_repair(q, g, k, qq, gg, flags, idx, dsel)
     if stats is not None:
         stats.update(sample=S, capacity=cap, fallback_rows=bad, max_candidates=int(count.max().item()) if m else 0)
     return idx, dsel
@@ -226,6 +264,107 @@ def _topk_stream_repair(q, g, k, qq, gg, flags, idx, dsel) -> int:
         idx.index_copy_(0, sel, ridx)
         dsel.index_copy_(0, sel, rd)
     return int(bad.numel())
+
+
+def _topk_stream_repair_keep(q, g, k, qq, gg, flags, idx, dsel, junk) -> int:
+    """_topk_stream_repair for topk_stream(junk=...): the flagged rows (overflowed lists, rows with fewer than k non-junk
+    entries, NaN rows) through get_euclidean + rank_rows + rank_keep_topk, the distances gathered (+inf in the padding)."""
+    bad = torch.nonzero(flags).flatten()
+    rows = max(1, _STREAM_TOPK_CHUNK_BYTES // (g.shape[0] * 16))          # distances, ranked indices and the rank's share
+    for b0 in range(0, bad.numel(), rows):
+        sel = bad[b0:b0 + rows]
+        d = get_euclidean(q.index_select(0, sel), g, qq.index_select(0, sel), gg)
+        ridx = rank_keep_topk(rank_rows(d), k, junk.rows(sel))[0]
+        idx.index_copy_(0, sel, ridx)
+        dsel.index_copy_(0, sel, gather_ranked(d, ridx))
+        del d, ridx
+    return int(bad.numel())
+
+
+class JunkFilter:
+    """The labels the evaluation protocol filters a ranked list with (utils/eval_reid.py:49-58, utils/visrank.py:193-232), as
+    int64 tensors: gallery entry j is JUNK for query i when g_pids[j] == q_pids[i] and its camera test holds -- plain camera
+    ids: g_cams[j] == q_cams[i]; camsets=True: g_cams[j] is a bitmask of cameras (bit c = camera c, 0..62) and bit q_cams[i]
+    is set.  What CMC / mAP drop per query, and what rank_keep_topk / topk_stream(junk=...) / R1_mAP(ranked_topk=...) leave
+    out of the ranked lists."""
+
+    def __init__(self, q_pids, q_cams, g_pids, g_cams, camsets=False):
+        dev = next((a.device for a in (q_pids, q_cams, g_pids, g_cams) if isinstance(a, torch.Tensor)), torch.device("cpu"))
+        self.q_pids, self.q_cams, self.g_pids, self.g_cams = (_dev_i64(a, dev) for a in (q_pids, q_cams, g_pids, g_cams))
+        self.camsets = bool(camsets)
+        if self.q_pids.dim() != 1 or self.g_pids.dim() != 1 or self.q_cams.shape != self.q_pids.shape or \
+                self.g_cams.shape != self.g_pids.shape:
+            raise L.CreidError("JunkFilter needs one pid and one camera (or camera-set mask) per query and per gallery entry, got "
+                               f"{tuple(self.q_pids.shape)}, {tuple(self.q_cams.shape)}, {tuple(self.g_pids.shape)}, "
+                               f"{tuple(self.g_cams.shape)}")
+
+    @classmethod
+    def from_labels(cls, pids, camids, num_query, device, respect_camids=False):
+        """pids / camids as R1_mAP.compute receives them: [nq + ng] vectors (lists, numpy, tensors), queries first; with
+        respect_camids=True camids is a list of camera-id lists ([c] for a query) or a CameraSets, whose device masks and query
+        cameras are used as they are.  Camera ids beyond 62 with sets: CreidError."""
+        nq = int(num_query)
+        p = pids if isinstance(pids, torch.Tensor) else np.asarray(pids)
+        if respect_camids:
+            q_cams, g_masks = _camset_split(camids, nq)
+            return cls(_dev_i64(p[:nq], device), _dev_i64(q_cams, device), _dev_i64(p[nq:], device), _dev_i64(g_masks, device),
+                       camsets=True)
+        c = camids if isinstance(camids, torch.Tensor) else np.asarray(camids)
+        return cls(_dev_i64(p[:nq], device), _dev_i64(c[:nq], device), _dev_i64(p[nq:], device), _dev_i64(c[nq:], device))
+
+    def check_shape(self, m, n):
+        if self.q_pids.shape[0] != m or self.g_pids.shape[0] != n:
+            raise L.CreidError(f"JunkFilter of {self.q_pids.shape[0]} queries x {self.g_pids.shape[0]} gallery entries on "
+                               f"{m} x {n} rows")
+
+    def rows(self, sel):
+        """The filter of the queries `sel` (a slice or an index tensor) against the same gallery."""
+        out = JunkFilter.__new__(JunkFilter)
+        take = (lambda a: a[sel].contiguous()) if isinstance(sel, slice) else (lambda a: a.index_select(0, sel))
+        out.q_pids, out.q_cams, out.g_pids, out.g_cams, out.camsets = take(self.q_pids), take(self.q_cams), self.g_pids, \
+            self.g_cams, self.camsets
+        return out
+
+    def gallery_slice(self, stride, count):
+        """The filter of the same queries against gallery entries 0, stride, 2 stride, ... (`count` of them)."""
+        out = JunkFilter.__new__(JunkFilter)
+        out.q_pids, out.q_cams, out.camsets = self.q_pids, self.q_cams, self.camsets
+        out.g_pids, out.g_cams = self.g_pids[::stride][:count].contiguous(), self.g_cams[::stride][:count].contiguous()
+        return out
+
+    def matched(self, idx):
+        """g_pids[idx] == the row's pid for a list of ranked indices [m, k]; False where idx is the padding (-1)."""
+        real = idx >= 0
+        return (self.g_pids[idx.clamp(min=0)] == self.q_pids[:, None]) & real
+
+
+def rank_keep_topk(indices: torch.Tensor, k: int, junk: JunkFilter):
+    """From ranked gallery indices int64 [m, n] (rank_rows) the first k entries of every row that are not junk, in order:
+    (idx int64 [m, k] padded with -1, matched bool [m, k]: the entry has the query's pid, count int32 [m]: the real entries).
+    creid_rank_keep_topk: one wave per query, no atomics.  1 <= k <= 1024."""
+    L.require_gpu(indices, junk.q_pids, junk.g_pids, junk.q_cams, junk.g_cams)
+    if indices.dtype != torch.int64 or indices.dim() != 2:
+        raise L.CreidError("rank_keep_topk needs ranked indices int64 [m, n]")
+    m, n = indices.shape
+    k = int(k)
+    if not 1 <= k <= 1024:
+        raise L.CreidError(f"rank_keep_topk: k = {k} outside 1 .. 1024")
+    if junk.q_pids.shape[0] != m:
+        raise L.CreidError(f"rank_keep_topk: {m} ranked rows but a JunkFilter of {junk.q_pids.shape[0]} queries")
+    indices = indices.contiguous()
+    dev = indices.device
+    idx = torch.empty((m, k), dtype=torch.int64, device=dev)
+    matched = torch.empty((m, k), dtype=torch.uint8, device=dev)
+    count = torch.empty(m, dtype=torch.int32, device=dev)
+    L.check(L.lib().creid_rank_keep_topk(L.ptr(indices), m, n, junk.g_pids.shape[0], k, L.ptr(junk.q_pids), L.ptr(junk.g_pids),
+                                         L.ptr(junk.q_cams), L.ptr(junk.g_cams), 1 if junk.camsets else 0, L.ptr(idx),
+                                         L.ptr(matched), L.ptr(count), L.stream()), "creid_rank_keep_topk")
+    return idx, matched.bool(), count
+
+
+def gather_ranked(distmat: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    """distmat[i, idx[i, :]] for ranked lists padded with -1: +inf in the padding."""
+    return torch.gather(distmat, 1, idx.clamp(min=0)).masked_fill_(idx < 0, float("inf"))
 
 
 STREAM_RESCORE_CAPACITY = 1024        # entries of one query creid_stream_topk_rescore re-scores (RS_CAP, csrc/stream_prefilter.hip)
@@ -1162,7 +1301,7 @@ class R1_mAP:
 
     def __init__(self, pl_module=None, num_query=0, max_rank=50, feat_norm=True, dist_func="euclidean",
                  compute_dtype=torch.float32, streamed=False, reranking=False, prefilter=None, prefilter_capacity=None,
-                 query_expansion=False):
+                 query_expansion=False, ranked_topk=None):
         """streamed=True: metric-only evaluation that never materialises the distance / index matrices (euclidean; plain
         camera ids or, with compute(respect_camids=True), camera sets; compute_dtype fp32, bf16 or f16 -- the 16-bit modes
         run the 16-bit MFMA and return exactly what their materialised evaluation returns); `last` then holds the per-query
@@ -1186,7 +1325,18 @@ class R1_mAP:
         re-ranking, camera sets -- then runs on the expanded rows, exactly as R1_mAP(feat_norm=False) runs on the rows
         query_expansion returns.  `prefilter` also goes to the expansion's neighbour search.  `last["query_expansion"]` holds the
         options and query_expansion's stats (stage_ms when `last` came in holding {"query_expansion": {"timing": True}}).
-        CreidError with feat_norm=False: expansion is defined on unit rows."""
+        CreidError with feat_norm=False: expansion is defined on unit rows.
+        ranked_topk=K (an int, 1 .. 1024; default None: nothing changes): after the metrics, `last["ranked"]` holds the ranked
+        lists the metrics are defined on -- per query the first K' = min(K, gallery size) gallery entries that are not junk (the
+        query's pid seen by its camera, or by a camera set that holds it: utils/eval_reid.py:49-58, what utils/visrank.py:193-232
+        draws) -- as device tensors: indices int64 [nq, K'] (padded with -1), distances fp32 [nq, K'] (+inf in the padding),
+        matched bool [nq, K'] (the entry has the query's pid) and count int32 [nq] (the real entries).  On every route and with
+        every other option; streamed routes build them with topk_stream(junk=...) on the rows the evaluation multiplied (no
+        matrix; with prefilter= too, by the plain streamed kernels), materialised ones with rank_keep_topk on `last["indices"]`.
+        The metrics returned are those of the same call without the keyword."""
+        if ranked_topk is not None and not (_is_int(ranked_topk) and 1 <= ranked_topk <= 1024):
+            raise L.CreidError(f"R1_mAP(ranked_topk=...) must be an int, 1 .. 1024, got {ranked_topk!r}")
+        self.ranked_topk = None if ranked_topk is None else int(ranked_topk)
         self.reranking = rerank_options(reranking)
         self.query_expansion = expansion_options(query_expansion)
         if self.query_expansion is not None and not feat_norm:
@@ -1240,6 +1390,11 @@ class R1_mAP:
         if self._qe_info is not None:
             self.last["query_expansion"] = self._qe_info
 
+    def _ranked_from_indices(self, indices, distmat, junk):
+        """The materialised routes' `last["ranked"]`: the first K' non-junk entries of the ranked rows and their distances."""
+        idx, matched, count = rank_keep_topk(indices, min(self.ranked_topk, indices.shape[1]), junk)
+        return dict(indices=idx, distances=gather_ranked(distmat, idx), matched=matched, count=count)
+
     def compute(self, feats, pids, camids, respect_camids=False):
         if not isinstance(feats, torch.Tensor) or not feats.is_cuda:
             raise L.CreidError("R1_mAP.compute needs device features (no CPU fallback)")
@@ -1269,6 +1424,9 @@ class R1_mAP:
             cmc, mAP, all_topk, single = eval_func(indices, pids[:nq], pids[nq:], camids[:nq], camids[nq:],
                                                    self.max_rank, respect_camids)
             self.last = dict(distmat=distmat, indices=indices, single_performance=single)
+            if self.ranked_topk is not None:
+                self.last["ranked"] = self._ranked_from_indices(
+                    indices, distmat, JunkFilter.from_labels(pids, camids, nq, feats.device, respect_camids=True))
             self._keep_expansion_info()
             return cmc, mAP, all_topk
         # np.argsort + eval_func's per-query loop in ONE pass: the ranked rows are evaluated while they are still in LDS
@@ -1284,6 +1442,8 @@ class R1_mAP:
         vi = np.nonzero(valid_h)[0]
         single = np.stack([vi.astype(np.float64), pids[:nq][vi].astype(np.float64), pack[max_rank + 6 + nq:][vi]], axis=1)
         self.last = dict(distmat=distmat, indices=indices, single_performance=single, valid=valid, ap=ap, first=first)
+        if self.ranked_topk is not None:
+            self.last["ranked"] = self._ranked_from_indices(indices, distmat, JunkFilter.from_labels(pids, camids, nq, feats.device))
         self._keep_expansion_info()
         return pack[:max_rank].astype(np.float32), float(pack[max_rank]), pack[max_rank + 1:max_rank + 6].copy()
 
@@ -1401,6 +1561,12 @@ class R1_mAP:
         self.last = dict(valid=valid, ap=ap, first=first, single_performance=single, plan=plan)
         if info is not None:
             self.last["prefilter"] = info
+        if self.ranked_topk is not None:
+            # the lists the metrics above are defined on, from the rows and norms the evaluation multiplied: no matrix either
+            junk = JunkFilter(plan.q_pids, plan.q_cams, plan.g_pids, plan.g_cams, camsets=plan.camsets)
+            ridx, rdist = topk_stream(fq, fg, min(self.ranked_topk, fg.shape[0]), qq, gg, junk=junk)
+            self.last["ranked"] = dict(indices=ridx, distances=rdist, matched=junk.matched(ridx),
+                                       count=(ridx >= 0).sum(1, dtype=torch.int32))
         self._keep_expansion_info()
         return cmc_h, mAP_h, topk_h
 
@@ -1440,14 +1606,20 @@ class R1_mAP:
         dev = feats.device
         gp, gc = _dev_i64(pids[nq:], dev), _dev_i64(camids[nq:], dev)
         vs, aps, firsts = [], [], []
+        junk = JunkFilter.from_labels(pids, camids, nq, dev) if self.ranked_topk is not None else None
+        ranked = []
         for lo in range(0, nq, query_chunk):
             hi = min(nq, lo + query_chunk)
             d = get_euclidean(f[lo:hi], g, sq[lo:hi].contiguous(), gg) if euclid else self.dist_func(f[lo:hi].contiguous(), g)
             idx = rank_rows(d)
+            if junk is not None:                                  # per chunk, before its matrix and indices are freed
+                ranked.append(self._ranked_from_indices(idx, d, junk.rows(slice(lo, hi))))
             del d
             _, _, _, _, v, a, fr = eval_func_device(idx, pids[lo:hi], gp, camids[lo:hi], gc, self.max_rank)
             vs.append(v); aps.append(a); firsts.append(fr)
             del idx
         v = torch.cat(vs).cpu().numpy() > 0; a = torch.cat(aps).cpu().numpy(); fr = torch.cat(firsts).cpu().numpy()
+        if junk is not None:
+            self.last = dict(ranked={key: torch.cat([r[key] for r in ranked]) for key in ranked[0]})
         self._keep_expansion_info()
         return merge_eval_results(v, a, fr, min(self.max_rank, g.shape[0]))

@@ -231,6 +231,34 @@ int creid_stream_topk_collect_h16(const void* q, const void* g, const float* qq,
                                   int64_t D, int dtype, const float* tau, int32_t cap, uint64_t* cand, int32_t* count,
                                   void* stream);
 
+/* ---- ranked lists under the evaluation protocol, with NO m x n matrix: the first k gallery entries of a query that are not
+ * junk (utils/eval_reid.py:49-58, the lists utils/visrank.py:193-232 draws).  Entry j is junk for query i when
+ * g_pids[j] == q_pids[i] and -- camsets == 0 -- g_cams[j] == q_cams[i], or -- camsets != 0 -- bit q_cams[i] of the camera-set
+ * mask g_cams[j] is set (q_cams inside 0..62: the CALLER checks, as for creid_stream_plan_camsets).  All four int64, on the
+ * device.
+ *  collect_keep / collect_keep_h16: creid_stream_topk_collect / _h16 -- same arguments, limits, checks and distance bits --
+ *            where a column takes a slot only if it is not junk.  tau must bound the k-th smallest distance over the row's
+ *            NON-junk columns.  creid_stream_topk_select then serves unchanged: a row with fewer than k entries is flagged.
+ *  creid_rank_keep_topk: the materialised form.  idx int64 [m][n]: ranked gallery indices (creid_rank_rows); ng: the length
+ *            of g_pids / g_cams (an index outside [0, ng) is dropped).  out_idx int64 [m][k]: the first k non-junk entries of
+ *            each row in order, padded with -1; out_matched uint8 [m][k]: g_pids[out_idx] == q_pids[row], 0 in the padding;
+ *            out_count int32 [m]: the entries that are real.  1 <= k <= 1024 else CREID_E_SHAPE; m == 0 returns 0.
+ *  creid_junk_mask_rows: dist fp32 [m][ld >= n], column j = entry j of g_pids / g_cams: junk cells become +inf, in place (the
+ *            threshold sample of the streamed form). */
+int creid_stream_topk_collect_keep(const float* q, const float* g, const float* qq, const float* gg, int64_t m, int64_t n,
+                                   int64_t D, const float* tau, const int64_t* q_pids, const int64_t* g_pids,
+                                   const int64_t* q_cams, const int64_t* g_cams, int32_t camsets, int32_t cap, uint64_t* cand,
+                                   int32_t* count, void* stream);
+int creid_stream_topk_collect_keep_h16(const void* q, const void* g, const float* qq, const float* gg, int64_t m, int64_t n,
+                                       int64_t D, int dtype, const float* tau, const int64_t* q_pids, const int64_t* g_pids,
+                                       const int64_t* q_cams, const int64_t* g_cams, int32_t camsets, int32_t cap,
+                                       uint64_t* cand, int32_t* count, void* stream);
+int creid_rank_keep_topk(const int64_t* idx, int64_t m, int64_t n, int64_t ng, int32_t k, const int64_t* q_pids,
+                         const int64_t* g_pids, const int64_t* q_cams, const int64_t* g_cams, int32_t camsets,
+                         int64_t* out_idx, uint8_t* out_matched, int32_t* out_count, void* stream);
+int creid_junk_mask_rows(float* dist, int64_t m, int64_t n, int64_t ld, const int64_t* q_pids, const int64_t* g_pids,
+                         const int64_t* q_cams, const int64_t* g_cams, int32_t camsets, void* stream);
+
 /* ---- exact fp32 top-k with the contraction on the 16-bit MFMA (csrc/stream_prefilter.hip): the 16-bit streamed contraction
  * only pre-filters, with a proven margin; the pairs it keeps are re-scored with the fp32 kernels' arithmetic, so the result has
  * the indices and the distance bits of creid_stream_topk_collect + creid_stream_topk_select on the fp32 rows.
