@@ -5,6 +5,7 @@
 #pragma once
 #include "common.hpp"
 #include <stdlib.h>
+#include <type_traits>
 
 constexpr int SQ_TM = 64, SQ_TN = 256;           // a tile: 64 query rows x 256 gallery columns (four units of 64 columns)
 constexpr int EPI_COUNT = 0, EPI_TOPK = 1;       // what a streamed contraction does with a finished tile
@@ -108,6 +109,62 @@ static int stream_count_launch(const StreamSplit& sp, int cap, void* stream, Arg
   if (attr_rc != hipSuccess) return (int)attr_rc;
   hipLaunchKernelGGL(Kernel, dim3(sp.grid), dim3(256), (size_t)(2 * SQ_TM * cap + EXTRA) * sizeof(unsigned), as_stream(stream), args...);
   return (int)hipGetLastError();
+}
+
+/* The arguments of a streamed contraction, in the groups its epilogues read.  An entry point fills the groups of its epilogue
+ * and leaves the others empty ({}); stream_args_pass tests exactly the groups the epilogue uses, and the kernels receive the
+ * empty ones as null pointers and zeros. */
+struct StreamRows { const void *q, *g; const float *qq, *gg; int64_t m, n, D; };       // the operands and their square norms
+struct StreamPids { const int64_t *q_pids = nullptr, *g_pids = nullptr; };             // EPI_COUNT, EPI_BAND, EPI_TOPK_KEEP
+struct StreamPos {                                                                     // EPI_COUNT, EPI_BAND: the positive lists
+  int32_t cap = 0;
+  const uint32_t* key = nullptr;
+  const int32_t *idx = nullptr, *npos = nullptr;
+  uint32_t* hist = nullptr;
+};
+struct StreamList {       // EPI_TOPK[_KEEP]: thresholds and candidate lists; EPI_BAND: row margins and the lists of ambiguous pairs
+  const float* thr = nullptr;
+  unsigned long long* list = nullptr;
+  int32_t* count = nullptr;
+  int32_t cap = 0;
+};
+struct StreamCams { const int64_t *q_cams = nullptr, *g_cams = nullptr; int camsets = 0; };   // EPI_TOPK_KEEP
+
+/* The argument tests of every streamed contraction; false: return *rc (0: nothing to do).  d_mult / d_max: the widths the
+ * kernel loads; dtype_ok: the 16-bit kernels' dtype test.  An empty query set is a no-op -- for the count epilogues whatever
+ * the capacities and widths are, for the top-k epilogues once they have passed: the precedence each family of entry points
+ * has always had (tests/test_stream_h16_cpu.py and the *_abi_argument_checks GPU tests pin both). */
+template <int EPI>
+static bool stream_args_pass(const StreamRows& x, const StreamPids& pids, const StreamPos& pos, const StreamList& list,
+                             const StreamCams& cams, int64_t d_mult, int64_t d_max, bool dtype_ok, int* rc) {
+  constexpr bool topk = epi_is_topk(EPI);
+  constexpr bool use_pids = EPI != EPI_TOPK, use_pos = !topk, use_list = EPI != EPI_COUNT, use_cams = EPI == EPI_TOPK_KEEP;
+  const bool ptrs = x.q && x.g && x.qq && x.gg && (!use_pids || (pids.q_pids && pids.g_pids)) &&
+                    (!use_pos || (pos.key && pos.idx && pos.npos && pos.hist)) &&
+                    (!use_list || (list.thr && list.list && list.count)) && (!use_cams || (cams.q_cams && cams.g_cams));
+  const auto stop = [rc](int code) { *rc = code; return false; };
+  if (!(x.m >= 0 && x.n > 0 && x.D > 0)) return stop(CREID_E_ARG);
+  if (!topk && x.m == 0) return stop(0);
+  if (!topk && !ptrs) return stop(CREID_E_ARG);
+  if ((use_pos && !stream_count_cap_ok(pos.cap)) || (use_list && !stream_topk_cap_ok(list.cap)) || x.D % d_mult != 0 || x.D > d_max)
+    return stop(CREID_E_SHAPE);
+  if (!stream_mn_ok(x.m, x.n)) return stop(CREID_E_SHAPE);
+  if (!dtype_ok) return stop(CREID_E_DTYPE);
+  if (x.m == 0) return stop(0);
+  if (!ptrs) return stop(CREID_E_ARG);
+  return true;
+}
+
+/* Launch of either file's kernel for the epilogue EPI: the count epilogues through stream_count_launch (dynamic LDS; the banded
+ * count with its row margins behind the lists), the top-k epilogues with static LDS only. */
+template <auto Kernel, int EPI, class... Args>
+static int stream_launch(const StreamSplit& sp, int pos_cap, void* stream, Args... args) {
+  if constexpr (epi_is_topk(EPI)) {
+    hipLaunchKernelGGL(Kernel, dim3(sp.grid), dim3(256), 0, as_stream(stream), args...);
+    CREID_LAUNCH_RET();
+  } else {
+    return stream_count_launch<Kernel, EPI == EPI_BAND ? SQ_TM : 0>(sp, pos_cap, stream, args...);
+  }
 }
 
 // Device side of the split: the run [g0, g1) of workgroup blockIdx.x, in units of the rows laid end to end.

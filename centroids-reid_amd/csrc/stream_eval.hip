@@ -501,6 +501,26 @@ static int stream_poslist_launch(const float* q, const float* g, const float* qq
   CREID_LAUNCH_RET();
 }
 
+/* The one host side of the streamed fp32 contraction: the argument tests, the work split, and the launch of the kernel for the
+ * epilogue EPI with the groups it does not use left empty.  ABL / skip_count: the timing ablation of creid_stream_count. */
+template <int EPI, int ABL = 0>
+static int stream_f32_launch(const StreamRows& x, const StreamPids& pids, const StreamPos& pos, const StreamList& list,
+                             const StreamCams& cams, void* stream, int skip_count = 0) {
+  int rc;
+  if (!stream_args_pass<EPI>(x, pids, pos, list, cams, 4, INT64_MAX, true, &rc)) return rc;
+  constexpr bool topk = epi_is_topk(EPI);
+  const StreamSplit sp = stream_split(x.m, x.n, x.D);
+  const int cap = topk ? list.cap : pos.cap, log2cap = topk ? 0 : stream_log2cap(pos.cap);
+  const auto launch = [&](auto fullk) {
+    constexpr bool F = decltype(fullk)::value;
+    return stream_launch<sqdist_count_f32_kernel<F ? ABL : 0, F, EPI>, EPI>(
+        sp, pos.cap, stream, static_cast<const float*>(x.q), static_cast<const float*>(x.g), x.qq, x.gg, (int)x.m, (int)x.n,
+        (int)x.D, pids.q_pids, pids.g_pids, cap, log2cap, pos.key, pos.idx, pos.npos, pos.hist, sp.tiles_m, sp.U, sp.upw, sp.mode,
+        skip_count, list.thr, list.list, list.count, cams.q_cams, cams.g_cams, cams.camsets);
+  };
+  return x.D % SQ_BK == 0 ? launch(std::true_type{}) : launch(std::false_type{});
+}
+
 extern "C" {
 
 /* Device-side index for the streamed evaluation.  g_pids / g_cams int64[n], q_pids / q_cams int64[m] on the device; the pid
@@ -543,40 +563,26 @@ int creid_stream_poslist_camsets(const float* q, const float* g, const float* qq
 int creid_stream_count(const float* q, const float* g, const float* qq, const float* gg, int64_t m, int64_t n, int64_t D,
                        const int64_t* q_pids, const int64_t* g_pids, int32_t cap, const uint32_t* pos_key,
                        const int32_t* pos_idx, const int32_t* npos, uint32_t* hist, void* stream) {
-  CREID_CHECK_ARG(m >= 0 && n > 0 && D > 0);
-  if (m == 0) return 0;
-  CREID_CHECK_ARG(q && g && qq && gg && q_pids && g_pids && pos_key && pos_idx && npos && hist);
-  if (!stream_count_cap_ok(cap) || D % 4 != 0) return CREID_E_SHAPE;
-  if (!stream_mn_ok(m, n)) return CREID_E_SHAPE;
-  const int log2cap = stream_log2cap(cap);
   // timing ablation only (CREID_STREAM_NOEPI=1: contraction without the count epilogue -- results are then wrong)
   static const int skip_count = creid_ablation_env("CREID_STREAM_NOEPI");
-  const StreamSplit sp = stream_split(m, n, D);
-#define CREID_COUNT_LAUNCH_(A, F)                                                                                     \
-  return stream_count_launch<sqdist_count_f32_kernel<A, F>>(                                                           \
-      sp, (int)cap, stream, q, g, qq, gg, (int)m, (int)n, (int)D, q_pids, g_pids, (int)cap, log2cap, pos_key, pos_idx, npos, hist, \
-      sp.tiles_m, sp.U, sp.upw, sp.mode, skip_count & 1, (const float*)nullptr, (unsigned long long*)nullptr, (int32_t*)nullptr, \
-      (const int64_t*)nullptr, (const int64_t*)nullptr, 0)
-#define CREID_COUNT_LAUNCH(A)                                                                                          \
-  do { if (D % SQ_BK == 0) CREID_COUNT_LAUNCH_(A, true); else CREID_COUNT_LAUNCH_(0, false); } while (0)
+#define CREID_COUNT_LAUNCH(A)                                                                                                   \
+  return stream_f32_launch<EPI_COUNT, A>({q, g, qq, gg, m, n, D}, {q_pids, g_pids}, {cap, pos_key, pos_idx, npos, hist}, {}, {}, stream, \
+                                         skip_count & 1)
 #ifdef CREID_ABL_BUILD
   switch (skip_count >> 1) {
-    case 1: CREID_COUNT_LAUNCH(2); break;
-    case 2: CREID_COUNT_LAUNCH(4); break;
-    case 3: CREID_COUNT_LAUNCH(6); break;
-    case 4: CREID_COUNT_LAUNCH(8); break;
-    case 7: CREID_COUNT_LAUNCH(14); break;
-    case 8: CREID_COUNT_LAUNCH(16); break;
-    case 15: CREID_COUNT_LAUNCH(30); break;
-    case 16: CREID_COUNT_LAUNCH(32); break;
-    case 32: CREID_COUNT_LAUNCH(64); break;
-    default: CREID_COUNT_LAUNCH(0); break;
+    case 1: CREID_COUNT_LAUNCH(2);
+    case 2: CREID_COUNT_LAUNCH(4);
+    case 3: CREID_COUNT_LAUNCH(6);
+    case 4: CREID_COUNT_LAUNCH(8);
+    case 7: CREID_COUNT_LAUNCH(14);
+    case 8: CREID_COUNT_LAUNCH(16);
+    case 15: CREID_COUNT_LAUNCH(30);
+    case 16: CREID_COUNT_LAUNCH(32);
+    case 32: CREID_COUNT_LAUNCH(64);
   }
-#else
-  CREID_COUNT_LAUNCH(0);
 #endif
+  CREID_COUNT_LAUNCH(0);
 #undef CREID_COUNT_LAUNCH
-#undef CREID_COUNT_LAUNCH_
 }
 
 int creid_stream_finalize(const int32_t* npos, const uint32_t* hist, int64_t m, int32_t cap, uint8_t* valid, double* ap,
@@ -591,42 +597,17 @@ int creid_stream_finalize(const int32_t* npos, const uint32_t* hist, int64_t m, 
 
 int creid_stream_topk_collect(const float* q, const float* g, const float* qq, const float* gg, int64_t m, int64_t n,
                               int64_t D, const float* tau, int32_t cap, uint64_t* cand, int32_t* count, void* stream) {
-  CREID_CHECK_ARG(m >= 0 && n > 0 && D > 0);
-  if (!stream_topk_cap_ok(cap) || D % 4 != 0) return CREID_E_SHAPE;
-  if (!stream_mn_ok(m, n)) return CREID_E_SHAPE;
-  if (m == 0) return 0;
-  CREID_CHECK_ARG(q && g && qq && gg && tau && cand && count);
-  const StreamSplit sp = stream_split(m, n, D);
-#define CREID_TOPK_LAUNCH(F)                                                                                            \
-  hipLaunchKernelGGL((sqdist_count_f32_kernel<0, F, EPI_TOPK>), dim3(sp.grid), dim3(256), 0, as_stream(stream),         \
-                     q, g, qq, gg, (int)m, (int)n, (int)D, (const int64_t*)nullptr, (const int64_t*)nullptr, (int)cap, 0, \
-                     (const unsigned*)nullptr, (const int32_t*)nullptr, (const int32_t*)nullptr, (unsigned*)nullptr,    \
-                     sp.tiles_m, sp.U, sp.upw, sp.mode, 0, tau, reinterpret_cast<unsigned long long*>(cand), count,     \
-                     (const int64_t*)nullptr, (const int64_t*)nullptr, 0)
-  if (D % SQ_BK == 0) CREID_TOPK_LAUNCH(true); else CREID_TOPK_LAUNCH(false);
-#undef CREID_TOPK_LAUNCH
-  CREID_LAUNCH_RET();
+  return stream_f32_launch<EPI_TOPK>({q, g, qq, gg, m, n, D}, {}, {},
+                                     {tau, reinterpret_cast<unsigned long long*>(cand), count, cap}, {}, stream);
 }
 
 int creid_stream_topk_collect_keep(const float* q, const float* g, const float* qq, const float* gg, int64_t m, int64_t n,
                                    int64_t D, const float* tau, const int64_t* q_pids, const int64_t* g_pids,
                                    const int64_t* q_cams, const int64_t* g_cams, int32_t camsets, int32_t cap, uint64_t* cand,
                                    int32_t* count, void* stream) {
-  CREID_CHECK_ARG(m >= 0 && n > 0 && D > 0);
-  if (!stream_topk_cap_ok(cap) || D % 4 != 0) return CREID_E_SHAPE;
-  if (!stream_mn_ok(m, n)) return CREID_E_SHAPE;
-  if (m == 0) return 0;
-  CREID_CHECK_ARG(q && g && qq && gg && tau && q_pids && g_pids && q_cams && g_cams && cand && count);
-  const StreamSplit sp = stream_split(m, n, D);
-#define CREID_TOPK_KEEP_LAUNCH(F)                                                                                       \
-  hipLaunchKernelGGL((sqdist_count_f32_kernel<0, F, EPI_TOPK_KEEP>), dim3(sp.grid), dim3(256), 0, as_stream(stream),    \
-                     q, g, qq, gg, (int)m, (int)n, (int)D, q_pids, g_pids, (int)cap, 0,                                 \
-                     (const unsigned*)nullptr, (const int32_t*)nullptr, (const int32_t*)nullptr, (unsigned*)nullptr,    \
-                     sp.tiles_m, sp.U, sp.upw, sp.mode, 0, tau, reinterpret_cast<unsigned long long*>(cand), count,     \
-                     q_cams, g_cams, camsets != 0 ? 1 : 0)
-  if (D % SQ_BK == 0) CREID_TOPK_KEEP_LAUNCH(true); else CREID_TOPK_KEEP_LAUNCH(false);
-#undef CREID_TOPK_KEEP_LAUNCH
-  CREID_LAUNCH_RET();
+  return stream_f32_launch<EPI_TOPK_KEEP>({q, g, qq, gg, m, n, D}, {q_pids, g_pids}, {},
+                                          {tau, reinterpret_cast<unsigned long long*>(cand), count, cap},
+                                          {q_cams, g_cams, camsets != 0 ? 1 : 0}, stream);
 }
 
 int creid_stream_topk_select(const uint64_t* cand, const int32_t* count, int64_t m, int32_t cap, int32_t k, int64_t* out_idx,

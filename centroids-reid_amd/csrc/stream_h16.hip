@@ -318,6 +318,25 @@ static int stream_poslist_h16_launch(const void* q, const void* g, const float* 
   CREID_LAUNCH_RET();
 }
 
+/* The one host side of the streamed 16-bit contraction: the argument tests, the work split, and the launch of the kernel for
+ * the dtype and the epilogue EPI with the groups it does not use left empty. */
+template <int EPI>
+static int stream_h16_launch(const StreamRows& x, int dtype, const StreamPids& pids, const StreamPos& pos, const StreamList& list,
+                             const StreamCams& cams, void* stream) {
+  int rc;
+  if (!stream_args_pass<EPI>(x, pids, pos, list, cams, 8, H_MAX_D, creid_is16(dtype), &rc)) return rc;
+  constexpr bool topk = epi_is_topk(EPI);
+  const StreamSplit sp = stream_split(x.m, x.n, x.D, 2);
+  const int cap = topk ? list.cap : pos.cap, log2cap = topk ? 0 : stream_log2cap(pos.cap), acap = EPI == EPI_BAND ? list.cap : 0;
+  const auto launch = [&](auto dt) {
+    return stream_launch<sqdist_stream_h16_kernel<decltype(dt)::value, EPI>, EPI>(
+        sp, pos.cap, stream, static_cast<const unsigned short*>(x.q), static_cast<const unsigned short*>(x.g), x.qq, x.gg, (int)x.m,
+        (int)x.n, (int)x.D, pids.q_pids, pids.g_pids, cap, log2cap, pos.key, pos.idx, pos.npos, pos.hist, sp.tiles_m, sp.U, sp.upw,
+        sp.mode, list.thr, list.list, list.count, acap, cams.q_cams, cams.g_cams, cams.camsets);
+  };
+  return dtype == CREID_BF16 ? launch(std::integral_constant<int, CREID_BF16>{}) : launch(std::integral_constant<int, CREID_F16>{});
+}
+
 extern "C" {
 
 int creid_stream_poslist_h16(const void* q, const void* g, const float* qq, const float* gg, int64_t m, int64_t n, int64_t D,
@@ -340,93 +359,32 @@ int creid_stream_poslist_h16_camsets(const void* q, const void* g, const float* 
 int creid_stream_count_h16(const void* q, const void* g, const float* qq, const float* gg, int64_t m, int64_t n, int64_t D,
                            int dtype, const int64_t* q_pids, const int64_t* g_pids, int32_t cap, const uint32_t* pos_key,
                            const int32_t* pos_idx, const int32_t* npos, uint32_t* hist, void* stream) {
-  CREID_CHECK_ARG(m >= 0 && n > 0 && D > 0);
-  if (m == 0) return 0;
-  CREID_CHECK_ARG(q && g && qq && gg && q_pids && g_pids && pos_key && pos_idx && npos && hist);
-  if (!stream_count_cap_ok(cap) || D % 8 != 0 || D > H_MAX_D) return CREID_E_SHAPE;
-  if (!stream_mn_ok(m, n)) return CREID_E_SHAPE;
-  if (!creid_is16(dtype)) return CREID_E_DTYPE;
-  const int log2cap = stream_log2cap(cap);
-  const StreamSplit sp = stream_split(m, n, D, 2);
-  const unsigned short* qh = static_cast<const unsigned short*>(q);
-  const unsigned short* gh = static_cast<const unsigned short*>(g);
-#define CREID_COUNT_H16_LAUNCH(DT)                                                                                          \
-  return stream_count_launch<sqdist_stream_h16_kernel<DT, EPI_COUNT>>(                                                       \
-      sp, (int)cap, stream, qh, gh, qq, gg, (int)m, (int)n, (int)D, q_pids, g_pids, (int)cap, log2cap, pos_key, pos_idx, npos, hist, \
-      sp.tiles_m, sp.U, sp.upw, sp.mode, (const float*)nullptr, (unsigned long long*)nullptr, (int32_t*)nullptr, 0,               \
-      (const int64_t*)nullptr, (const int64_t*)nullptr, 0)
-  if (dtype == CREID_BF16) CREID_COUNT_H16_LAUNCH(CREID_BF16); else CREID_COUNT_H16_LAUNCH(CREID_F16);
-#undef CREID_COUNT_H16_LAUNCH
+  return stream_h16_launch<EPI_COUNT>({q, g, qq, gg, m, n, D}, dtype, {q_pids, g_pids}, {cap, pos_key, pos_idx, npos, hist}, {}, {},
+                                      stream);
 }
 
 int creid_stream_topk_collect_h16(const void* q, const void* g, const float* qq, const float* gg, int64_t m, int64_t n,
                                   int64_t D, int dtype, const float* tau, int32_t cap, uint64_t* cand, int32_t* count,
                                   void* stream) {
-  CREID_CHECK_ARG(m >= 0 && n > 0 && D > 0);
-  if (!stream_topk_cap_ok(cap) || D % 8 != 0 || D > H_MAX_D) return CREID_E_SHAPE;
-  if (!stream_mn_ok(m, n)) return CREID_E_SHAPE;
-  if (!creid_is16(dtype)) return CREID_E_DTYPE;
-  if (m == 0) return 0;
-  CREID_CHECK_ARG(q && g && qq && gg && tau && cand && count);
-  const StreamSplit sp = stream_split(m, n, D, 2);
-  const unsigned short* qh = static_cast<const unsigned short*>(q);
-  const unsigned short* gh = static_cast<const unsigned short*>(g);
-#define CREID_TOPK_H16_LAUNCH(DT)                                                                                           \
-  hipLaunchKernelGGL((sqdist_stream_h16_kernel<DT, EPI_TOPK>), dim3(sp.grid), dim3(256), 0, as_stream(stream), qh, gh, qq,   \
-                     gg, (int)m, (int)n, (int)D, (const int64_t*)nullptr, (const int64_t*)nullptr, (int)cap, 0,              \
-                     (const unsigned*)nullptr, (const int32_t*)nullptr, (const int32_t*)nullptr, (unsigned*)nullptr,         \
-                     sp.tiles_m, sp.U, sp.upw, sp.mode, tau, reinterpret_cast<unsigned long long*>(cand), count, 0,          \
-                     (const int64_t*)nullptr, (const int64_t*)nullptr, 0)
-  if (dtype == CREID_BF16) CREID_TOPK_H16_LAUNCH(CREID_BF16); else CREID_TOPK_H16_LAUNCH(CREID_F16);
-#undef CREID_TOPK_H16_LAUNCH
-  CREID_LAUNCH_RET();
+  return stream_h16_launch<EPI_TOPK>({q, g, qq, gg, m, n, D}, dtype, {}, {},
+                                     {tau, reinterpret_cast<unsigned long long*>(cand), count, cap}, {}, stream);
 }
 
 int creid_stream_topk_collect_keep_h16(const void* q, const void* g, const float* qq, const float* gg, int64_t m, int64_t n,
                                        int64_t D, int dtype, const float* tau, const int64_t* q_pids, const int64_t* g_pids,
                                        const int64_t* q_cams, const int64_t* g_cams, int32_t camsets, int32_t cap,
                                        uint64_t* cand, int32_t* count, void* stream) {
-  CREID_CHECK_ARG(m >= 0 && n > 0 && D > 0);
-  if (!stream_topk_cap_ok(cap) || D % 8 != 0 || D > H_MAX_D) return CREID_E_SHAPE;
-  if (!stream_mn_ok(m, n)) return CREID_E_SHAPE;
-  if (!creid_is16(dtype)) return CREID_E_DTYPE;
-  if (m == 0) return 0;
-  CREID_CHECK_ARG(q && g && qq && gg && tau && q_pids && g_pids && q_cams && g_cams && cand && count);
-  const StreamSplit sp = stream_split(m, n, D, 2);
-  const unsigned short* qh = static_cast<const unsigned short*>(q);
-  const unsigned short* gh = static_cast<const unsigned short*>(g);
-#define CREID_TOPK_KEEP_H16_LAUNCH(DT)                                                                                      \
-  hipLaunchKernelGGL((sqdist_stream_h16_kernel<DT, EPI_TOPK_KEEP>), dim3(sp.grid), dim3(256), 0, as_stream(stream), qh, gh,  \
-                     qq, gg, (int)m, (int)n, (int)D, q_pids, g_pids, (int)cap, 0,                                            \
-                     (const unsigned*)nullptr, (const int32_t*)nullptr, (const int32_t*)nullptr, (unsigned*)nullptr,         \
-                     sp.tiles_m, sp.U, sp.upw, sp.mode, tau, reinterpret_cast<unsigned long long*>(cand), count, 0,          \
-                     q_cams, g_cams, camsets != 0 ? 1 : 0)
-  if (dtype == CREID_BF16) CREID_TOPK_KEEP_H16_LAUNCH(CREID_BF16); else CREID_TOPK_KEEP_H16_LAUNCH(CREID_F16);
-#undef CREID_TOPK_KEEP_H16_LAUNCH
-  CREID_LAUNCH_RET();
+  return stream_h16_launch<EPI_TOPK_KEEP>({q, g, qq, gg, m, n, D}, dtype, {q_pids, g_pids}, {},
+                                          {tau, reinterpret_cast<unsigned long long*>(cand), count, cap},
+                                          {q_cams, g_cams, camsets != 0 ? 1 : 0}, stream);
 }
 
 int creid_stream_count_band_h16(const void* q, const void* g, const float* qq, const float* gg, int64_t m, int64_t n, int64_t D,
                                 int dtype, const int64_t* q_pids, const int64_t* g_pids, int32_t cap, const uint32_t* pos_key,
                                 const int32_t* pos_idx, const int32_t* npos, const float* margin, int32_t amb_cap, uint32_t* amb,
                                 int32_t* amb_count, uint32_t* hist, void* stream) {
-  CREID_CHECK_ARG(m >= 0 && n > 0 && D > 0);
-  if (m == 0) return 0;
-  CREID_CHECK_ARG(q && g && qq && gg && q_pids && g_pids && pos_key && pos_idx && npos && margin && amb && amb_count && hist);
-  if (!stream_count_cap_ok(cap) || !stream_topk_cap_ok(amb_cap) || D % 8 != 0 || D > H_MAX_D) return CREID_E_SHAPE;
-  if (!stream_mn_ok(m, n)) return CREID_E_SHAPE;
-  if (!creid_is16(dtype)) return CREID_E_DTYPE;
-  const int log2cap = stream_log2cap(cap);
-  const StreamSplit sp = stream_split(m, n, D, 2);
-  const unsigned short* qh = static_cast<const unsigned short*>(q);
-  const unsigned short* gh = static_cast<const unsigned short*>(g);
-#define CREID_BAND_H16_LAUNCH(DT)                                                                                           \
-  return stream_count_launch<sqdist_stream_h16_kernel<DT, EPI_BAND>, SQ_TM>(                                                 \
-      sp, (int)cap, stream, qh, gh, qq, gg, (int)m, (int)n, (int)D, q_pids, g_pids, (int)cap, log2cap, pos_key, pos_idx, npos, hist, \
-      sp.tiles_m, sp.U, sp.upw, sp.mode, margin, reinterpret_cast<unsigned long long*>(amb), amb_count, (int)amb_cap,             \
-      (const int64_t*)nullptr, (const int64_t*)nullptr, 0)
-  if (dtype == CREID_BF16) CREID_BAND_H16_LAUNCH(CREID_BF16); else CREID_BAND_H16_LAUNCH(CREID_F16);
-#undef CREID_BAND_H16_LAUNCH
+  return stream_h16_launch<EPI_BAND>({q, g, qq, gg, m, n, D}, dtype, {q_pids, g_pids}, {cap, pos_key, pos_idx, npos, hist},
+                                     {margin, reinterpret_cast<unsigned long long*>(amb), amb_count, amb_cap}, {}, stream);
 }
 
 }  // extern "C"

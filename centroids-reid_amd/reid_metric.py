@@ -9,6 +9,7 @@ device; only the final few scalars come back to the host.
 from __future__ import annotations
 
 import os
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -93,6 +94,33 @@ def rank_rows(distmat: torch.Tensor) -> torch.Tensor:
     return out
 
 
+class _PerQuery(NamedTuple):
+    """The per-query results of every evaluation route, on the device: valid u8 [m] (2: the query's positive list overflowed),
+    ap f64 [m], first i32 [m] (rank of the first match)."""
+    valid: torch.Tensor
+    ap: torch.Tensor
+    first: torch.Tensor
+
+    @classmethod
+    def empty(cls, m, device):
+        return cls(torch.empty(m, dtype=torch.uint8, device=device), torch.empty(m, dtype=torch.float64, device=device),
+                   torch.empty(m, dtype=torch.int32, device=device))
+
+    @classmethod
+    def finalize(cls, npos, hist, cap):
+        """creid_stream_finalize: the histogram prefix of a streamed count (npos i32 [m], hist i32 [m, cap]) -> results."""
+        m = npos.shape[0]
+        out = cls.empty(m, npos.device)
+        L.check(L.lib().creid_stream_finalize(L.ptr(npos), L.ptr(hist), m, cap, L.ptr(out.valid), L.ptr(out.ap), L.ptr(out.first),
+                                              L.stream()), "creid_stream_finalize")
+        return out
+
+    def merge(self, rows, other):
+        """The results `other` of the queries `rows` (an index tensor) take the place of these rows' own."""
+        for mine, theirs in zip(self, other):
+            mine.index_copy_(0, rows, theirs)
+
+
 def rank_rows_eval(distmat: torch.Tensor, q_pids, g_pids, q_camids, g_camids):
     """rank_rows + the per-query half of eval_func (plain camera ids) in one pass over the distance matrix
     (creid_rank_rows_eval): returns (indices int64 [m, n], valid u8 [m], ap f64 [m], first i32 [m]) -- the index matrix is
@@ -103,14 +131,13 @@ def rank_rows_eval(distmat: torch.Tensor, q_pids, g_pids, q_camids, g_camids):
     dev = distmat.device
     qp, gp, qc, gc = (_dev_i64(a, dev) for a in (q_pids, g_pids, q_camids, g_camids))
     out = torch.empty((m, n), dtype=torch.int64, device=dev)
-    valid = torch.empty(m, dtype=torch.uint8, device=dev)
-    ap = torch.empty(m, dtype=torch.float64, device=dev)
-    first = torch.empty(m, dtype=torch.int32, device=dev)
+    res = _PerQuery.empty(m, dev)
     nbytes = L.lib().creid_rank_rows_workspace_bytes(m, n)
     ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
     L.check(L.lib().creid_rank_rows_eval(L.ptr(distmat), m, n, n, L.ptr(out), L.ptr(ws), nbytes, L.ptr(qp), L.ptr(gp), L.ptr(qc),
-                                         L.ptr(gc), L.ptr(valid), L.ptr(ap), L.ptr(first), L.stream()), "creid_rank_rows_eval")
-    return out, valid, ap, first
+                                         L.ptr(gc), L.ptr(res.valid), L.ptr(res.ap), L.ptr(res.first), L.stream()),
+            "creid_rank_rows_eval")
+    return (out, *res)
 
 
 def topk_rows(distmat: torch.Tensor, k: int):
@@ -202,83 +229,90 @@ def topk_stream(q: torch.Tensor, g: torch.Tensor, k: int, qq=None, gg=None, *, s
     qq = row_sqnorm(q) if qq is None else qq
     gg = row_sqnorm(g) if gg is None else gg
     q, g = _pad_width(q, 8 if h16 else 4), _pad_width(g, 8 if h16 else 4)
-    D, dev, lib, st = q.shape[1], q.device, L.lib(), L.stream()
-    dt = L.dtype_code(q)
-    stride = n // S
-    gs, ggs = g[::stride][:S].contiguous(), gg[::stride][:S].contiguous()
-    if junk is not None:
-        js = junk.gallery_slice(stride, S)
-        camsets = 1 if junk.camsets else 0
-    idx = torch.empty((m, k), dtype=torch.int64, device=dev)
-    dsel = torch.empty((m, k), dtype=torch.float32, device=dev)
-    flags = torch.zeros(m, dtype=torch.uint8, device=dev)
-    count = torch.zeros(m, dtype=torch.int32, device=dev)
-    step = max(64, _STREAM_TOPK_CHUNK_BYTES // (max(cap * 8, S * 4)) // 64 * 64)
+    gs, ggs, js = _topk_sample(g, gg, S, junk)
+    idx, dsel, flags, count = _topk_outputs(m, k, q.device)
+    step = _topk_chunk_rows(cap, S)
     for r0 in range(0, m, step):
         r1 = min(m, r0 + step)
         qc, qqc = q[r0:r1], qq[r0:r1]
+        jc = None if junk is None else junk.rows(slice(r0, r1))
         ds = get_euclidean(qc, gs, qqc, ggs)
         if junk is not None:
             # the k-th smallest over the sample's NON-junk columns: an upper bound of the k-th smallest non-junk distance
-            L.check(lib.creid_junk_mask_rows(L.ptr(ds), r1 - r0, S, S, L.ptr(junk.q_pids[r0:r1]), L.ptr(js.g_pids),
-                                             L.ptr(junk.q_cams[r0:r1]), L.ptr(js.g_cams), camsets, st), "creid_junk_mask_rows")
+            L.check(L.lib().creid_junk_mask_rows(L.ptr(ds), r1 - r0, S, S, L.ptr(jc.q_pids), L.ptr(js.g_pids), L.ptr(jc.q_cams),
+                                                 L.ptr(js.g_cams), 1 if junk.camsets else 0, L.stream()), "creid_junk_mask_rows")
         tau = topk_rows(ds, k)[1][:, k - 1].contiguous()
         del ds
-        cand = torch.empty((r1 - r0, cap), dtype=torch.int64, device=dev)
-        if junk is not None and h16:
-            L.check(lib.creid_stream_topk_collect_keep_h16(
-                L.ptr(qc), L.ptr(g), L.ptr(qqc), L.ptr(gg), r1 - r0, n, D, dt, L.ptr(tau), L.ptr(junk.q_pids[r0:r1]),
-                L.ptr(junk.g_pids), L.ptr(junk.q_cams[r0:r1]), L.ptr(junk.g_cams), camsets, cap, L.ptr(cand), L.ptr(count[r0:r1]),
-                st), "creid_stream_topk_collect_keep_h16")
-        elif junk is not None:
-            L.check(lib.creid_stream_topk_collect_keep(
-                L.ptr(qc), L.ptr(g), L.ptr(qqc), L.ptr(gg), r1 - r0, n, D, L.ptr(tau), L.ptr(junk.q_pids[r0:r1]),
-                L.ptr(junk.g_pids), L.ptr(junk.q_cams[r0:r1]), L.ptr(junk.g_cams), camsets, cap, L.ptr(cand), L.ptr(count[r0:r1]),
-                st), "creid_stream_topk_collect_keep")
-        elif h16:
-            L.check(lib.creid_stream_topk_collect_h16(L.ptr(qc), L.ptr(g), L.ptr(qqc), L.ptr(gg), r1 - r0, n, D, dt, L.ptr(tau),
-                                                      cap, L.ptr(cand), L.ptr(count[r0:r1]), st), "creid_stream_topk_collect_h16")
-        else:
-            L.check(lib.creid_stream_topk_collect(L.ptr(qc), L.ptr(g), L.ptr(qqc), L.ptr(gg), r1 - r0, n, D, L.ptr(tau), cap,
-                                                  L.ptr(cand), L.ptr(count[r0:r1]), st), "creid_stream_topk_collect")
-        L.check(lib.creid_stream_topk_select(L.ptr(cand), L.ptr(count[r0:r1]), r1 - r0, cap, k, L.ptr(idx[r0:r1]),
-                                             L.ptr(dsel[r0:r1]), L.ptr(flags[r0:r1]), st), "creid_stream_topk_select")
+        cand = torch.empty((r1 - r0, cap), dtype=torch.int64, device=q.device)
+        _topk_collect(qc, g, qqc, gg, tau, cap, cand, count[r0:r1], jc)
+        L.check(L.lib().creid_stream_topk_select(L.ptr(cand), L.ptr(count[r0:r1]), r1 - r0, cap, k, L.ptr(idx[r0:r1]),
+                                                 L.ptr(dsel[r0:r1]), L.ptr(flags[r0:r1]), L.stream()), "creid_stream_topk_select")
         del tau, cand
-    if junk is not None:
-        bad = _topk_stream_repair_keep(q, g, k, qq, gg, flags, idx, dsel, junk)
-    else:
-        bad = _topk_stream_repair(q, g, k, qq, gg, flags, idx, dsel)
+    bad = _topk_stream_repair(q, g, k, qq, gg, flags, idx, dsel, junk)
     if stats is not None:
-        stats.update(sample=S, capacity=cap, fallback_rows=bad, max_candidates=int(count.max().item()) if m else 0)
+        stats.update(_topk_stats(S, cap, bad, count))
     return idx, dsel
 
 
-def _topk_stream_repair(q, g, k, qq, gg, flags, idx, dsel) -> int:
-    """The flagged rows of topk_stream (overflowed lists, NaN rows; with a pre-filter also rows that keep too many entries) redone
-    through the materialised kernels in bounded row chunks, into idx / dsel; returns their number."""
+# The pieces the plain and the pre-filtered driver of topk_stream share.
+def _topk_outputs(m, k, device):
+    """idx int64 [m, k], dsel fp32 [m, k], and -- zeroed -- flags u8 [m] (rows to repair), count i32 [m] (entries listed)."""
+    return (torch.empty((m, k), dtype=torch.int64, device=device), torch.empty((m, k), dtype=torch.float32, device=device),
+            torch.zeros(m, dtype=torch.uint8, device=device), torch.zeros(m, dtype=torch.int32, device=device))
+
+
+def _topk_chunk_rows(cap, S):
+    """Query rows per chunk: the candidate lists (cap x 8 bytes a row) and the sample slice (S x 4) inside
+    _STREAM_TOPK_CHUNK_BYTES, in whole query tiles of 64 rows and at least one."""
+    return max(64, _STREAM_TOPK_CHUNK_BYTES // (max(cap * 8, S * 4)) // 64 * 64)
+
+
+def _topk_sample(g, gg, S, junk=None):
+    """The threshold sample: gallery rows 0, stride, 2 stride, ... (S of them), their norms, and junk's filter against them."""
+    stride = g.shape[0] // S
+    return g[::stride][:S].contiguous(), gg[::stride][:S].contiguous(), None if junk is None else junk.gallery_slice(stride, S)
+
+
+def _topk_collect(q, g, qq, gg, thr, cap, cand, count, junk=None):
+    """creid_stream_topk_collect[_keep][_h16], by the operands' dtype and the filter: every (distance <= thr[row], column) --
+    with junk (the filter of THESE query rows): that is not junk -- into the row's list cand [rows, cap]; count += entries."""
+    h16 = q.dtype in _H16
+    name = "creid_stream_topk_collect" + ("_keep" if junk is not None else "") + ("_h16" if h16 else "")
+    dt = (L.dtype_code(q),) if h16 else ()
+    keep = () if junk is None else (L.ptr(junk.q_pids), L.ptr(junk.g_pids), L.ptr(junk.q_cams), L.ptr(junk.g_cams),
+                                    1 if junk.camsets else 0)
+    L.check(getattr(L.lib(), name)(L.ptr(q), L.ptr(g), L.ptr(qq), L.ptr(gg), q.shape[0], g.shape[0], q.shape[1], *dt, L.ptr(thr),
+                                   *keep, cap, L.ptr(cand), L.ptr(count), L.stream()), name)
+
+
+def _topk_stats(S, cap, bad, count):
+    return dict(sample=S, capacity=cap, fallback_rows=bad, max_candidates=int(count.max().item()) if count.numel() else 0)
+
+
+def _topk_stream_repair(q, g, k, qq, gg, flags, idx, dsel, junk=None) -> int:
+    """The flagged rows of topk_stream (overflowed lists, NaN rows; with a pre-filter also rows that keep too many entries; with
+    junk also rows with fewer than k non-junk entries) redone through the materialised kernels in bounded row chunks, into
+    idx / dsel; returns their number.  Plain: get_euclidean + topk_rows; junk: get_euclidean + rank_rows + rank_keep_topk, the
+    distances gathered (+inf in the padding)."""
     bad = torch.nonzero(flags).flatten()
-    rows = max(1, _STREAM_TOPK_CHUNK_BYTES // (g.shape[0] * 4))
+    # per gallery entry a row holds its distance -- with junk also its ranked index and the rank's share
+    rows = max(1, _STREAM_TOPK_CHUNK_BYTES // (g.shape[0] * (4 if junk is None else 16)))
     for b0 in range(0, bad.numel(), rows):
         sel = bad[b0:b0 + rows]
-        ridx, rd = topk_rows(get_euclidean(q.index_select(0, sel), g, qq.index_select(0, sel), gg), k)
+        d = get_euclidean(q.index_select(0, sel), g, qq.index_select(0, sel), gg)
+        if junk is None:
+            ridx, rd = topk_rows(d, k)
+        else:
+            ridx = rank_keep_topk(rank_rows(d), k, junk.rows(sel))[0]
+            rd = gather_ranked(d, ridx)
         idx.index_copy_(0, sel, ridx)
         dsel.index_copy_(0, sel, rd)
+        del d, ridx, rd
     return int(bad.numel())
 
 
 def _topk_stream_repair_keep(q, g, k, qq, gg, flags, idx, dsel, junk) -> int:
-    """_topk_stream_repair for topk_stream(junk=...): the flagged rows (overflowed lists, rows with fewer than k non-junk
-    entries, NaN rows) through get_euclidean + rank_rows + rank_keep_topk, the distances gathered (+inf in the padding)."""
-    bad = torch.nonzero(flags).flatten()
-    rows = max(1, _STREAM_TOPK_CHUNK_BYTES // (g.shape[0] * 16))          # distances, ranked indices and the rank's share
-    for b0 in range(0, bad.numel(), rows):
-        sel = bad[b0:b0 + rows]
-        d = get_euclidean(q.index_select(0, sel), g, qq.index_select(0, sel), gg)
-        ridx = rank_keep_topk(rank_rows(d), k, junk.rows(sel))[0]
-        idx.index_copy_(0, sel, ridx)
-        dsel.index_copy_(0, sel, gather_ranked(d, ridx))
-        del d, ridx
-    return int(bad.numel())
+    return _topk_stream_repair(q, g, k, qq, gg, flags, idx, dsel, junk)
 
 
 class JunkFilter:
@@ -476,19 +510,14 @@ def _topk_stream_prefilter(q, g, k, qq, gg, dtype, g_pack, S, cap, stats):
         return out
     q, g = _pad_width(q, 8), _pad_width(g, 8)       # zero columns change neither a norm, a rounding nor an fmaf chain
     gh = g_pack.rounded
-    D, dev, lib, st = q.shape[1], q.device, L.lib(), L.stream()
-    dt = L._DT[dtype]
+    D, dev = q.shape[1], q.device
     clock.mark("pack_g")
-    stride = n // S
-    ghs, ggs = gh[::stride][:S].contiguous(), gg[::stride][:S].contiguous()
-    idx = torch.empty((m, k), dtype=torch.int64, device=dev)
-    dsel = torch.empty((m, k), dtype=torch.float32, device=dev)
-    flags = torch.zeros(m, dtype=torch.uint8, device=dev)
-    count = torch.zeros(m, dtype=torch.int32, device=dev)
+    ghs, ggs, _ = _topk_sample(gh, gg, S)
+    idx, dsel, flags, count = _topk_outputs(m, k, dev)
     kept = torch.zeros(m, dtype=torch.int32, device=dev)
     margin = torch.empty(m, dtype=torch.float64, device=dev)
     up = torch.tensor(float("inf"), dtype=torch.float32, device=dev)
-    step = max(64, _STREAM_TOPK_CHUNK_BYTES // (max(cap * 8, S * 4)) // 64 * 64)
+    step = _topk_chunk_rows(cap, S)
     for r0 in range(0, m, step):
         r1 = min(m, r0 + step)
         qc, qqc = q[r0:r1], qq[r0:r1]
@@ -502,24 +531,19 @@ def _topk_stream_prefilter(q, g, k, qq, gg, dtype, g_pack, S, cap, stats):
         thr = torch.nextafter(tau + margin2, up.expand_as(tau)).contiguous()
         cand = torch.empty((r1 - r0, cap), dtype=torch.int64, device=dev)
         clock.mark("sample")
-        L.check(lib.creid_stream_topk_collect_h16(L.ptr(qp.rounded), L.ptr(gh), L.ptr(qqc), L.ptr(gg), r1 - r0, n, D, dt, L.ptr(thr),
-                                                  cap, L.ptr(cand), L.ptr(count[r0:r1]), st), "creid_stream_topk_collect_h16")
+        _topk_collect(qp.rounded, gh, qqc, gg, thr, cap, cand, count[r0:r1])
         clock.mark("collect")
-        L.check(lib.creid_stream_topk_rescore(L.ptr(cand), L.ptr(count[r0:r1]), r1 - r0, cap, k, L.ptr(qc), L.ptr(g), L.ptr(qqc),
-                                              L.ptr(gg), n, D, L.ptr(margin2), L.ptr(idx[r0:r1]), L.ptr(dsel[r0:r1]),
-                                              L.ptr(flags[r0:r1]), L.ptr(kept[r0:r1]), st), "creid_stream_topk_rescore")
+        L.check(L.lib().creid_stream_topk_rescore(L.ptr(cand), L.ptr(count[r0:r1]), r1 - r0, cap, k, L.ptr(qc), L.ptr(g), L.ptr(qqc),
+                                                  L.ptr(gg), n, D, L.ptr(margin2), L.ptr(idx[r0:r1]), L.ptr(dsel[r0:r1]),
+                                                  L.ptr(flags[r0:r1]), L.ptr(kept[r0:r1]), L.stream()), "creid_stream_topk_rescore")
         clock.mark("rescore")
         del qp, tau, thr, cand, margin2
     bad = _topk_stream_repair(q, g, k, qq, gg, flags, idx, dsel)      # the fp32 path's repair, on the fp32 tensors
     clock.mark("repair")
     if stats is not None:
         if clock.on:                                        # per stage, summed over the row chunks
-            stage_ms = {}
-            clock.marks[-1][1].synchronize()
-            for (_, prev), (name, ev) in zip(clock.marks, clock.marks[1:]):
-                stage_ms[name] = stage_ms.get(name, 0.0) + prev.elapsed_time(ev)
-            stats["stage_ms"] = stage_ms
-        stats.update(sample=S, capacity=cap, fallback_rows=bad, max_candidates=int(count.max().item()) if m else 0,
+            stats["stage_ms"] = clock.stage_ms()
+        stats.update(_topk_stats(S, cap, bad, count),
                      prefilter=dtype, max_rescored=int(kept.max().item()) if m else 0, rescore_capacity=STREAM_RESCORE_CAPACITY,
                      margin_max=float(margin.max().item()) if m else 0.0, kept=kept)
     return idx, dsel
@@ -569,8 +593,13 @@ class _StageClock:
             self.marks.append((name, ev))
 
     def stage_ms(self):
+        """Milliseconds per stage name; marks that share a name (row chunks, both normalisations of an expansion round, a
+        redone speculation) are summed."""
         self.marks[-1][1].synchronize()
-        return {name: prev.elapsed_time(ev) for (_, prev), (name, ev) in zip(self.marks, self.marks[1:])}
+        ms = {}
+        for (_, prev), (name, ev) in zip(self.marks, self.marks[1:]):
+            ms[name] = ms.get(name, 0.0) + prev.elapsed_time(ev)
+        return ms
 
 
 def re_ranking(q: torch.Tensor, g: torch.Tensor, k1: int = 20, k2: int = 6, lambda_value: float = 0.3, *, stats=None,
@@ -823,11 +852,7 @@ def _expanded_rows(X, nq, k, alpha, rounds, scope, prefilter, out_dtype, stats):
         info.pop("kept", None)                              # (a device tensor of the pre-filtered search; the counters stay)
         per_round.append(info)
         if timing:
-            clock.marks[-1][1].synchronize()
-            ms = {}
-            for (_, prev), (name, ev) in zip(clock.marks, clock.marks[1:]):         # both normalisations under one name
-                ms[name] = ms.get(name, 0.0) + prev.elapsed_time(ev)
-            stage_ms.append(ms)
+            stage_ms.append(clock.stage_ms())                   # both normalisations under one name
     if stats is not None:
         stats.update(per_round[-1], rounds_stats=per_round)
         if timing:
@@ -949,23 +974,32 @@ def eval_func_device(indices: torch.Tensor, q_pids, g_pids, q_camids, g_camids, 
     if camsets and isinstance(g_camids, (torch.Tensor, np.ndarray)):
         q_camids = _check_query_cams(np.asarray(q_camids, np.int64))
     elif camsets:
-        g_camids = _camset_masks(g_camids)
-        q_camids = _check_query_cams(np.asarray([int(np.atleast_1d(c)[0]) for c in q_camids], np.int64))
+        q_camids, g_camids = _camset_split(list(q_camids) + list(g_camids), m)
     qp, gp, qc, gc = (_dev_i64(a, dev) for a in (q_pids, g_pids, q_camids, g_camids))
-    valid = torch.empty(m, dtype=torch.uint8, device=dev)
-    ap = torch.empty(m, dtype=torch.float64, device=dev)
-    first = torch.empty(m, dtype=torch.int32, device=dev)
+    res = _PerQuery.empty(m, dev)
     lib = L.lib()
     fn = lib.creid_cmc_ap_ranked_camsets if camsets else lib.creid_cmc_ap_ranked
-    L.check(fn(L.ptr(indices), m, n, L.ptr(qp), L.ptr(gp), L.ptr(qc), L.ptr(gc), L.ptr(valid), L.ptr(ap), L.ptr(first),
+    L.check(fn(L.ptr(indices), m, n, L.ptr(qp), L.ptr(gp), L.ptr(qc), L.ptr(gc), L.ptr(res.valid), L.ptr(res.ap), L.ptr(res.first),
                L.stream()), "creid_cmc_ap_ranked")
-    cmc = torch.empty(max_rank, dtype=torch.float32, device=dev)
-    mAP = torch.empty(1, dtype=torch.float64, device=dev)
-    topk = torch.empty(5, dtype=torch.float64, device=dev)
-    nvalid = torch.empty(1, dtype=torch.int64, device=dev)
-    L.check(lib.creid_eval_reduce(L.ptr(valid), L.ptr(ap), L.ptr(first), m, max_rank, L.ptr(cmc), L.ptr(mAP),
-                                  L.ptr(topk), L.ptr(nvalid), L.stream()), "creid_eval_reduce")
-    return cmc, mAP, topk, nvalid, valid, ap, first
+    return (*eval_reduce_device(*res, max_rank), *res)
+
+
+def _pack_results(cmc, mAP, topk, valid, ap, tail=()):
+    """Everything the host needs of an evaluation as ONE float64 device tensor, so that one read-back (one synchronisation
+    instead of five) fetches it: [cmc (max_rank) | mAP | topk (5) | valid (m) | ap (m) | tail], exact for the f32 / u8 members.
+    tail: float64 device tensors that ride along."""
+    return torch.cat([cmc.double(), mAP, topk, valid.double(), ap, *tail])
+
+
+def _unpack_results(pack, max_rank, q_pids):
+    """The read-back of _pack_results (q_pids: the m queries' pids, a numpy vector) -> (cmc f32 [max_rank], mAP float,
+    topk f64 [5], valid bool [m], ap f64 [m], tail f64, single_performance f64 [n_valid, 3] = rows [q_idx, q_pid, AP])."""
+    pack = pack.cpu().numpy()
+    m, o = len(q_pids), max_rank + 6
+    valid, ap = pack[o:o + m] == 1, pack[o + m:o + 2 * m]
+    vi = np.nonzero(valid)[0]
+    single = np.stack([vi.astype(np.float64), q_pids[vi].astype(np.float64), ap[vi]], axis=1)
+    return pack[:max_rank].astype(np.float32), float(pack[max_rank]), pack[max_rank + 1:o].copy(), valid, ap, pack[o + 2 * m:], single
 
 
 def eval_func(indices, q_pids, g_pids, q_camids, g_camids, max_rank=50, respect_camids=False):
@@ -975,11 +1009,9 @@ def eval_func(indices, q_pids, g_pids, q_camids, g_camids, max_rank=50, respect_
         raise L.CreidError("eval_func needs a device tensor of ranked indices (no CPU fallback)")
     cmc, mAP, topk, nvalid, valid, ap, first = eval_func_device(indices, q_pids, g_pids, q_camids, g_camids, max_rank,
                                                                 camsets=bool(respect_camids))
-    valid_h = valid.cpu().numpy().astype(bool)
-    vi = np.nonzero(valid_h)[0]
     qp = np.asarray(q_pids.cpu() if isinstance(q_pids, torch.Tensor) else q_pids)
-    single = np.stack([vi.astype(np.float64), qp[vi].astype(np.float64), ap.cpu().numpy()[vi]], axis=1)
-    return cmc.cpu().numpy(), float(mAP.item()), topk.cpu().numpy(), single
+    cmc, mAP, topk, _, _, _, single = _unpack_results(_pack_results(cmc, mAP, topk, valid, ap), cmc.shape[0], qp)
+    return cmc, mAP, topk, single
 
 
 # --------------------------------------------------------------------------- streamed (metric-only) evaluation
@@ -1152,60 +1184,69 @@ class StreamPlan:
         self.q_pids, self.g_pids, self.q_cams, self.g_cams = t(qp, np.int64), t(gp, np.int64), t(qc, np.int64), t(gc, np.int64)
 
 
+class _PosLists(NamedTuple):
+    """The positives of every query as the streamed count reads them: key / idx i32 [m, cap] (distance keys ascending and the
+    gallery entries behind them), npos i32 [m] (negative: more positives than `cap`), and the histogram hist i32 [m, cap] the
+    count bumps."""
+    cap: int
+    key: torch.Tensor
+    idx: torch.Tensor
+    npos: torch.Tensor
+    hist: torch.Tensor
+
+    def rows(self, sel):
+        """The lists of the queries `sel` (an index tensor), gathered, with a fresh histogram."""
+        return _PosLists(self.cap, self.key.index_select(0, sel), self.idx.index_select(0, sel), self.npos.index_select(0, sel),
+                         torch.zeros((sel.shape[0], self.cap), dtype=torch.int32, device=sel.device))
+
+
+def _stream_poslist(fq, fg, qq, gg, plan: StreamPlan) -> _PosLists:
+    """creid_stream_poslist[_h16][_camsets], by the rows' dtype and plan.camsets (camera sets only change which same-pid
+    entries are positives: another poslist, the same count and finalize): the positives' distances of every query, and a
+    zeroed histogram."""
+    m, n, D, cap, dev = fq.shape[0], fg.shape[0], fq.shape[1], plan.cap, fq.device
+    h16 = fq.dtype in _H16
+    pl = _PosLists(cap, torch.empty((m, cap), dtype=torch.int32, device=dev), torch.empty((m, cap), dtype=torch.int32, device=dev),
+                   torch.empty(m, dtype=torch.int32, device=dev), torch.zeros((m, cap), dtype=torch.int32, device=dev))
+    name = "creid_stream_poslist" + ("_h16" if h16 else "")
+    dt = (L.dtype_code(fq),) if h16 else ()
+    L.check(getattr(L.lib(), name + ("_camsets" if plan.camsets else ""))(
+        L.ptr(fq), L.ptr(fg), L.ptr(qq), L.ptr(gg), m, n, D, *dt, L.ptr(plan.q_slot), L.ptr(plan.csr_off), L.ptr(plan.g_order),
+        L.ptr(plan.q_cams), L.ptr(plan.g_cams), cap, L.ptr(pl.key), L.ptr(pl.idx), L.ptr(pl.npos), L.stream()), name)
+    return pl
+
+
+def _stream_count(fq, fg, qq, gg, q_pids, g_pids, pl: _PosLists):
+    """creid_stream_count[_h16]: the streamed contraction with the in-register count epilogue, into pl.hist."""
+    h16 = fq.dtype in _H16
+    name = "creid_stream_count" + ("_h16" if h16 else "")
+    dt = (L.dtype_code(fq),) if h16 else ()
+    L.check(getattr(L.lib(), name)(L.ptr(fq), L.ptr(fg), L.ptr(qq), L.ptr(gg), fq.shape[0], fg.shape[0], fq.shape[1], *dt,
+                                   L.ptr(q_pids), L.ptr(g_pids), pl.cap, L.ptr(pl.key), L.ptr(pl.idx), L.ptr(pl.npos),
+                                   L.ptr(pl.hist), L.stream()), name)
+
+
 def stream_eval(fq, fg, qq, gg, plan: StreamPlan):
-    if plan.cap is None:
-        plan.finish()
-    return _stream_eval(fq, fg, qq, gg, plan)
-
-
-def _stream_eval(fq, fg, qq, gg, plan: StreamPlan):
     """Per-query (valid u8[m], AP f64[m], first-match rank i32[m]) with no m x n matrix: positives' distances ->
     streamed MFMA contraction with an in-register count epilogue -> histogram prefix.  valid == 2 marks a query
     whose positive list overflowed the plan's capacity (see StreamPlan.overflow).  fp32 features run on the f32 MFMA
-    (csrc/stream_eval.hip), bf16 / f16 features (D % 8 == 0) on the 16-bit MFMA (csrc/stream_h16.hip)."""
+    (csrc/stream_eval.hip), bf16 / f16 features (D % 8 == 0) on the 16-bit MFMA (csrc/stream_h16.hip).  A plan that has not
+    read its capacity back yet is finished first (StreamPlan.finish: one synchronisation)."""
+    if plan.cap is None:
+        plan.finish()
     L.require_gpu(fq, fg, qq, gg)
     assert fq.dtype == fg.dtype and fq.dtype in (torch.float32,) + _H16
-    h16 = fq.dtype in _H16
-    m, n, D = fq.shape[0], fg.shape[0], fq.shape[1]
-    assert (m, n) == (plan.m, plan.n)
-    dev, lib, st = fq.device, L.lib(), L.stream()
-    cap = plan.cap
-    pos_key = torch.empty((m, cap), dtype=torch.int32, device=dev)
-    pos_idx = torch.empty((m, cap), dtype=torch.int32, device=dev)
-    npos = torch.empty(m, dtype=torch.int32, device=dev)
-    hist = torch.zeros((m, cap), dtype=torch.int32, device=dev)
-    # camera sets only change which same-pid entries are positives: another poslist, the same count and finalize
-    camsets = plan.camsets
-    if h16:
-        dt = L.dtype_code(fq)
-        poslist = lib.creid_stream_poslist_h16_camsets if camsets else lib.creid_stream_poslist_h16
-        L.check(poslist(L.ptr(fq), L.ptr(fg), L.ptr(qq), L.ptr(gg), m, n, D, dt, L.ptr(plan.q_slot),
-                        L.ptr(plan.csr_off), L.ptr(plan.g_order), L.ptr(plan.q_cams), L.ptr(plan.g_cams),
-                        cap, L.ptr(pos_key), L.ptr(pos_idx), L.ptr(npos), st), "creid_stream_poslist_h16")
-        L.check(lib.creid_stream_count_h16(L.ptr(fq), L.ptr(fg), L.ptr(qq), L.ptr(gg), m, n, D, dt, L.ptr(plan.q_pids),
-                                           L.ptr(plan.g_pids), cap, L.ptr(pos_key), L.ptr(pos_idx), L.ptr(npos), L.ptr(hist),
-                                           st), "creid_stream_count_h16")
-    else:
-        poslist = lib.creid_stream_poslist_camsets if camsets else lib.creid_stream_poslist
-        L.check(poslist(L.ptr(fq), L.ptr(fg), L.ptr(qq), L.ptr(gg), m, n, D, L.ptr(plan.q_slot),
-                        L.ptr(plan.csr_off), L.ptr(plan.g_order), L.ptr(plan.q_cams), L.ptr(plan.g_cams), cap,
-                        L.ptr(pos_key), L.ptr(pos_idx), L.ptr(npos), st), "creid_stream_poslist")
-        L.check(lib.creid_stream_count(L.ptr(fq), L.ptr(fg), L.ptr(qq), L.ptr(gg), m, n, D, L.ptr(plan.q_pids),
-                                       L.ptr(plan.g_pids), cap, L.ptr(pos_key), L.ptr(pos_idx), L.ptr(npos), L.ptr(hist), st),
-                "creid_stream_count")
-    valid = torch.empty(m, dtype=torch.uint8, device=dev)
-    ap = torch.empty(m, dtype=torch.float64, device=dev)
-    first = torch.empty(m, dtype=torch.int32, device=dev)
-    L.check(lib.creid_stream_finalize(L.ptr(npos), L.ptr(hist), m, cap, L.ptr(valid), L.ptr(ap), L.ptr(first), st),
-            "creid_stream_finalize")
-    return valid, ap, first
+    assert (fq.shape[0], fg.shape[0]) == (plan.m, plan.n)
+    pl = _stream_poslist(fq, fg, qq, gg, plan)
+    _stream_count(fq, fg, qq, gg, plan.q_pids, plan.g_pids, pl)
+    return _PerQuery.finalize(pl.npos, pl.hist, pl.cap)
 
 
 EVAL_PREFILTER_CAPACITY = 1024        # ambiguous pairs a query may list (creid_stream_count_band_h16: power of two, 64 .. 8192)
 
 
 def _stream_eval_prefilter(fq, fg, qq, gg, plan: StreamPlan, dtype, acap, clock):
-    """_stream_eval on fp32 features with the counting contraction on the 16-bit MFMA and the fp32 path's histogram, element for
+    """stream_eval on fp32 features with the counting contraction on the 16-bit MFMA and the fp32 path's histogram, element for
     element.  d: the fp32 kernels' distance; dh: the 16-bit streamed kernel's distance on the rows rounded once to `dtype`, given
     the fp32 rows' own qq / gg; m_i = prefilter_margin >= |dh - d| over row i (query statistics against the gallery's maxima, as in
     _topk_stream_prefilter; inflated by 1 + 2^-20 and rounded UP to fp32), so d_ij lies in [dh_ij - m_i, dh_ij + m_i].  The
@@ -1230,56 +1271,34 @@ def _stream_eval_prefilter(fq, fg, qq, gg, plan: StreamPlan, dtype, acap, clock)
     margin = prefilter_margin(qp.stats[:, 0], qp.stats[:, 1], x2, gmax[0], gmax[1], gmax[2], torch.maximum(gmax[2], gmax[3]), D)
     margin32 = _round_up_f32((1.0 + _PREFILTER_INFLATE) * margin)
     clock.mark("pack")
-    pos_key = torch.empty((m, cap), dtype=torch.int32, device=dev)
-    pos_idx = torch.empty((m, cap), dtype=torch.int32, device=dev)
-    npos = torch.empty(m, dtype=torch.int32, device=dev)
-    hist = torch.zeros((m, cap), dtype=torch.int32, device=dev)
     amb = torch.empty((m, acap), dtype=torch.int32, device=dev)
     amb_count = torch.zeros(m, dtype=torch.int32, device=dev)
     flags = torch.zeros(m, dtype=torch.uint8, device=dev)
-    L.check(lib.creid_stream_poslist(L.ptr(fq), L.ptr(fg), L.ptr(qq), L.ptr(gg), m, n, D, L.ptr(plan.q_slot),
-                                     L.ptr(plan.csr_off), L.ptr(plan.g_order), L.ptr(plan.q_cams), L.ptr(plan.g_cams), cap,
-                                     L.ptr(pos_key), L.ptr(pos_idx), L.ptr(npos), st), "creid_stream_poslist")
+    pl = _stream_poslist(fq, fg, qq, gg, plan)
     clock.mark("poslist")
     L.check(lib.creid_stream_count_band_h16(L.ptr(qp.rounded), L.ptr(gp.rounded), L.ptr(qq), L.ptr(gg), m, n, D, dt,
-                                            L.ptr(plan.q_pids), L.ptr(plan.g_pids), cap, L.ptr(pos_key), L.ptr(pos_idx),
-                                            L.ptr(npos), L.ptr(margin32), acap, L.ptr(amb), L.ptr(amb_count), L.ptr(hist), st),
+                                            L.ptr(plan.q_pids), L.ptr(plan.g_pids), cap, L.ptr(pl.key), L.ptr(pl.idx),
+                                            L.ptr(pl.npos), L.ptr(margin32), acap, L.ptr(amb), L.ptr(amb_count), L.ptr(pl.hist), st),
             "creid_stream_count_band_h16")
     clock.mark("count")
     L.check(lib.creid_stream_count_rescore(L.ptr(amb), L.ptr(amb_count), m, acap, L.ptr(fq), L.ptr(fg), L.ptr(qq), L.ptr(gg), n, D,
-                                           cap, L.ptr(pos_key), L.ptr(pos_idx), L.ptr(npos), L.ptr(hist), L.ptr(flags), st),
+                                           cap, L.ptr(pl.key), L.ptr(pl.idx), L.ptr(pl.npos), L.ptr(pl.hist), L.ptr(flags), st),
             "creid_stream_count_rescore")
     # a gallery out of range: every row to the fp32 count, except those that have no list and take the general path
-    flags = torch.where(torch.isfinite(gmax).all(), flags, (npos >= 0).to(torch.uint8))
-    valid = torch.empty(m, dtype=torch.uint8, device=dev)
-    ap = torch.empty(m, dtype=torch.float64, device=dev)
-    first = torch.empty(m, dtype=torch.int32, device=dev)
-    L.check(lib.creid_stream_finalize(L.ptr(npos), L.ptr(hist), m, cap, L.ptr(valid), L.ptr(ap), L.ptr(first), st),
-            "creid_stream_finalize")
+    flags = torch.where(torch.isfinite(gmax).all(), flags, (pl.npos >= 0).to(torch.uint8))
+    res = _PerQuery.finalize(pl.npos, pl.hist, cap)
     clock.mark("rescore")
-    state = dict(flags=flags, ambiguous=amb_count, gmax=gmax, margin_max=margin.max().reshape(1) if m else gmax[:1] * 0,
-                 pos_key=pos_key, pos_idx=pos_idx, npos=npos)
-    return valid, ap, first, state
+    state = dict(flags=flags, ambiguous=amb_count, gmax=gmax, margin_max=margin.max().reshape(1) if m else gmax[:1] * 0, lists=pl)
+    return (*res, state)
 
 
 def _stream_eval_prefilter_repair(fq, fg, qq, gg, plan: StreamPlan, state, rows, valid, ap, first):
     """The rows creid_stream_count_rescore flagged, redone with the fp32 creid_stream_count on the gathered rows (their q, qq,
     q_pids, positive lists and a fresh histogram) and merged into valid / ap / first."""
-    dev, lib, st = fq.device, L.lib(), L.stream()
-    sel = torch.as_tensor(rows, device=dev)
-    r, n, D, cap = len(rows), fg.shape[0], fq.shape[1], plan.cap
-    q, sq, qp = fq.index_select(0, sel), qq.index_select(0, sel), plan.q_pids.index_select(0, sel)
-    pos_key, pos_idx = state["pos_key"].index_select(0, sel), state["pos_idx"].index_select(0, sel)
-    npos = state["npos"].index_select(0, sel)
-    hist = torch.zeros((r, cap), dtype=torch.int32, device=dev)
-    L.check(lib.creid_stream_count(L.ptr(q), L.ptr(fg), L.ptr(sq), L.ptr(gg), r, n, D, L.ptr(qp), L.ptr(plan.g_pids), cap,
-                                   L.ptr(pos_key), L.ptr(pos_idx), L.ptr(npos), L.ptr(hist), st), "creid_stream_count")
-    v2 = torch.empty(r, dtype=torch.uint8, device=dev)
-    a2 = torch.empty(r, dtype=torch.float64, device=dev)
-    f2 = torch.empty(r, dtype=torch.int32, device=dev)
-    L.check(lib.creid_stream_finalize(L.ptr(npos), L.ptr(hist), r, cap, L.ptr(v2), L.ptr(a2), L.ptr(f2), st),
-            "creid_stream_finalize")
-    valid.index_copy_(0, sel, v2); ap.index_copy_(0, sel, a2); first.index_copy_(0, sel, f2)
+    sel = torch.as_tensor(rows, device=fq.device)
+    pl = state["lists"].rows(sel)
+    _stream_count(fq.index_select(0, sel), fg, qq.index_select(0, sel), gg, plan.q_pids.index_select(0, sel), plan.g_pids, pl)
+    _PerQuery(valid, ap, first).merge(sel, _PerQuery.finalize(pl.npos, pl.hist, pl.cap))
 
 
 def eval_reduce_device(valid, ap, first, max_rank):
@@ -1386,6 +1405,18 @@ class R1_mAP:
         self._qe_info = {**o, **info}
         return f, row_sqnorm(f)
 
+    def _rows(self, feats):
+        """The rows one evaluation multiplies and their square norms, the same tensors on every route: euclidean -- normalised
+        (or expanded) into compute_dtype, or cast to it; cosine -- fp32, and no norms (get_cosine normalises again).  Prints
+        what the reference prints, so once per evaluation."""
+        if self.dist_name != "euclidean":
+            return (self._normalised(feats, torch.float32)[0] if self.feat_norm else feats), None
+        if self.feat_norm:
+            print("The test feature is normalized")
+            return self._normalised(feats)
+        f = feats if self.compute_dtype == torch.float32 else feats.to(self.compute_dtype)
+        return f, row_sqnorm(f)
+
     def _keep_expansion_info(self):
         if self._qe_info is not None:
             self.last["query_expansion"] = self._qe_info
@@ -1404,20 +1435,13 @@ class R1_mAP:
         nq = self.num_query
         if self.streamed and self.dist_name == "euclidean" and self.compute_dtype in (torch.float32,) + _H16:
             return self._compute_streamed(feats, pids, camids, camsets=bool(respect_camids))
-        if self.dist_name == "euclidean":
-            if self.feat_norm:
-                print("The test feature is normalized")
-                f, sq = self._normalised(feats)
-            else:
-                f = feats if self.compute_dtype == torch.float32 else feats.to(self.compute_dtype)
-                sq = row_sqnorm(f)
-            if self.reranking is not None:
-                distmat = re_ranking(f[:nq], f[nq:], **self.reranking)
-            else:
-                distmat = get_euclidean(f[:nq], f[nq:], sq[:nq].contiguous(), sq[nq:].contiguous())
-        else:
-            f = self._normalised(feats, torch.float32)[0] if self.feat_norm else feats
+        f, sq = self._rows(feats)
+        if self.dist_name != "euclidean":
             distmat = self.dist_func(f[:nq].contiguous(), f[nq:].contiguous())
+        elif self.reranking is not None:
+            distmat = re_ranking(f[:nq], f[nq:], **self.reranking)
+        else:
+            distmat = get_euclidean(f[:nq], f[nq:], sq[:nq].contiguous(), sq[nq:].contiguous())
         pids = np.asarray(pids)
         if respect_camids:                      # (ragged list-of-lists of camera sets: keep as a list)
             indices = rank_rows(distmat)
@@ -1437,35 +1461,24 @@ class R1_mAP:
             max_rank = distmat.shape[1]
             print("Note: number of gallery samples is quite small, got {}".format(distmat.shape[1]))
         cmc, mAP, topk, _ = eval_reduce_device(valid, ap, first, max_rank)
-        pack = torch.cat([cmc.double(), mAP, topk, valid.double(), ap]).cpu().numpy()          # one read-back
-        valid_h = pack[max_rank + 6:max_rank + 6 + nq] == 1
-        vi = np.nonzero(valid_h)[0]
-        single = np.stack([vi.astype(np.float64), pids[:nq][vi].astype(np.float64), pack[max_rank + 6 + nq:][vi]], axis=1)
+        cmc_h, mAP_h, topk_h, _, _, _, single = _unpack_results(_pack_results(cmc, mAP, topk, valid, ap), max_rank, pids[:nq])
         self.last = dict(distmat=distmat, indices=indices, single_performance=single, valid=valid, ap=ap, first=first)
         if self.ranked_topk is not None:
             self.last["ranked"] = self._ranked_from_indices(indices, distmat, JunkFilter.from_labels(pids, camids, nq, feats.device))
         self._keep_expansion_info()
-        return pack[:max_rank].astype(np.float32), float(pack[max_rank]), pack[max_rank + 1:max_rank + 6].copy()
+        return cmc_h, mAP_h, topk_h
 
-    def _compute_streamed(self, feats, pids, camids, plan=None, _normed=None, _clock=None, camsets=False):
+    def _compute_streamed(self, feats, pids, camids, camsets=False):
         """camsets: `camids` is the respect_camids=True argument (a list of camera-id lists, or a CameraSets); the gallery
         entries' sets become bitmasks and the same three launches run on them (StreamPlan(camsets=True))."""
         nq = self.num_query
-        camids_arg, g_masks = camids, None
+        g_masks = None
         if camsets:
             q_cams, g_masks = _camset_split(camids, nq)           # (raises before anything is launched)
-        if _normed is not None:                 # the redo of a failed speculation: rows already normalised, nothing printed twice
-            f, sq = _normed
-        else:
-            # exactly the rows and norms of the materialised branch of compute(): both paths multiply the same tensors
-            if self.compute_dtype in _H16:
-                feats = _pad_width(feats, 8)
-            if self.feat_norm:
-                print("The test feature is normalized")
-                f, sq = self._normalised(feats)
-            else:
-                f = feats if self.compute_dtype == torch.float32 else feats.to(self.compute_dtype)
-                sq = row_sqnorm(f)
+        # exactly the rows and norms of the materialised branch of compute(): both paths multiply the same tensors
+        if self.compute_dtype in _H16:
+            feats = _pad_width(feats, 8)
+        f, sq = self._rows(feats)
         pids = np.asarray(pids)
         hint_key = (nq, len(pids) - nq) + (("camsets",) if camsets else ())       # (a capacity learnt on sets is no guide for ids)
         plan_kw = {}
@@ -1475,89 +1488,78 @@ class R1_mAP:
             plan_kw = dict(camsets=True, g_cam_masks=g_masks if on_dev else None)
         else:
             camids = np.asarray(camids)
-        speculative = False
-        if plan is None:
-            # index built on the device BEHIND the normalisation launch.  Its 8-byte read-back (finish: the positive-list
-            # capacity) would be a host synchronisation in the middle of the pipeline; an evaluation of the same shape as an
-            # earlier one instead ASSUMES that call's capacity, enqueues everything, and checks the assumption against the
-            # plan's statistics in the final read-back (wrong -> the contraction is redone with the right capacity; a capacity
-            # larger than needed gives identical results)
-            plan = StreamPlan.on_device(pids, camids, nq, feats.device, **plan_kw)
-            hint = _CAP_HINT.get(hint_key) if os.environ.get("CREID_EVAL_SPECULATE", "1") == "1" else None
-            if plan.cap is None and hint:        # 0 = "do not speculate": the last label set of this shape had overflow queries
-                plan.cap, plan.overflow, speculative = hint, np.zeros(0, np.int64), True
+        # index built on the device BEHIND the normalisation launch.  Its 8-byte read-back (finish: the positive-list
+        # capacity) would be a host synchronisation in the middle of the pipeline; an evaluation of the same shape as an
+        # earlier one instead ASSUMES that call's capacity, enqueues everything, and checks the assumption against the
+        # plan's statistics in the final read-back (wrong -> the contraction is redone with the right capacity; a capacity
+        # larger than needed gives identical results)
+        plan = StreamPlan.on_device(pids, camids, nq, feats.device, **plan_kw)
+        hint = _CAP_HINT.get(hint_key) if os.environ.get("CREID_EVAL_SPECULATE", "1") == "1" else None
+        speculative = plan.cap is None and bool(hint)  # 0 = "do not speculate": the last label set of this shape had overflow queries
+        if speculative:
+            plan.cap, plan.overflow = hint, np.zeros(0, np.int64)
         if plan.cap is None:
             plan.finish()
         fq, fg = f[:nq], f[nq:]
         qq, gg = sq[:nq].contiguous(), sq[nq:].contiguous()
-        pf = None
+        pf = clock = None
         if self.prefilter is not None:
             # zero columns behind the normalised rows change neither a norm, a rounding nor an fmaf chain
             fq, fg = _pad_width(fq, 8), _pad_width(fg, 8)
-            clock = _clock or _StageClock(bool((self.last.get("prefilter") or {}).get("timing")))
-            valid, ap, first, pf = _stream_eval_prefilter(fq, fg, qq, gg, plan, self.prefilter, self.prefilter_capacity, clock)
-        else:
-            valid, ap, first = _stream_eval(fq, fg, qq, gg, plan)
-        if len(plan.overflow):
-            # queries with more positives than the LDS list holds: the general path on just those rows
-            rows = torch.as_tensor(plan.overflow, device=feats.device)
-            d = get_euclidean(fq.index_select(0, rows), fg, qq.index_select(0, rows), gg)
-            idx = rank_rows(d)
-            _, _, _, _, v2, a2, f2 = eval_func_device(idx, pids[:nq][plan.overflow], plan.g_pids, camids[:nq][plan.overflow],
-                                                      plan.g_cams, self.max_rank, camsets=camsets)
-            valid.index_copy_(0, rows, v2); ap.index_copy_(0, rows, a2); first.index_copy_(0, rows, f2)
+            clock = _StageClock(bool((self.last.get("prefilter") or {}).get("timing")))
         max_rank = min(self.max_rank, fg.shape[0])
-        cmc, mAP, topk, _ = eval_reduce_device(valid, ap, first, max_rank)
-        # ONE read-back for everything the host needs (five separate .cpu() calls are five synchronisations):
-        # [cmc (max_rank) | mAP | topk (5) | valid (m) | ap (m)] as float64 (exact for the f32 / u8 members)
-        stats = plan._stats.double() if speculative else torch.zeros(2, dtype=torch.float64, device=feats.device)
-        if pf is not None:                       # [flags (m) | gallery maxima (4) | margin max] ride in front of the statistics
-            stats = torch.cat([pf["flags"].double(), pf["gmax"], pf["margin_max"], stats])
-        pack = torch.cat([cmc.double(), mAP, topk, valid.double(), ap, stats]).cpu().numpy()
-        if speculative:
+        for _ in range(2):  # a speculation that fails is redone once, synchronously, on the same rows and the same clock
+            if self.prefilter is not None:
+                valid, ap, first, pf = _stream_eval_prefilter(fq, fg, qq, gg, plan, self.prefilter, self.prefilter_capacity, clock)
+                res = _PerQuery(valid, ap, first)
+            else:
+                res = stream_eval(fq, fg, qq, gg, plan)
+            if len(plan.overflow):
+                # queries with more positives than the LDS list holds: the general path on just those rows
+                rows = torch.as_tensor(plan.overflow, device=feats.device)
+                d = get_euclidean(fq.index_select(0, rows), fg, qq.index_select(0, rows), gg)
+                res.merge(rows, eval_func_device(rank_rows(d), pids[:nq][plan.overflow], plan.g_pids, camids[:nq][plan.overflow],
+                                                 plan.g_cams, self.max_rank, camsets=camsets)[4:])
+            cmc, mAP, topk, _ = eval_reduce_device(*res, max_rank)
+            # riding along: the plan's statistics, and in front of them the pre-filter's [flags (m) | gallery maxima (4) | margin max]
+            tail = [plan._stats.double() if speculative else torch.zeros(2, dtype=torch.float64, device=feats.device)]
+            if pf is not None:
+                tail = [pf["flags"].double(), pf["gmax"], pf["margin_max"]] + tail
+            cmc_h, mAP_h, topk_h, _, _, tail, single = _unpack_results(_pack_results(cmc, mAP, topk, res.valid, res.ap, tail),
+                                                                       max_rank, pids[:nq])
+            if not speculative:
+                if getattr(plan, "_stats", None) is not None:
+                    _CAP_HINT[hint_key] = 0 if len(plan.overflow) else plan.cap
+                break
             need = 2
-            while need < max(int(pack[-2]), 1):
+            while need < max(int(tail[-2]), 1):
                 need *= 2
-            nover = int(pack[-1])
+            nover = int(tail[-1])
             # a label set with overflow queries (> 128 positives) cannot be speculated on (their list is only known to the
             # synchronous plan): remember that instead of a capacity, so that evaluations of this shape stop redoing
             _CAP_HINT[hint_key] = 0 if nover > 0 else need
-            if need > plan.cap or nover > 0:                     # the assumed capacity was too small: redo, synchronously
-                plan.cap = None
-                plan.finish()
-                return self._compute_streamed(feats, pids, camids_arg, plan=plan, _normed=(f, sq),
-                                              _clock=clock if pf is not None else None, camsets=camsets)
-        elif getattr(plan, "_stats", None) is not None:
-            _CAP_HINT[hint_key] = 0 if len(plan.overflow) else plan.cap
-        pack = pack[:-2]
+            if need <= plan.cap and nover == 0:
+                break
+            plan.cap, speculative = None, False                  # the assumed capacity was too small: redo, synchronously
+            plan.finish()
         info = None
         if pf is not None:
-            tail, pack = pack[-(nq + 5):], pack[:-(nq + 5)]
             bad = np.setdiff1d(np.nonzero(tail[:nq] != 0)[0], plan.overflow)   # (the general path's rows keep their results)
             if len(bad):
                 # rows whose list overflowed: the fp32 count on just those rows, merged and reduced again (a second read-back,
                 # only when it happens)
-                _stream_eval_prefilter_repair(fq, fg, qq, gg, plan, pf, bad, valid, ap, first)
-                cmc, mAP, topk, _ = eval_reduce_device(valid, ap, first, max_rank)
-                pack = torch.cat([cmc.double(), mAP, topk, valid.double(), ap]).cpu().numpy()
+                _stream_eval_prefilter_repair(fq, fg, qq, gg, plan, pf, bad, *res)
+                cmc, mAP, topk, _ = eval_reduce_device(*res, max_rank)
+                cmc_h, mAP_h, topk_h, _, _, _, single = _unpack_results(_pack_results(cmc, mAP, topk, res.valid, res.ap),
+                                                                        max_rank, pids[:nq])
             clock.mark("repair")
             info = dict(dtype=self.prefilter if np.isfinite(tail[nq:nq + 4]).all() else None, capacity=self.prefilter_capacity,
                         margin_max=float(tail[nq + 4]), fallback_rows=int(len(bad)), ambiguous=pf["ambiguous"])
             # per stage, summed over a redone speculation: the failed attempt's read-back and plan.finish() lie between its
             # `rescore` mark and the second attempt's `pack` mark, so they are billed to `pack`
             if clock.on:
-                stage_ms = {}
-                clock.marks[-1][1].synchronize()
-                for (_, prev), (name, ev) in zip(clock.marks, clock.marks[1:]):
-                    stage_ms[name] = stage_ms.get(name, 0.0) + prev.elapsed_time(ev)
-                info["stage_ms"] = stage_ms
-        cmc_h = pack[:max_rank].astype(np.float32)
-        mAP_h = float(pack[max_rank])
-        topk_h = pack[max_rank + 1:max_rank + 6].copy()
-        valid_h = pack[max_rank + 6:max_rank + 6 + nq] == 1
-        ap_h = pack[max_rank + 6 + nq:]
-        vi = np.nonzero(valid_h)[0]
-        single = np.stack([vi.astype(np.float64), pids[:nq][vi].astype(np.float64), ap_h[vi]], axis=1)
+                info["stage_ms"] = clock.stage_ms()
+        valid, ap, first = res
         self.last = dict(valid=valid, ap=ap, first=first, single_performance=single, plan=plan)
         if info is not None:
             self.last["prefilter"] = info
@@ -1591,16 +1593,9 @@ class R1_mAP:
             raise L.CreidError("R1_mAP.compute_chunked(respect_camids=True) runs the streamed euclidean kernels only "
                                f"(dist_func={self.dist_name!r}, compute_dtype={self.compute_dtype})")
         nq = self.num_query
-        if not euclid:
-            # SOLVER.DISTANCE_FUNC = cosine (utils/reid_metric.py:51-59,93-110 works with either function): the same
-            # query-chunk loop on the cosine matrix
-            f = self._normalised(feats, torch.float32)[0] if self.feat_norm else feats
-            sq = None
-        elif self.feat_norm:
-            f, sq = self._normalised(feats)
-        else:
-            f = feats if self.compute_dtype == torch.float32 else feats.to(self.compute_dtype)
-            sq = row_sqnorm(f)
+        # SOLVER.DISTANCE_FUNC = cosine (utils/reid_metric.py:51-59,93-110 works with either function): the same query-chunk
+        # loop on the cosine matrix
+        f, sq = self._rows(feats)
         g, gg = f[nq:].contiguous(), (sq[nq:].contiguous() if sq is not None else None)
         pids = np.asarray(pids); camids = np.asarray(camids)
         dev = feats.device

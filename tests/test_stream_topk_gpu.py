@@ -2,6 +2,8 @@
 creid_stream_topk_collect + creid_stream_topk_select in csrc/stream_eval.hip) against the materialised path
 rm.topk_rows(rm.get_euclidean(q, g, qq, gg), k) on the same device tensors -- the same indices and the same distance
 bits, ties by gallery index -- through the Python surface, inference.get_similar and the C ABI."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -260,3 +262,84 @@ def test_stream_topk_abi_argument_checks():
     assert collect() == 0 and select() == 0
     torch.cuda.synchronize()
     assert count.tolist() == [n] * m and flags.tolist() == [1] * m
+
+
+# ------------------------------------------------------------------------------------------ more than one row chunk
+CHUNK_M, CHUNK_N, CHUNK_K = 150, 700, 5
+CHUNK_BYTES = 32768          # row chunks of 64 (150 = 64 + 64 + 22), repair chunks of 32768 // (700 * 4) = 11 rows, 2 with junk
+CHUNK_SETTINGS = {"streamed": dict(sample=64), "repair": dict(sample=5, capacity=64)}
+# (case, D): D = 40 is a multiple of the 16-bit kernels' 8-element chunk; the pre-filter also runs at D = 44, where topk_stream
+# pads the fp32 rows to 48 columns
+CHUNK_CASES = [("fp32", 40), ("bf16", 40), ("f16", 40), ("prefilter", 40), ("prefilter", 44), ("junk", 40), ("junk-bf16", 40),
+               ("junk-camsets", 40)]
+
+
+@functools.lru_cache(maxsize=None)
+def _chunk_case(case, D):
+    """(q, g, qq, gg, keywords, materialised reference) of one case: seeded N(0, 1) rows, 40 pids over 3 cameras (camera sets:
+    masks over the same 3).  Computed once, shared by both settings, never written."""
+    from centroids_reid_amd import reid_metric as rm
+    rng = np.random.default_rng(CHUNK_M * 7 + CHUNK_N + D)
+    qh = rng.standard_normal((CHUNK_M, D)).astype(np.float32)
+    gh = rng.standard_normal((CHUNK_N, D)).astype(np.float32)
+    q_pids, g_pids = rng.integers(0, 40, CHUNK_M), rng.integers(0, 40, CHUNK_N)
+    q_cams, g_cams, g_masks = rng.integers(0, 3, CHUNK_M), rng.integers(0, 3, CHUNK_N), rng.integers(1, 8, CHUNK_N)
+    dtype = torch.bfloat16 if case.endswith("bf16") else torch.float16 if case == "f16" else torch.float32
+    q, g = torch.from_numpy(qh).cuda().to(dtype), torch.from_numpy(gh).cuda().to(dtype)
+    qq, gg = rm.row_sqnorm(q), rm.row_sqnorm(g)
+    d = rm.get_euclidean(q, g, qq, gg)
+    kw = {}
+    if case == "prefilter":
+        kw["prefilter"] = torch.bfloat16
+    if case.startswith("junk"):
+        camsets = case == "junk-camsets"
+        dev = lambda a: torch.from_numpy(a.astype(np.int64)).cuda()
+        kw["junk"] = rm.JunkFilter(dev(q_pids), dev(q_cams), dev(g_pids), dev(g_masks if camsets else g_cams), camsets=camsets)
+        ridx = rm.rank_keep_topk(rm.rank_rows(d), CHUNK_K, kw["junk"])[0]
+        ref = (ridx, rm.gather_ranked(d, ridx))
+    else:
+        ref = rm.topk_rows(d, CHUNK_K)
+    return q, g, qq, gg, kw, ref
+
+
+@pytest.mark.parametrize("setting", list(CHUNK_SETTINGS))
+@pytest.mark.parametrize("case,D", CHUNK_CASES, ids=[f"{c}-{D}" for c, D in CHUNK_CASES])
+def test_topk_stream_in_several_row_chunks(case, D, setting, monkeypatch):
+    """150 x 700, k = 5 with the temporaries bounded to 32 KiB instead of 256 MiB: three row chunks (64, 64, 22), repair chunks
+    of 11 rows (2 with junk).  "streamed": sample 64 at the default capacity; "repair": sample 5 and capacity 64 -- the threshold
+    is the largest of five columns, so the lists overflow and the repair runs in many chunks.  Either way the result is the
+    materialised reference and the result of the same call in ONE chunk, indices and distance bits, with the same counters."""
+    from centroids_reid_amd import reid_metric as rm
+    q, g, qq, gg, kw, ref = _chunk_case(case, D)
+    one, chunked = {}, {}
+    whole = rm.topk_stream(q, g, CHUNK_K, qq, gg, stats=one, **CHUNK_SETTINGS[setting], **kw)
+    monkeypatch.setattr(rm, "_STREAM_TOPK_CHUNK_BYTES", CHUNK_BYTES)
+    got = rm.topk_stream(q, g, CHUNK_K, qq, gg, stats=chunked, **CHUNK_SETTINGS[setting], **kw)
+    print(f"{case} D={D} {setting}: fallback_rows {chunked['fallback_rows']} max_candidates {chunked['max_candidates']}")
+    _assert_equal(got, ref)
+    _assert_equal(got, whole)
+    assert chunked["fallback_rows"] == one["fallback_rows"] and chunked["max_candidates"] == one["max_candidates"]
+    if setting == "repair":
+        assert chunked["fallback_rows"] > 11
+
+
+def test_stage_times_are_summed_over_row_chunks(monkeypatch):
+    """The pre-filtered search in three row chunks marks pack_q / sample / collect / rescore once per chunk: stage_ms holds one
+    entry per name.  re_ranking's stage names are unique."""
+    from centroids_reid_amd import reid_metric as rm
+    q, g, qq, gg, kw, _ = _chunk_case("prefilter", 40)
+    monkeypatch.setattr(rm, "_STREAM_TOPK_CHUNK_BYTES", CHUNK_BYTES)
+    stats = {"timing": True}
+    rm.topk_stream(q, g, CHUNK_K, qq, gg, sample=64, stats=stats, **kw)
+    print(stats["stage_ms"])
+    assert set(stats["stage_ms"]) == {"pack_g", "pack_q", "sample", "collect", "rescore", "repair"}
+    assert all(isinstance(v, float) and np.isfinite(v) and v >= 0 for v in stats["stage_ms"].values())
+    monkeypatch.undo()
+    gen = torch.Generator(device="cuda").manual_seed(7)
+    stats = {"timing": True}
+    rm.re_ranking(torch.randn((20, 32), generator=gen, device="cuda"), torch.randn((120, 32), generator=gen, device="cuda"),
+                  k1=6, k2=3, stats=stats)
+    print(stats["stage_ms"])
+    assert list(stats["stage_ms"]) == ["neighbours", "row_maxima", "reciprocal_sets", "weights", "expansion", "column_index",
+                                       "blend"]
+    assert all(isinstance(v, float) and np.isfinite(v) and v >= 0 for v in stats["stage_ms"].values())

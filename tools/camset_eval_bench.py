@@ -125,7 +125,7 @@ def run_case(name, nq, ng, npid, ncam, warmup, reps):
         idx = rm.rank_rows(rm.get_euclidean(fq, fg, qq, gg))
         rm.eval_func_device(idx, qp, gp, qc, plan.g_cams, camsets=True)
 
-    dev_new = events_ms(lambda: rm._stream_eval(fq, fg, qq, gg, plan), warmup, reps)
+    dev_new = events_ms(lambda: rm.stream_eval(fq, fg, qq, gg, plan), warmup, reps)
     dev_old = events_ms(lambda: quiet(old_device), warmup, reps)
     med = lambda v: (float(np.median(v)), min(v), max(v))                       # noqa: E731
     return dict(name=name, shape=f"{nq} / {ng} / {npid} / {ncam}", n_cent=n_cent, t={k: med(v) for k, v in t.items()}, mem=mem,

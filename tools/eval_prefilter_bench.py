@@ -89,7 +89,7 @@ def run_case(f, pids, cams, nq, noise, warmup, reps):
     for i in range(warmup + reps):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        rm._stream_eval(fq, fg, qq, gg, plan)
+        rm.stream_eval(fq, fg, qq, gg, plan)
         e1.record()
         e1.synchronize()
         kern.append(e0.elapsed_time(e1))
