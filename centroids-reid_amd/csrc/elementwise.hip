@@ -33,6 +33,14 @@ template <> struct Vec16<unsigned short> {
   static __device__ __forceinline__ float rnd(float v) { return bf16_bits_to_f32(f32_to_bf16_bits(v)); }   // value as stored
 };
 
+// An f32 -> f16 conversion whose operand the compiler sees coming out of an fma may be folded into v_fma_mixlo/hi_f16, which rounds
+// the exact fma ONCE, to f16; the same expression converted with v_cvt_pk_f16_f32 rounds twice (fp32, then f16).  Which lanes of
+// which kernel get the folded form is the compiler's choice (gfx950, ROCm 7: elements 6 and 7 of the second chunk of
+// bn2d_bwd_apply_kernel's two-chunk loop and nowhere else), and the two differ by one f16 ulp where the fp32 value falls on an f16
+// tie -- a few elements in a million, enough to break "bit-identical to the separate launches" between kernels of this file.
+// Every f16 value stored here therefore converts from an fp32 value that is opaque to that fold: fp32 first, then f16, everywhere.
+static __device__ __forceinline__ float f16_src(float v) { asm("" : "+v"(v)); return v; }
+
 template <> struct Vec16<_Float16> {                            // f16 storage (the reference's own mixed precision)
   static constexpr int N = 8;
   static __device__ __forceinline__ void load(const _Float16* p, float (&v)[8]) {
@@ -44,10 +52,10 @@ template <> struct Vec16<_Float16> {                            // f16 storage (
   static __device__ __forceinline__ void store(_Float16* p, const float (&v)[8]) {
     unsigned w[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) w[i] = F16T::pack2(v[2 * i], v[2 * i + 1]);
+    for (int i = 0; i < 4; ++i) w[i] = F16T::pack2(f16_src(v[2 * i]), f16_src(v[2 * i + 1]));
     *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
   }
-  static __device__ __forceinline__ float rnd(float v) { return (float)(_Float16)v; }
+  static __device__ __forceinline__ float rnd(float v) { return (float)(_Float16)f16_src(v); }
 };
 
 // ------------------------------------------------------------------ BN statistics finalize
@@ -1134,8 +1142,15 @@ static inline unsigned ew_blocks_cap(int64_t total_threads_needed, int64_t mult,
   int64_t b = (total_threads_needed + 255) / 256;
   if (b > cap) b = cap;
   if (b < 1) b = 1;
-  // make blocks*256 a multiple of `mult` (mult is a power of two <= 512)
-  const int64_t q = mult > 256 ? mult / 256 : 1;
+  // make blocks*256 a multiple of `mult` for ANY mult (the 16-byte chunks per row, C / 8 or C / 4, of a kernel whose threads keep
+  // one channel chunk across their grid-stride trips): blocks a multiple of mult / gcd(mult, 256).  A power of two <= 256 gives
+  // q = 1 and 512 gives 2 -- the grids of every shipped layer; C = 40 (mult 5) rounds up to the next multiple of 5 blocks.
+  // The rounding is upwards, so for a mult with an odd factor the cap is approximate: the grid may exceed it by up to q - 1
+  // workgroups, and even a one-workgroup problem gets q of them (251 for C = 8 * 251).  Harmless -- a thread whose first index is
+  // past the end does nothing -- and no such C is tuned for; a power of two never exceeds the cap.
+  int64_t g = mult > 0 ? mult : 1, r = 256;
+  while (r) { const int64_t t = g % r; g = r; r = t; }
+  const int64_t q = mult > 0 ? mult / g : 1;
   b = (b + q - 1) / q * q;
   return (unsigned)b;
 }
@@ -1411,7 +1426,8 @@ int creid_maxpool3x3s2_fwd(const void* x, int64_t B, int64_t H, int64_t W, int64
 
 int creid_maxpool3x3s2_bwd(const void* dy, const uint8_t* idx, int64_t B, int64_t H, int64_t W, int64_t C, int dtype,
                            void* dx, void* stream) {
-  CREID_CHECK_ARG(dy && dx && idx && B > 0 && H > 0 && W > 0 && C % 8 == 0);
+  // even H, W as the forward: the kernel walks W / 2 column pairs, an odd last column of dx would never be written
+  CREID_CHECK_ARG(dy && dx && idx && B > 0 && H > 0 && W > 0 && C % 8 == 0 && H % 2 == 0 && W % 2 == 0);
   hipStream_t s = as_stream(stream);
   DISPATCH_T(dtype,
              hipLaunchKernelGGL(maxpool_bwd_kernel<float>, dim3((unsigned)(B * H)), dim3(256), 0, s,

@@ -955,6 +955,7 @@ int creid_bn2d_bwd_pooled(const void* x, const void* dy_pooled, const uint8_t* i
                           void* stream);
 int creid_maxpool3x3s2_fwd(const void* x, int64_t B, int64_t H, int64_t W, int64_t C, int dtype, void* y,
                            uint8_t* idx, void* stream);
+/* H and W even and C % 8 == 0 in all four (forward, backward and the two fused forms), else CREID_E_ARG. */
 int creid_maxpool3x3s2_bwd(const void* dy, const uint8_t* idx, int64_t B, int64_t H, int64_t W, int64_t C,
                            int dtype, void* dx, void* stream);
 /* nn.AdaptiveAvgPool2d(1) (modelling/baseline.py:89,93): feat fp32 [B, C]. */
