@@ -835,7 +835,8 @@ __global__ __launch_bounds__(256) void rownorm_bwd_kernel(const float* __restric
     if (n > eps) { a = 1.f / n; b = xg / (n * n * n); } else { a = 1.f / eps; b = 0.f; }
   } else {
     const float den = n + eps;
-    a = 1.f / den; b = n > 0.f ? xg / (n * den * den) : 0.f;
+    // (xg / n) / den^2, not xg / (n * den * den): with eps = 1e-12 that product underflows to 0 for n < ~7e-22 and b was +-inf
+    a = 1.f / den; b = n > 0.f ? (xg / n) / (den * den) : 0.f;
   }
   for (int d = threadIdx.x; d < D; d += 256) dx[(int64_t)blockIdx.x * D + d] = a * gr[d] - b * xr[d];
 }

@@ -25,8 +25,10 @@ def flat_offsets(params):
 def flatten_(params, device, grad_tail=0):
     """Re-home `params` (list of nn.Parameter) as views of one flat fp32 buffer; returns (flat, gflat).  `grad_tail` extra
     elements behind the gradients: room for the gradient of parameters another optimiser owns (the centers), so that ONE
-    collective carries both."""
+    collective carries both.  The tail is padded to a multiple of 4 like every tensor in front of it: the non-finite check
+    of f16 training runs over gflat[n_scaled:], tail included, with a kernel that takes whole float4 only."""
     offs, n_pad = flat_offsets(params)
+    grad_tail = (int(grad_tail) + 3) // 4 * 4
     flat = torch.zeros(n_pad, dtype=torch.float32, device=device)
     gflat = torch.zeros(n_pad + grad_tail, dtype=torch.float32, device=device)
     for p, off in zip(params, offs):

@@ -16,7 +16,8 @@ fp64 best candidate beats every other candidate by more than the sum of their tw
 count as one: their fp32 distances are bit-equal, and the kernel must then return the FIRST index); the hinge is decided when
 |ap - an + margin| > b_d(ap) + b_d(an).  On decided anchors the kernel's index / coefficient must equal the fp64 one, on the
 others the index must lie inside the window and the coefficient be 0 or 1 / n.  Everything downstream takes the kernel's own
-(p_idx, n_idx, coef) as operands.
+(p_idx, n_idx, coef) as operands.  mine64 takes any distance matrix with its bound: the euclidean kind here (pdist64, dist_bound),
+the cosine kind of creid_triplet_cosine_fwd in tests/opt_ref.py (cos_dist64, cos_dist_bound, triplet_cos_bwd64 below).
 """
 from __future__ import annotations
 
@@ -127,6 +128,49 @@ def dist_bound(x, d):
     den = d + torch.sqrt((d * d - e).clamp_min(0.0))
     b = torch.minimum(e / den.clamp_min(1e-300), torch.sqrt(e))
     return b + 1e-6 + U * (d + b)
+
+
+def cos_dist64(x):
+    """the cosine kind of triplet_mine_body on rows the caller has scaled to unit length: clamp(|1 - x.y|, 1e-12), fp64 x [N, D]"""
+    return (1.0 - x @ x.t()).abs().clamp_min(1e-12)
+
+
+def cos_dist_bound(x, d):
+    """KIND 1 of triplet_mine_body: x.y is a per-lane chain of 4 ceil(D / 256) fma + 6 wave-sum levels, then 1 - dot rounds once
+    (exactly, near 1); abs and the clamp are 1-Lipschitz.  The same window machinery (mine64) takes this bound as b."""
+    D = x.shape[1]
+    ax = x.abs()
+    e = (4 * math.ceil(D / 256) + 6) * U * (ax @ ax.t())
+    return e + U * (d + e)
+
+
+def triplet_cos_bwd64(x, dap, dan, pi, ni, coef, g):
+    """triplet_bwd_body<1> on its stored operands: every active anchor a contributes, for its positive (weight -coef) and its
+    negative (+coef), w sign(1 - x_a.x_o) x_o to row a and w sign(.) x_a to row o -- nothing where the stored distance is the
+    clamp value (<= 1e-12: no gradient).  The kernel recomputes x_r.x_o (chain of ceil(D / 256) fma, 6 wave levels, 3 adds): where
+    |1 - x_r.x_o| is within that sum's error the sign it takes is undecided, and the term enters the bound with its whole
+    magnitude, twice (the reference takes the fp64 sign).  Otherwise (nt + 3) u |g| sum |w| |x_o|: the products, the running
+    sum, g * acc.  Returns (g dx, bound); the caller adds the accumulator's start and its rounding."""
+    N, D = x.shape
+    e_rel = (math.ceil(D / 256) + 9) * U
+    dx, mag, loose = (torch.zeros(N, D, dtype=F64) for _ in range(3))
+    nt = torch.zeros(N, dtype=F64)
+    clampv = torch.tensor(1e-12, dtype=torch.float32)
+    for a in range(N):
+        c = float(coef[a])
+        if c == 0.0:
+            continue
+        for o, dist, w in ((int(pi[a]), dap[a], -c), (int(ni[a]), dan[a], c)):
+            if not bool(torch.as_tensor(dist, dtype=torch.float32) > clampv):
+                continue
+            v = 1.0 - float(x[a] @ x[o])
+            und = abs(v) <= e_rel * float(x[a].abs() @ x[o].abs())
+            s = (v > 0) - (v < 0)
+            for r, q in ((a, o), (o, a)):
+                dx[r] += w * s * x[q]
+                nt[r] += 1
+                (loose if und else mag)[r] += abs(c) * x[q].abs() * (2.0 if und else 1.0)
+    return g * dx, abs(g) * ((nt[:, None] + 3) * U * mag + loose)
 
 
 def row_classes(x):

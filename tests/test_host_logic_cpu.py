@@ -82,6 +82,31 @@ def test_center_sgd_tail_adoption_is_rechecked_when_grad_is_rebound():
     assert opt.grad_in_adam_tail and float(tail.sum()) == 0.0
 
 
+def test_flat_gradient_buffer_and_its_tail_are_whole_float4():
+    """FusedAdam.step (f16 training) hands gflat[:n_scaled] and gflat[n_scaled:] -- the tail included -- to
+    creid_amp_unscale_check, which refuses n % 4 != 0.  Every offset and the padded total are multiples of 4, build_optimizer
+    sizes the tail as a sum of padded centers, and flatten_ pads a tail of any other length a caller asks for."""
+    from types import SimpleNamespace as NS
+    from centroids_reid_amd.solver import build_optimizer, flat_offsets, flatten_
+    sizes = [(3,), (5, 7), (1,), (4, 4), (2, 3, 3)]
+    params = [torch.nn.Parameter(torch.randn(*s)) for s in sizes]
+    before = [p.detach().clone() for p in params]
+    offs, total = flat_offsets(params)
+    assert all(o % 4 == 0 for o in offs) and total % 4 == 0
+    for tail in (0, 1, 6, 15, 16):
+        ps = [torch.nn.Parameter(b.clone()) for b in before]
+        flat, gflat = flatten_(ps, "cpu", tail)
+        assert flat.numel() == total and gflat.numel() % 4 == 0 and gflat.numel() - total >= tail
+        assert all((gflat.numel() - o) % 4 == 0 for o in offs)              # every suffix a prefix split can leave
+        assert all(torch.equal(p.detach(), b) for p, b in zip(ps, before))
+    hp = NS(SOLVER=NS(OPTIMIZER_NAME="Adam", BASE_LR=1e-3, WEIGHT_DECAY=5e-4, CENTER_LR=0.5))
+    named = [("backbone.w", torch.nn.Parameter(torch.randn(3, 3))), ("fc.weight", torch.nn.Parameter(torch.randn(5))),
+             ("center_loss.centers", torch.nn.Parameter(torch.randn(7, 3))), ("center_b", torch.nn.Parameter(torch.randn(2)))]
+    adam, center = build_optimizer(named, hp)
+    assert adam.gflat.numel() % 4 == 0 and adam.gtail.numel() == 24 + 4 and center.grad_in_adam_tail
+    assert all((adam.gflat.numel() - o) % 4 == 0 for o in adam._offsets)
+
+
 def test_tuned_plan_file_is_well_formed():
     """centroids-reid_amd/tuned_plans.json (what _lib registers through creid_tune_set at load time): every (kind, key) unique -- a
     duplicate would make the later entry silently win --, kinds / key lengths / plan words in the ranges the launchers decode
