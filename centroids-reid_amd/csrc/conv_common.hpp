@@ -94,7 +94,25 @@ static inline IGemmGeom dgrad_geom(const creid_conv_desc* d) {
   igemm_finish_geom(g);
   return g;
 }
+// The shape check of every stem entry point (they take no creid_conv_desc, so check_desc never sees them): CREID_E_ARG for a
+// non-positive extent, CREID_E_SHAPE for an odd H or W and for a size the kernels' index arithmetic does not hold --
+//   * rows: fast_divmod decomposes a GEMM row with fp32 reciprocals, exact below 2^24 only (check_desc's limit for every other
+//     convolution), and stem_geom narrows B * (H/2) * (W/2) to int;
+//   * source: the kernels form the PIXEL index (b * SH + iy) * SW + ix of the padded image in int and widen it to 64 bits only
+//     for the x 4 of the channel pitch, so B * (H + 8) * (W + 6) must fit an int.
+// 0 otherwise.  Called before anything is launched.
+static inline int stem_check_shape(int64_t B, int64_t H, int64_t W) {
+  if (B <= 0 || H <= 0 || W <= 0) return CREID_E_ARG;
+  if (H % 2 || W % 2) return CREID_E_SHAPE;
+  const int64_t lim = 1LL << 24;
+  if (B >= lim || H / 2 >= lim || W / 2 >= lim || (H / 2) * (W / 2) >= lim) return CREID_E_SHAPE;   // (no 64-bit overflow below)
+  if (B * ((H / 2) * (W / 2)) >= lim) return CREID_E_SHAPE;
+  if (B * ((H + 8) * (W + 6)) > 0x7fffffffLL) return CREID_E_SHAPE;
+  return 0;
+}
+
 // The stem (7x7 s2 on the pre-padded NHWC4 image [B, H + 8, W + 6, 4]): a "tap" is one kernel row of 8 pixels x 4 channels.
+// Callers check stem_check_shape first: the narrowing casts below are then exact.
 static inline IGemmGeom stem_geom(int64_t B, int64_t H, int64_t W) {
   IGemmGeom g;
   g.M = (int)(B * (H / 2) * (W / 2)); g.OH = (int)(H / 2); g.OW = (int)(W / 2);

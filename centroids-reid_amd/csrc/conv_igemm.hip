@@ -1541,8 +1541,8 @@ int creid_conv2d_dgrad_fused_nhwc(const creid_conv_desc* d, const void* dy, cons
  * (k = r*32 + s*4 + c, zero for s = 7, c = 3 and r = 7); y [B, H/2, W/2, 64]. */
 int creid_stem_conv_fwd(int64_t batch, int64_t H, int64_t W, const void* xpad, const void* w_stem, void* y,
                         float* bn_partial, int dtype, void* stream) {
-  CREID_CHECK_ARG(xpad && w_stem && y && batch > 0 && H > 0 && W > 0);
-  if (H % 2 || W % 2) return CREID_E_SHAPE;
+  CREID_CHECK_ARG(xpad && w_stem && y);
+  if (const int rc = stem_check_shape(batch, H, W)) return rc;
   IGemmGeom g = stem_geom(batch, H, W);
   return launch_igemm(g, xpad, w_stem, y, nullptr, bn_partial, dtype, as_stream(stream));
 }
@@ -1550,8 +1550,8 @@ int creid_stem_conv_fwd(int64_t batch, int64_t H, int64_t W, const void* xpad, c
 /* the stem with its eval-mode BatchNorm (and, for the IBN-a variant, ReLU) folded into the epilogue */
 int creid_stem_conv_fwd_affine(int64_t batch, int64_t H, int64_t W, const void* xpad, const void* w_stem, void* y,
                                const float* scale_shift, int relu, int dtype, void* stream) {
-  CREID_CHECK_ARG(xpad && w_stem && y && scale_shift && batch > 0 && H > 0 && W > 0);
-  if (H % 2 || W % 2) return CREID_E_SHAPE;
+  CREID_CHECK_ARG(xpad && w_stem && y && scale_shift);
+  if (const int rc = stem_check_shape(batch, H, W)) return rc;
   IGemmGeom g = stem_geom(batch, H, W);
   g.epi_scale = scale_shift; g.epi_shift = scale_shift + 64; g.epi_relu = relu ? 1 : 0;
   return launch_igemm(g, xpad, w_stem, y, nullptr, nullptr, dtype, as_stream(stream));

@@ -313,6 +313,7 @@ int creid_stem_conv_pool_fwd_affine(int64_t batch, int64_t H, int64_t W, const v
                                     const float* scale_shift, int relu, int dtype, void* stream) {
   CREID_CHECK_ARG(xpad && w_stem && y && scale_shift && batch > 0 && H > 0 && W > 0);
   if (!creid_is16(dtype)) return CREID_E_DTYPE;
+  if (const int rc = stem_check_shape(batch, H, W)) return rc;
   if (H % 8 || W % 4) return CREID_E_SHAPE;
   const int H1 = (int)(H / 2), W1 = (int)(W / 2);
   hipStream_t s = as_stream(stream);

@@ -1460,6 +1460,8 @@ int creid_conv2d_wgrad_x3_nhwc(const creid_conv_desc* d, const void* x, const vo
 size_t creid_stem_conv_wgrad_workspace_bytes(int64_t batch, int64_t H, int64_t W, int dtype) {
   // (stride 2: the launch looks its plan up with the stem geometry's stride -- with the default of 1 a measured plan of a 1 x 1
   // layer that happens to share (M, 64, 256) at another batch size answered here but not there: workspace too small)
+  // 0: a shape creid_stem_conv_wgrad refuses (stem_check_shape) -- that call then returns the refusal whatever workspace it is handed
+  if (stem_check_shape(batch, H, W)) return 0;
   const WgradPlan p = plan_wgrad((int)(batch * (H / 2) * (W / 2)), 64, 256, dtype, 2);
   return (size_t)p.splits * 64 * 256 * sizeof(float);
 }
@@ -1467,8 +1469,8 @@ size_t creid_stem_conv_wgrad_workspace_bytes(int64_t batch, int64_t H, int64_t W
 /* stem weight gradient into the OIHW [64,3,7,7] fp32 tensor (see creid_stem_conv_fwd for layouts). */
 int creid_stem_conv_wgrad(int64_t batch, int64_t H, int64_t W, const void* xpad, const void* dy, float* dw_oihw,
                           int accumulate, void* ws, size_t ws_bytes, int dtype, void* stream) {
-  CREID_CHECK_ARG(xpad && dy && dw_oihw && ws && batch > 0 && H > 0 && W > 0);
-  if (H % 2 || W % 2) return CREID_E_SHAPE;
+  CREID_CHECK_ARG(xpad && dy && dw_oihw && ws);
+  if (const int rc = stem_check_shape(batch, H, W)) return rc;
   IGemmGeom g = stem_geom(batch, H, W);
   return run_wgrad(g, dy, xpad, 64, dw_oihw, 1, 4, 3, 7, 7, accumulate, ws, ws_bytes, dtype, as_stream(stream));
 }

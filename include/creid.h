@@ -770,7 +770,11 @@ int creid_conv2d_wgrad_reduce(const creid_conv_desc* d, float* dw_oihw, int accu
                               size_t ws_bytes, int dtype, void* stream);
 
 /* Stem (resnet.py:94): Conv2d(3, 64, 7, stride 2, pad 3) on the zero-padded NHWC4 image
- * xpad [B, H+8, W+6, 4] made by creid_image_to_nhwc4_pad; w_stem [64][8][32] from creid_stem_weight_prep. */
+ * xpad [B, H+8, W+6, 4] made by creid_image_to_nhwc4_pad; w_stem [64][8][32] from creid_stem_weight_prep.
+ * Every stem call below (the three forwards, the weight gradient and its workspace size) refuses, before anything is launched:
+ * CREID_E_ARG a null pointer or a non-positive batch, H or W; CREID_E_SHAPE an odd H or W, batch * (H/2) * (W/2) >= 2^24 (the
+ * kernels decompose an output row into (image, y, x) with fp32 reciprocals, exact below 2^24 only -- the limit of every other
+ * convolution) and batch * (H+8) * (W+6) > 2^31 - 1 (they index the padded image's pixels in 32 bits). */
 int creid_stem_conv_fwd(int64_t batch, int64_t H, int64_t W, const void* xpad, const void* w_stem, void* y,
                         float* bn_partial, int dtype, void* stream);
 /* the stem with its eval-mode BatchNorm (scale_shift float[2][64]) and optional ReLU (resnet_ibn_a.py:129) folded in */
@@ -797,6 +801,9 @@ int creid_bottleneck_c3_c1_fwd_affine(int64_t M, int64_t c_mid, int64_t c_out, i
 int creid_bottleneck_c3_c1_fwd_stats(int64_t M, int64_t c_mid, int64_t c_out, int64_t c_next, const void* a2, const void* w3_krsc,
                                      const float* fold3, const void* residual, void* out3, const void* w1_krsc, void* out1_raw,
                                      float* bn_partial1, int dtype, void* stream);
+/* Stem weight gradient into the fp32 OIHW [64, 3, 7, 7] tensor (dy [batch, H/2, W/2, 64]; accumulate, ws as in
+ * creid_conv2d_wgrad_nhwc).  creid_stem_conv_wgrad_workspace_bytes returns 0 for a shape the stem calls refuse (above):
+ * creid_stem_conv_wgrad then returns that refusal whatever workspace it is given. */
 size_t creid_stem_conv_wgrad_workspace_bytes(int64_t batch, int64_t H, int64_t W, int dtype);
 int creid_stem_conv_wgrad(int64_t batch, int64_t H, int64_t W, const void* xpad, const void* dy,
                           float* dw_oihw, int accumulate, void* ws, size_t ws_bytes, int dtype, void* stream);
