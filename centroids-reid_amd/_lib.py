@@ -58,6 +58,11 @@ SIGNATURES = {
                                                      _p]),
     "creid_rank_keep_topk": (C.c_int, [_p, _i64, _i64, _i64, _i32, _p, _p, _p, _p, _i32, _p, _p, _p, _p]),
     "creid_junk_mask_rows": (C.c_int, [_p, _i64, _i64, _i64, _p, _p, _p, _p, _i32, _p]),
+    "creid_stream_dist_hist": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _i32, _p, _i32, _i32, _i32, _p, _p]),
+    "creid_stream_dist_hist_h16": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, C.c_int, _p, _p, _p, _p, _i32, _p, _i32, _i32, _i32, _p,
+                                             _p]),
+    "creid_dist_hist_matrix": (C.c_int, [_p, _i64, _i64, _p, _p, _p, _p, _i32, _p, _i32, _i32, _i32, _p, _p]),
+    "creid_roc_descend": (C.c_int, [_p, _i32, _i32, _i32, _p, _p, _p, _p]),
     "creid_prefilter_pack": (C.c_int, [_p, _i64, _i64, C.c_int, _p, _p, _p]),
     "creid_stream_topk_rescore": (C.c_int, [_p, _p, _i64, _i32, _i32, _p, _p, _p, _p, _i64, _i64, _p, _p, _p, _p, _p, _p]),
     "creid_stream_count_band_h16": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i64, C.c_int, _p, _p, _i32, _p, _p, _p, _p, _i32, _p, _p, _p,

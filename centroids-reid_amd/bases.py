@@ -147,12 +147,16 @@ def load_checkpoint_file(path, map_location="cpu"):
 
 class ModelBase(_Base):
     def __init__(self, cfg=None, test_dataloader=None, compute_dtype=None, eval_precision=None, eval_prefilter=None,
-                 eval_query_expansion=None, **kwargs):
+                 eval_query_expansion=None, eval_roc=None, **kwargs):
         """eval_prefilter=torch.bfloat16 | torch.float16: get_val_metrics runs its streamed evaluation with the counting
         contraction on the 16-bit MFMA and the fp32 results (R1_mAP(prefilter=...)); not with camera-aware centroids.
         eval_query_expansion=True | a dict of k / alpha / rounds / scope: get_val_metrics expands the normalised rows by their
-        nearest neighbours before ranking (R1_mAP(query_expansion=...); needs TEST.FEAT_NORM)."""
+        nearest neighbours before ranking (R1_mAP(query_expansion=...); needs TEST.FEAT_NORM).
+        eval_roc=True | a tuple of false-accept rates: get_val_metrics also reports the open-set operating points of the
+        validation distances (R1_mAP(roc=...)): one line per rate, `TAR@FAR=<rate>` and `thr@FAR=<rate>` (the squared-L2
+        threshold below which a pair is accepted) in the logged dict, the whole result in `self.last_roc`."""
         super().__init__()
+        self.eval_roc = eval_roc
         self.eval_prefilter = eval_prefilter
         self.eval_query_expansion = eval_query_expansion
         if cfg is None:
@@ -395,7 +399,8 @@ class ModelBase(_Base):
                                   feat_norm=self.hparams.TEST.FEAT_NORM, streamed=True,   # only the metrics are used
                                   prefilter=None if respect_camids else self.eval_prefilter,
                                   query_expansion=getattr(self, "eval_query_expansion", None),
-                                  ranked_topk=int(self.hparams.TEST.VISUALIZE_TOPK) if visualize else None)
+                                  ranked_topk=int(self.hparams.TEST.VISUALIZE_TOPK) if visualize else None,
+                                  roc=getattr(self, "eval_roc", None))
         cmc, mAP, all_topk = self.r1_map_func.compute(feats=embeddings.float(), pids=labels, camids=camids,
                                                       respect_camids=respect_camids)
         if visualize:
@@ -408,6 +413,13 @@ class ModelBase(_Base):
             topks[f"Top-{kk}"] = top_k
         print(f"mAP: {mAP}")
         log_data = {"mAP": mAP, **topks}
+        if self.r1_map_func.roc is not None:
+            self.last_roc = roc = self.r1_map_func.last["roc"]
+            for i, rate in enumerate(roc["target"]):
+                print("TAR@FAR={:g}: {:.2%} (threshold {:.6g}, {} false accepts of {})".format(
+                    rate, roc["tar"][i], roc["threshold"][i], roc["false_accepts"][i], roc["n_impostor"][i]))
+                log_data[f"TAR@FAR={rate:g}"] = float(roc["tar"][i])
+                log_data[f"thr@FAR={rate:g}"] = float(roc["threshold"][i])
         logger = getattr(self.trainer, "logger", None)
         if logger is not None:
             logger.log_metrics(log_data, step=self.trainer.current_epoch)

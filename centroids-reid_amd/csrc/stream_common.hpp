@@ -11,9 +11,12 @@ constexpr int SQ_TM = 64, SQ_TN = 256;           // a tile: 64 query rows x 256 
 constexpr int EPI_COUNT = 0, EPI_TOPK = 1;       // what a streamed contraction does with a finished tile
 constexpr int EPI_BAND = 2;                      // the count with a per-row error band (16-bit kernel only: stream_consume.hpp)
 constexpr int EPI_TOPK_KEEP = 3;                 // the top-k that lists only the entries the evaluation protocol keeps (no junk)
+constexpr int EPI_HIST = 4;                      // the radix histogram of the non-junk distance keys, by class (open-set ROC)
 constexpr bool epi_is_topk(int epi) { return epi == EPI_TOPK || epi == EPI_TOPK_KEEP; }
 constexpr int PL_MAXC = 128;                     // positive-list capacity of the count epilogue (LDS: [64][cap] keys + histogram)
 constexpr int TS_MIN_CAP = 64, TS_MAX_CAP = 8192;   // candidate-list capacity of the top-k epilogue
+constexpr int HS_MAX_BITS = 11, HS_MAX_BINS = 8192; // histogram epilogue: digit width, and nsel << bits (the LDS table
+                                                    // [nsel][2][2^bits] words fits the count's 64 KiB of dynamic LDS)
 
 // Argument tests of the entry points.  A list capacity is a power of two inside its epilogue's range (the kernels index with
 // shifts and masks: stream_log2cap); m and n leave room for the 32-bit tile arithmetic.
@@ -21,6 +24,12 @@ static bool stream_cap_ok(int64_t cap, int lo, int hi) { return cap >= lo && cap
 static bool stream_count_cap_ok(int64_t cap) { return stream_cap_ok(cap, 2, PL_MAXC); }
 static bool stream_topk_cap_ok(int64_t cap) { return stream_cap_ok(cap, TS_MIN_CAP, TS_MAX_CAP); }
 static bool stream_mn_ok(int64_t m, int64_t n) { return m <= 0x7ffffff0LL && n <= 0x7ffffff0LL; }
+// A radix pass: nsel selectors of prefix_bits leading key bits each, a digit of `bits` bits behind them.  Without a prefix there
+// is nothing to tell selectors apart, so there is one.
+static bool stream_hist_ok(int64_t nsel, int64_t prefix_bits, int64_t bits) {
+  return bits >= 1 && bits <= HS_MAX_BITS && prefix_bits >= 0 && prefix_bits + bits <= 32 && nsel >= 1 &&
+         nsel <= (HS_MAX_BINS >> bits) && (prefix_bits != 0 || nsel == 1);
+}
 static int stream_log2cap(int cap) {
   int l = 0;
   while ((1 << l) < cap) ++l;
@@ -128,25 +137,35 @@ struct StreamList {       // EPI_TOPK[_KEEP]: thresholds and candidate lists; EP
   int32_t* count = nullptr;
   int32_t cap = 0;
 };
-struct StreamCams { const int64_t *q_cams = nullptr, *g_cams = nullptr; int camsets = 0; };   // EPI_TOPK_KEEP
+struct StreamCams { const int64_t *q_cams = nullptr, *g_cams = nullptr; int camsets = 0; };   // EPI_TOPK_KEEP, EPI_HIST
+struct StreamHist {       // EPI_HIST: the pass's selectors (prefix may be null without prefix bits) and the counts it adds into
+  const uint32_t* prefix = nullptr;
+  int32_t nsel = 0, prefix_bits = 0, bits = 0;
+  unsigned long long* out = nullptr;
+};
 
 /* The argument tests of every streamed contraction; false: return *rc (0: nothing to do).  d_mult / d_max: the widths the
  * kernel loads; dtype_ok: the 16-bit kernels' dtype test.  An empty query set is a no-op -- for the count epilogues whatever
  * the capacities and widths are, for the top-k epilogues once they have passed: the precedence each family of entry points
- * has always had (tests/test_stream_h16_cpu.py and the *_abi_argument_checks GPU tests pin both). */
+ * has always had (tests/test_stream_h16_cpu.py and the *_abi_argument_checks GPU tests pin both); the histogram epilogue follows
+ * the top-k family (every refusal of a shape or dtype, then m == 0, then the pointers). */
 template <int EPI>
 static bool stream_args_pass(const StreamRows& x, const StreamPids& pids, const StreamPos& pos, const StreamList& list,
-                             const StreamCams& cams, int64_t d_mult, int64_t d_max, bool dtype_ok, int* rc) {
-  constexpr bool topk = epi_is_topk(EPI);
-  constexpr bool use_pids = EPI != EPI_TOPK, use_pos = !topk, use_list = EPI != EPI_COUNT, use_cams = EPI == EPI_TOPK_KEEP;
+                             const StreamCams& cams, int64_t d_mult, int64_t d_max, bool dtype_ok, int* rc,
+                             const StreamHist& hs = {}) {
+  constexpr bool topk = epi_is_topk(EPI), hist = EPI == EPI_HIST;
+  constexpr bool use_pids = EPI != EPI_TOPK, use_pos = !topk && !hist, use_list = EPI != EPI_COUNT && !hist;
+  constexpr bool use_cams = EPI == EPI_TOPK_KEEP || hist;
   const bool ptrs = x.q && x.g && x.qq && x.gg && (!use_pids || (pids.q_pids && pids.g_pids)) &&
                     (!use_pos || (pos.key && pos.idx && pos.npos && pos.hist)) &&
-                    (!use_list || (list.thr && list.list && list.count)) && (!use_cams || (cams.q_cams && cams.g_cams));
+                    (!use_list || (list.thr && list.list && list.count)) && (!use_cams || (cams.q_cams && cams.g_cams)) &&
+                    (!hist || (hs.out && (hs.prefix || hs.prefix_bits == 0)));
   const auto stop = [rc](int code) { *rc = code; return false; };
   if (!(x.m >= 0 && x.n > 0 && x.D > 0)) return stop(CREID_E_ARG);
-  if (!topk && x.m == 0) return stop(0);
-  if (!topk && !ptrs) return stop(CREID_E_ARG);
-  if ((use_pos && !stream_count_cap_ok(pos.cap)) || (use_list && !stream_topk_cap_ok(list.cap)) || x.D % d_mult != 0 || x.D > d_max)
+  if (!topk && !hist && x.m == 0) return stop(0);
+  if (!topk && !hist && !ptrs) return stop(CREID_E_ARG);
+  if ((use_pos && !stream_count_cap_ok(pos.cap)) || (use_list && !stream_topk_cap_ok(list.cap)) || x.D % d_mult != 0 || x.D > d_max ||
+      (hist && !stream_hist_ok(hs.nsel, hs.prefix_bits, hs.bits)))
     return stop(CREID_E_SHAPE);
   if (!stream_mn_ok(x.m, x.n)) return stop(CREID_E_SHAPE);
   if (!dtype_ok) return stop(CREID_E_DTYPE);
@@ -156,7 +175,9 @@ static bool stream_args_pass(const StreamRows& x, const StreamPids& pids, const 
 }
 
 /* Launch of either file's kernel for the epilogue EPI: the count epilogues through stream_count_launch (dynamic LDS; the banded
- * count with its row margins behind the lists), the top-k epilogues with static LDS only. */
+ * count with its row margins behind the lists), the top-k epilogues with static LDS only.  The histogram epilogue's table,
+ * 2 * (nsel << bits) words, takes the place of the count's lists: pos_cap = stream_hist_lds_cap(nsel, bits). */
+static int stream_hist_lds_cap(int nsel, int bits) { return ((nsel << bits) + SQ_TM - 1) / SQ_TM; }
 template <auto Kernel, int EPI, class... Args>
 static int stream_launch(const StreamSplit& sp, int pos_cap, void* stream, Args... args) {
   if constexpr (epi_is_topk(EPI)) {

@@ -5,8 +5,9 @@
 // register r of lane (l31 = lane & 31, kh = lane >> 5) is row wm * 32 + 4 kh + (r & 3) + 8 (r >> 2), column l31 of its block.
 //
 //   stream_segment_begin<EPI>   per (query tile, run of columns): the LDS state the consumer reads
-//   stream_tile_consume<EPI, H, NJ>   one finished tile: the count, the top-k, the banded-count or the junk-free top-k epilogue
-//   stream_segment_end          count / banded count: the LDS histogram leaves for global memory
+//   stream_tile_consume<EPI, H, NJ>   one finished tile: the count, the top-k, the banded-count, the junk-free top-k or the
+//                               radix-histogram epilogue
+//   stream_segment_end          count / banded count / radix histogram: the LDS histogram leaves for global memory
 //   STREAM_DISPATCH_NJ          the tile width as a compile-time constant
 //   poslist_pad / poslist_rank_emit   the tail of the two positives kernels
 //
@@ -18,7 +19,8 @@
 
 // The LDS state of a segment: per query row of the tile its norm, pid, number of positives and `kmax` (count: key of the row's last
 // positive; top-k: key of the row's threshold); count only: the rows' positive keys [64][cap] and the histogram [64][cap];
-// banded count: the count's state and the rows' margins `mg`; junk-free top-k: the top-k's state and the rows' pid and camera.
+// banded count: the count's state and the rows' margins `mg`; junk-free top-k: the top-k's state and the rows' pid and camera;
+// radix histogram: the rows' norm, pid and camera, and in `keys` the table [nsel][2][2^bits] of counts (class 0 genuine, 1 impostor).
 struct StreamLds {
   float* qq;
   long long* qpid;
@@ -33,7 +35,9 @@ struct StreamLds {
 // The problem the consumers see: sizes, list capacity, and the global arrays they read or write (count: q_pids .. hist_out;
 // top-k: tau .. cand_count; the other group is unused and may be null.  Banded count: the count's group, and tau = the rows'
 // margins, cand = the rows' lists of ambiguous columns -- [m][acap] 32-bit words --, cand_count = their lengths.  Junk-free
-// top-k: the top-k's group, the pids, and the cameras: q_cams plain ids; g_cams plain ids, or -- camsets != 0 -- bitmasks).
+// top-k: the top-k's group, the pids, and the cameras: q_cams plain ids; g_cams plain ids, or -- camsets != 0 -- bitmasks.
+// Radix histogram: the pids and the cameras; cap = the number of selectors nsel, log2cap = the digit's width `bits`, acap = the
+// prefix bits, pos_key = the nsel prefixes, cand = the counts uint64 [nsel][2][2^bits] the segments add into.)
 struct StreamProblem {
   int m, n, cap, log2cap;
   const float* qq;
@@ -53,13 +57,45 @@ struct StreamProblem {
   int camsets;
 };
 
+// One count per lane with `hit` into the LDS table `tab`, aggregated per wave: the first pending lane's bin is broadcast, the lanes
+// that share it are counted with one ballot and leave with ONE ds_add of the popcount; the rounds go on while they pay -- until
+// one collects fewer than HS_MIN_GROUP lanes, or after the first when `once` -- and whoever is still pending then adds for itself.
+// The first radix pass is the contended one: the distance keys of unit rows crowd into 2-4 of its bins, so a wave is done after
+// 2-4 rounds where 64 atomics would have queued on as many addresses.  Behind a prefix (`once`) the next digit is mantissa
+// bits, close to uniform over its bins: a round per distinct bin would be up to 64 serial rounds per call (measured: the second
+// pass 6.8 x the count kernel's time in fp32 and 27 x in bf16 with unbounded rounds, profiles/roc_stream.md), while 64 adds on
+// distinct addresses are one cheap instruction; the one round still collapses a run of equal keys.  Every lane of the wave
+// calls it (`lane` = its index in the wave); the loop is wave-uniform.
+constexpr int HS_MIN_GROUP = 4;
+__device__ __forceinline__ void wave_hist_add(unsigned* tab, bool hit, unsigned idx, int lane, bool once) {
+  unsigned long long todo = __ballot(hit);
+  while (todo) {
+    const int leader = __ffsll((long long)todo) - 1;
+    const unsigned lidx = __builtin_amdgcn_readlane(idx, leader);
+    const unsigned long long same = todo & __ballot(idx == lidx);
+    const int cnt = __popcll(same);
+    if (lane == leader) atomicAdd(&tab[lidx], (unsigned)cnt);
+    todo &= ~same;
+    if (once || cnt < HS_MIN_GROUP) break;
+  }
+  if ((todo >> lane) & 1ull) atomicAdd(&tab[idx], 1u);
+}
+
 // Every thread of the 256-thread workgroup calls it, behind a barrier after the previous segment's stream_segment_end; the
 // barrier that opens the first tile publishes the state.
 template <int EPI>
 __device__ __forceinline__ void stream_segment_begin(const StreamLds& L, const StreamProblem& P, int row0) {
   int ts = threadIdx.x;                            // opaque: the set-up's LDS addresses are recomputed per segment instead of
   asm volatile("" : "+v"(ts));                     // occupying registers (or scratch) across the k-loops
-  if constexpr (epi_is_topk(EPI)) {
+  if constexpr (EPI == EPI_HIST) {
+    for (int i = ts; i < (2 * P.cap) << P.log2cap; i += 256) L.keys[i] = 0u;
+    if (ts < SQ_TM) {
+      const int rr = row0 + ts;
+      L.qq[ts] = rr < P.m ? P.qq[rr] : 0.f;
+      L.qpid[ts] = rr < P.m ? (long long)P.q_pids[rr] : 0;
+      L.qcam[ts] = rr < P.m ? (long long)P.q_cams[rr] : 0;
+    }
+  } else if constexpr (epi_is_topk(EPI)) {
     if (ts < SQ_TM) {
       const int rr = row0 + ts;
       L.qq[ts] = rr < P.m ? P.qq[rr] : 0.f;
@@ -87,11 +123,20 @@ __device__ __forceinline__ void stream_segment_begin(const StreamLds& L, const S
   }
 }
 
-// count / banded count: flushes the segment's histogram (every thread of the workgroup, after the segment's last tile)
+// count / banded count: flushes the segment's histogram (every thread of the workgroup, after the segment's last tile);
+// radix histogram: the segment's table is added to the call's, bin for bin (64-bit integers: order-independent)
+template <int EPI = EPI_COUNT>
 __device__ __forceinline__ void stream_segment_end(const StreamLds& L, const StreamProblem& P, int row0) {
   int ts = threadIdx.x;
   asm volatile("" : "+v"(ts));                     // opaque, as in stream_segment_begin
   __syncthreads();
+  if constexpr (EPI == EPI_HIST) {
+    for (int i = ts; i < (2 * P.cap) << P.log2cap; i += 256) {
+      const unsigned v = L.keys[i];
+      if (v) atomicAdd(&P.cand[i], (unsigned long long)v);
+    }
+    return;
+  }
   for (int i = ts; i < SQ_TM * P.cap; i += 256) {
     const unsigned v = L.hist[i];
     const int rr = row0 + (i >> P.log2cap);
@@ -121,6 +166,12 @@ __device__ __forceinline__ void stream_segment_end(const StreamLds& L, const Str
 //              the slot is below `acap`) for creid_stream_count_rescore.  Otherwise every positive from l on ranks behind it and
 //              the slot is l, as the fp32 kernel finds it.  A pair whose dh, lo or hi is not finite is ambiguous.  key(hi) is
 //              formed again after the search instead of living through it: the search's registers are the count's.
+//   EPI_HIST : one pass of a radix select over the keys of the pairs the evaluation protocol keeps (open-set operating points:
+//              reid_metric.roc_stream).  An element of the row's pid fetches its camera word: junk counts nowhere, the others are
+//              genuine (class 0); every other pid is an impostor (class 1).  For selector s the element counts when its leading
+//              `acap` key bits equal pos_key[s] (always without prefix bits), in bin (key >> (32 - acap - bits)) & (2^bits - 1) of
+//              the LDS table [s][class], with wave-aggregated LDS atomics (wave_hist_add).  Integers only: the
+//              result does not depend on the work split or on the order of anything.
 template <int EPI, int H, int NJ>
 __device__ __forceinline__ void stream_tile_consume(const f32x16 (&acc)[NJ], int wm, int wn, int l31, int kh, int row0, int col0,
                                                     int skip_count, const StreamLds& L, const StreamProblem& P) {
@@ -136,7 +187,38 @@ __device__ __forceinline__ void stream_tile_consume(const f32x16 (&acc)[NJ], int
     gv[j] = okc[j] ? P.gg[c] : 0.f;
     if constexpr (!epi_is_topk(EPI)) gp[j] = okc[j] ? (long long)P.g_pids[c] : 0;
   }
-  if constexpr (epi_is_topk(EPI)) {
+  if constexpr (EPI == EPI_HIST) {
+    // One accumulator row at a time; a half-wave shares its row, so the 64 lanes of an aggregation hold two rows' elements.
+    // (The selectors' prefixes are uniform scalar loads per element; keeping them in LDS instead changed no timing:
+    // profiles/roc_stream.md.)
+    const int nsel = P.cap, bits = P.log2cap, pb = P.acap;
+    const int dshift = 32 - pb - bits;
+    const unsigned dmask = (1u << bits) - 1u;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int rl = rbase + (r & 3) + 8 * (r >> 2);
+      const float qv = L.qq[rl];
+      const long long qp = L.qpid[rl];
+      const bool okr = row0 + rl < P.m;
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        const unsigned key = mono_key(fmaf(-2.0f, acc[j][r], qv + gv[j]));
+        bool live = okr && okc[j];
+        unsigned cls = 1u;                                           // impostor
+        if (live && gp[j] == qp) {                                   // rare: the camera word is fetched for the row's pid only
+          const int64_t gc = P.g_cams[col0 + (wn + 2 * j) * 32 + l31], qc = L.qcam[rl];
+          cls = 0u;                                                  // genuine, unless the protocol removes it
+          if (P.camsets ? cam_removed<true>(gc, qc) : cam_removed<false>(gc, qc)) live = false;
+        }
+        const unsigned pfx = (unsigned)((unsigned long long)key >> (32 - pb));       // 0 without prefix bits
+        const unsigned bin = (key >> dshift) & dmask;
+        for (int s = 0; s < nsel; ++s) {
+          const unsigned want = pb ? P.pos_key[s] : 0u;              // uniform: a scalar load
+          wave_hist_add(L.keys, live && pfx == want, ((2u * s + cls) << bits) | bin, l31 + 32 * kh, pb != 0);
+        }
+      }
+    }
+  } else if constexpr (epi_is_topk(EPI)) {
     // One accumulator row at a time: its threshold is one LDS read, a hit one global atomic.
 #pragma unroll
     for (int r = 0; r < 16; ++r) {

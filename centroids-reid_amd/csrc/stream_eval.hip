@@ -127,6 +127,9 @@ __global__ __launch_bounds__(PL_MAXC) void stream_poslist_kernel(
 //              threshold keys (s_kmax) next to s_qq; no dynamic LDS; the label / list arguments of the count are unused.
 //   EPI_TOPK_KEEP: the collection without the evaluation protocol's junk (EPI_TOPK's arguments, and q_pids, g_pids, q_cams,
 //              g_cams, camsets; s_qpid / s_qcam next to s_kmax).
+//   EPI_HIST : one radix pass over the keys of the pairs the evaluation protocol keeps (q_pids, g_pids, q_cams, g_cams, camsets;
+//              cap = the number of selectors, log2cap = the digit's width, skip_count = the prefix bits, pos_key = the prefixes,
+//              cand = the uint64 counts the segments add into).  Dynamic LDS: the table [nsel][2][2^bits] in place of the lists.
 template <int ABL, bool FULLK, int EPI = EPI_COUNT>
 __global__ __launch_bounds__(256, FULLK ? 2 : 1) void sqdist_count_f32_kernel(
     const float* __restrict__ q, const float* __restrict__ g, const float* __restrict__ qq, const float* __restrict__ gg,
@@ -139,7 +142,7 @@ __global__ __launch_bounds__(256, FULLK ? 2 : 1) void sqdist_count_f32_kernel(
   __shared__ __attribute__((aligned(16))) float Bs[2][2][4][SQ_PB];
   __shared__ float s_qq[SQ_TM];
   __shared__ long long s_qpid[SQ_TM];
-  __shared__ long long s_qcam[SQ_TM];            // EPI_TOPK_KEEP only (no other instantiation names it: no LDS there)
+  __shared__ long long s_qcam[SQ_TM];            // EPI_TOPK_KEEP / EPI_HIST only (no other instantiation names it: no LDS there)
   __shared__ int s_np[SQ_TM];
   __shared__ unsigned s_kmax[SQ_TM];             // count: key of the row's last positive; top-k: key of the row's threshold
   extern __shared__ __attribute__((aligned(16))) unsigned dyn[];
@@ -149,8 +152,8 @@ __global__ __launch_bounds__(256, FULLK ? 2 : 1) void sqdist_count_f32_kernel(
   const int wm = wave >> 1, wn = wave & 1;
   const int l31 = lane & 31, kh = lane >> 5;
   const StreamLds L{s_qq, s_qpid, s_np, s_kmax, s_keys, s_hist, nullptr, s_qcam};
-  const StreamProblem P{m, n, cap, log2cap, qq, gg, q_pids, g_pids, pos_key, pos_idx, npos, hist_out, tau, cand, cand_count, 0,
-                        q_cams, g_cams, camsets};
+  const StreamProblem P{m, n, cap, log2cap, qq, gg, q_pids, g_pids, pos_key, pos_idx, npos, hist_out, tau, cand, cand_count,
+                        EPI == EPI_HIST ? skip_count : 0, q_cams, g_cams, camsets};
   long long g0, g1;                              // this workgroup's run, in units of the rows laid end to end
   stream_run(tiles_m, U, upw, mode, g0, g1);
 
@@ -333,7 +336,7 @@ __global__ __launch_bounds__(256, FULLK ? 2 : 1) void sqdist_count_f32_kernel(
       STREAM_DISPATCH_NJ(nj, tile, col, next);
       col += 256;
     }
-    if constexpr (EPI == EPI_COUNT) stream_segment_end(L, P, row0);
+    if constexpr (EPI == EPI_COUNT || EPI == EPI_HIST) stream_segment_end<EPI>(L, P, row0);
   }
 }
 
@@ -505,18 +508,20 @@ static int stream_poslist_launch(const float* q, const float* g, const float* qq
  * epilogue EPI with the groups it does not use left empty.  ABL / skip_count: the timing ablation of creid_stream_count. */
 template <int EPI, int ABL = 0>
 static int stream_f32_launch(const StreamRows& x, const StreamPids& pids, const StreamPos& pos, const StreamList& list,
-                             const StreamCams& cams, void* stream, int skip_count = 0) {
+                             const StreamCams& cams, void* stream, int skip_count = 0, const StreamHist& hs = {}) {
   int rc;
-  if (!stream_args_pass<EPI>(x, pids, pos, list, cams, 4, INT64_MAX, true, &rc)) return rc;
-  constexpr bool topk = epi_is_topk(EPI);
+  if (!stream_args_pass<EPI>(x, pids, pos, list, cams, 4, INT64_MAX, true, &rc, hs)) return rc;
+  constexpr bool topk = epi_is_topk(EPI), hist = EPI == EPI_HIST;
   const StreamSplit sp = stream_split(x.m, x.n, x.D);
-  const int cap = topk ? list.cap : pos.cap, log2cap = topk ? 0 : stream_log2cap(pos.cap);
+  const int cap = hist ? hs.nsel : topk ? list.cap : pos.cap, log2cap = hist ? hs.bits : topk ? 0 : stream_log2cap(pos.cap);
+  const int lds_cap = hist ? stream_hist_lds_cap(hs.nsel, hs.bits) : pos.cap;
   const auto launch = [&](auto fullk) {
     constexpr bool F = decltype(fullk)::value;
     return stream_launch<sqdist_count_f32_kernel<F ? ABL : 0, F, EPI>, EPI>(
-        sp, pos.cap, stream, static_cast<const float*>(x.q), static_cast<const float*>(x.g), x.qq, x.gg, (int)x.m, (int)x.n,
-        (int)x.D, pids.q_pids, pids.g_pids, cap, log2cap, pos.key, pos.idx, pos.npos, pos.hist, sp.tiles_m, sp.U, sp.upw, sp.mode,
-        skip_count, list.thr, list.list, list.count, cams.q_cams, cams.g_cams, cams.camsets);
+        sp, lds_cap, stream, static_cast<const float*>(x.q), static_cast<const float*>(x.g), x.qq, x.gg, (int)x.m, (int)x.n,
+        (int)x.D, pids.q_pids, pids.g_pids, cap, log2cap, hist ? hs.prefix : pos.key, pos.idx, pos.npos, pos.hist, sp.tiles_m, sp.U,
+        sp.upw, sp.mode, hist ? hs.prefix_bits : skip_count, list.thr, hist ? hs.out : list.list, list.count, cams.q_cams,
+        cams.g_cams, cams.camsets);
   };
   return x.D % SQ_BK == 0 ? launch(std::true_type{}) : launch(std::false_type{});
 }
@@ -608,6 +613,14 @@ int creid_stream_topk_collect_keep(const float* q, const float* g, const float* 
   return stream_f32_launch<EPI_TOPK_KEEP>({q, g, qq, gg, m, n, D}, {q_pids, g_pids}, {},
                                           {tau, reinterpret_cast<unsigned long long*>(cand), count, cap},
                                           {q_cams, g_cams, camsets != 0 ? 1 : 0}, stream);
+}
+
+int creid_stream_dist_hist(const float* q, const float* g, const float* qq, const float* gg, int64_t m, int64_t n, int64_t D,
+                           const int64_t* q_pids, const int64_t* g_pids, const int64_t* q_cams, const int64_t* g_cams,
+                           int32_t camsets, const uint32_t* prefix, int32_t nsel, int32_t prefix_bits, int32_t bits, uint64_t* hist,
+                           void* stream) {
+  return stream_f32_launch<EPI_HIST>({q, g, qq, gg, m, n, D}, {q_pids, g_pids}, {}, {}, {q_cams, g_cams, camsets != 0 ? 1 : 0}, stream,
+                                     0, {prefix, nsel, prefix_bits, bits, reinterpret_cast<unsigned long long*>(hist)});
 }
 
 int creid_stream_topk_select(const uint64_t* cand, const int32_t* count, int64_t m, int32_t cap, int32_t k, int64_t* out_idx,

@@ -164,7 +164,7 @@ __global__ __launch_bounds__(256, 2) void sqdist_stream_h16_kernel(
   __shared__ __attribute__((aligned(16))) unsigned short Bs[SQ_TN * H_BK];
   __shared__ float s_qq[SQ_TM];
   __shared__ long long s_qpid[SQ_TM];
-  __shared__ long long s_qcam[SQ_TM];            // EPI_TOPK_KEEP only (no other instantiation names it: no LDS there)
+  __shared__ long long s_qcam[SQ_TM];            // EPI_TOPK_KEEP / EPI_HIST only (no other instantiation names it: no LDS there)
   __shared__ int s_np[SQ_TM];
   __shared__ unsigned s_kmax[SQ_TM];             // count: key of the row's last positive; top-k: key of the row's threshold
   extern __shared__ __attribute__((aligned(16))) unsigned dyn[];
@@ -288,7 +288,7 @@ __global__ __launch_bounds__(256, 2) void sqdist_stream_h16_kernel(
       STREAM_DISPATCH_NJ(nj, tile, col, next);
       col += 256;
     }
-    if constexpr (!epi_is_topk(EPI)) stream_segment_end(L, P, row0);
+    if constexpr (!epi_is_topk(EPI)) stream_segment_end<EPI>(L, P, row0);
   }
 }
 
@@ -322,17 +322,21 @@ static int stream_poslist_h16_launch(const void* q, const void* g, const float* 
  * the dtype and the epilogue EPI with the groups it does not use left empty. */
 template <int EPI>
 static int stream_h16_launch(const StreamRows& x, int dtype, const StreamPids& pids, const StreamPos& pos, const StreamList& list,
-                             const StreamCams& cams, void* stream) {
+                             const StreamCams& cams, void* stream, const StreamHist& hs = {}) {
   int rc;
-  if (!stream_args_pass<EPI>(x, pids, pos, list, cams, 8, H_MAX_D, creid_is16(dtype), &rc)) return rc;
-  constexpr bool topk = epi_is_topk(EPI);
+  if (!stream_args_pass<EPI>(x, pids, pos, list, cams, 8, H_MAX_D, creid_is16(dtype), &rc, hs)) return rc;
+  constexpr bool topk = epi_is_topk(EPI), hist = EPI == EPI_HIST;
   const StreamSplit sp = stream_split(x.m, x.n, x.D, 2);
-  const int cap = topk ? list.cap : pos.cap, log2cap = topk ? 0 : stream_log2cap(pos.cap), acap = EPI == EPI_BAND ? list.cap : 0;
+  // the histogram epilogue: cap = the selectors, log2cap = the digit's width, acap = the prefix bits (stream_consume.hpp)
+  const int cap = hist ? hs.nsel : topk ? list.cap : pos.cap, log2cap = hist ? hs.bits : topk ? 0 : stream_log2cap(pos.cap);
+  const int acap = hist ? hs.prefix_bits : EPI == EPI_BAND ? list.cap : 0;
+  const int lds_cap = hist ? stream_hist_lds_cap(hs.nsel, hs.bits) : pos.cap;
   const auto launch = [&](auto dt) {
     return stream_launch<sqdist_stream_h16_kernel<decltype(dt)::value, EPI>, EPI>(
-        sp, pos.cap, stream, static_cast<const unsigned short*>(x.q), static_cast<const unsigned short*>(x.g), x.qq, x.gg, (int)x.m,
-        (int)x.n, (int)x.D, pids.q_pids, pids.g_pids, cap, log2cap, pos.key, pos.idx, pos.npos, pos.hist, sp.tiles_m, sp.U, sp.upw,
-        sp.mode, list.thr, list.list, list.count, acap, cams.q_cams, cams.g_cams, cams.camsets);
+        sp, lds_cap, stream, static_cast<const unsigned short*>(x.q), static_cast<const unsigned short*>(x.g), x.qq, x.gg, (int)x.m,
+        (int)x.n, (int)x.D, pids.q_pids, pids.g_pids, cap, log2cap, hist ? hs.prefix : pos.key, pos.idx, pos.npos, pos.hist,
+        sp.tiles_m, sp.U, sp.upw, sp.mode, list.thr, hist ? hs.out : list.list, list.count, acap, cams.q_cams, cams.g_cams,
+        cams.camsets);
   };
   return dtype == CREID_BF16 ? launch(std::integral_constant<int, CREID_BF16>{}) : launch(std::integral_constant<int, CREID_F16>{});
 }
@@ -377,6 +381,14 @@ int creid_stream_topk_collect_keep_h16(const void* q, const void* g, const float
   return stream_h16_launch<EPI_TOPK_KEEP>({q, g, qq, gg, m, n, D}, dtype, {q_pids, g_pids}, {},
                                           {tau, reinterpret_cast<unsigned long long*>(cand), count, cap},
                                           {q_cams, g_cams, camsets != 0 ? 1 : 0}, stream);
+}
+
+int creid_stream_dist_hist_h16(const void* q, const void* g, const float* qq, const float* gg, int64_t m, int64_t n, int64_t D,
+                               int dtype, const int64_t* q_pids, const int64_t* g_pids, const int64_t* q_cams, const int64_t* g_cams,
+                               int32_t camsets, const uint32_t* prefix, int32_t nsel, int32_t prefix_bits, int32_t bits,
+                               uint64_t* hist, void* stream) {
+  return stream_h16_launch<EPI_HIST>({q, g, qq, gg, m, n, D}, dtype, {q_pids, g_pids}, {}, {}, {q_cams, g_cams, camsets != 0 ? 1 : 0},
+                                     stream, {prefix, nsel, prefix_bits, bits, reinterpret_cast<unsigned long long*>(hist)});
 }
 
 int creid_stream_count_band_h16(const void* q, const void* g, const float* qq, const float* gg, int64_t m, int64_t n, int64_t D,

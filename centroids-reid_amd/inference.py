@@ -193,7 +193,10 @@ def get_similar(embeddings, paths, embeddings_gallery, paths_gallery, topk=0, no
     reid_metric.query_expansion's result with normalize_features=False.  CreidError, before any upload, with
     normalize_features=False: expansion is defined on unit rows.  stats["query_expansion"] holds the options and its stats.
     stats (a dict) receives "path" ("materialised" | "streamed" | "chunked" | "reranked"), topk_stream's counters ("prefilter"
-    among them: what ran) and re_ranking's statistics."""
+    among them: what ran) and re_ranking's statistics.
+    Open-set use ("is this person or item in the gallery at all?"): the returned squared-L2 "distances" compare directly with
+    the `threshold` reid_metric.roc_stream / R1_mAP(roc=...) gives for a false-accept rate on validation data of the same
+    normalisation and compute_dtype -- an entry is accepted iff its distance is STRICTLY below the threshold."""
     rr = rm.rerank_options(reranking)
     if rr is not None and (streamed is True or compute_dtype != torch.float32 or distance_func != "euclidean"):
         raise L.CreidError("get_similar(reranking=...) re-ranks the materialised squared-L2 fp32 matrix: not with streamed=True, "

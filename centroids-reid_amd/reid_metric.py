@@ -401,6 +401,176 @@ def gather_ranked(distmat: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     return torch.gather(distmat, 1, idx.clamp(min=0)).masked_fill_(idx < 0, float("inf"))
 
 
+# --------------------------------------------------------------------------- open-set operating points (TAR @ FAR)
+ROC_DEFAULT_FAR = (1e-4, 1e-3, 1e-2)
+ROC_MAX_RATES = 16
+_ROC_PASSES = ((0, 11), (11, 11), (22, 10))     # (prefix bits, digit bits) of the three radix passes over a 32-bit key
+_ROC_GROUP = 4                                  # targets that share a pass: 4 x 2^11 bins is the LDS table of the kernels
+
+
+def key_to_distance(key):
+    """The fp32 value whose order-preserving key (mono_key of csrc/stream_common.hpp) is `key` (numpy uint32)."""
+    key = np.asarray(key, dtype=np.uint32)
+    bits = np.where(key & np.uint32(0x80000000), key ^ np.uint32(0x80000000), ~key)
+    return bits.astype(np.uint32).view(np.float32)
+
+
+def _hist_args(junk: JunkFilter, m, n, prefix, prefix_bits, bits, out, device):
+    junk.check_shape(m, n)
+    L.require_gpu(junk.q_pids, junk.g_pids, junk.q_cams, junk.g_cams)
+    prefix_bits, bits = int(prefix_bits), int(bits)
+    if prefix_bits == 0:
+        nsel, prefix = 1, None
+    else:
+        if prefix is None:
+            raise L.CreidError("distance_histogram: prefix_bits > 0 needs the selectors' prefixes")
+        if not (isinstance(prefix, torch.Tensor) and prefix.is_cuda and prefix.dtype == torch.int32):
+            p = prefix.cpu().numpy() if isinstance(prefix, torch.Tensor) else np.asarray(prefix)
+            prefix = torch.from_numpy(p.astype(np.uint32).view(np.int32).reshape(-1)).to(device)    # the uint32 words, as int32
+        prefix = prefix.contiguous()
+        nsel = prefix.numel()
+    if not 1 <= bits <= 11 or prefix_bits < 0 or prefix_bits + bits > 32 or nsel < 1 or (nsel << bits) > 8192:
+        raise L.CreidError(f"distance_histogram: bits = {bits}, prefix_bits = {prefix_bits}, {nsel} selectors outside 1 <= bits <= 11, "
+                           "prefix_bits + bits <= 32, selectors x 2^bits <= 8192")
+    shape = (nsel, 2, 1 << bits)
+    if out is None:
+        out = torch.zeros(shape, dtype=torch.int64, device=device)
+    elif tuple(out.shape) != shape or out.dtype != torch.int64 or not out.is_cuda or not out.is_contiguous():
+        raise L.CreidError(f"distance_histogram: out must be a contiguous int64 device tensor {shape}, got {tuple(out.shape)} {out.dtype}")
+    labels = (L.ptr(junk.q_pids), L.ptr(junk.g_pids), L.ptr(junk.q_cams), L.ptr(junk.g_cams), 1 if junk.camsets else 0)
+    return labels, (L.ptr(prefix), nsel, prefix_bits, bits, L.ptr(out), L.stream()), out
+
+
+def distance_histogram(q: torch.Tensor, g: torch.Tensor, junk: JunkFilter, qq=None, gg=None, *, prefix=None, prefix_bits=0, bits=11,
+                       out=None) -> torch.Tensor:
+    """One radix pass over the distance keys of every query x gallery pair the evaluation protocol keeps, with NO m x n matrix
+    (creid_stream_dist_hist[_h16]: the streamed contraction with a counting epilogue).  key(i, j) is the order-preserving
+    32-bit key of the squared L2 distance get_euclidean(q, g, qq, gg) holds for the pair, bit for bit (fp32, bf16 or f16 rows).
+    A pair that is junk (`junk`, the JunkFilter of these rows) counts nowhere; else it is genuine (class 0: the query's pid) or
+    an impostor (class 1).  For selector s the pair counts when prefix_bits == 0 or key >> (32 - prefix_bits) == prefix[s], in
+    bin (key >> (32 - prefix_bits - bits)) & (2^bits - 1).  Returns int64 [nsel, 2, 2^bits] on the device (nsel = len(prefix),
+    1 without prefix bits); with out= the counts are ADDED into it, so calls over chunks of the queries accumulate.  Integer
+    atomics only: two runs, and both work splits, give the same counts.  NaN distances are outside the contract (they are
+    counted under whatever key their bits give)."""
+    L.require_gpu(q, g)
+    if q.dim() != 2 or g.dim() != 2 or q.dtype != g.dtype or q.shape[1] != g.shape[1] or q.dtype not in (torch.float32,) + _H16:
+        raise L.CreidError("distance_histogram needs fp32, bf16 or f16 rows [m, D] and [n, D] of one dtype")
+    qq = row_sqnorm(q) if qq is None else qq
+    gg = row_sqnorm(g) if gg is None else gg
+    m, n, D = q.shape[0], g.shape[0], q.shape[1]
+    labels, tail, out = _hist_args(junk, m, n, prefix, prefix_bits, bits, out, q.device)
+    h16 = q.dtype in _H16
+    name = "creid_stream_dist_hist" + ("_h16" if h16 else "")
+    dt = (L.dtype_code(q),) if h16 else ()
+    L.check(getattr(L.lib(), name)(L.ptr(q), L.ptr(g), L.ptr(qq), L.ptr(gg), m, n, D, *dt, *labels, *tail), name)
+    return out
+
+
+def distance_histogram_matrix(distmat: torch.Tensor, junk: JunkFilter, *, prefix=None, prefix_bits=0, bits=11, out=None) -> torch.Tensor:
+    """distance_histogram over an existing fp32 matrix [m, n] (creid_dist_hist_matrix): the keys of its entries, whatever
+    distance they hold."""
+    L.require_gpu(distmat)
+    if distmat.dtype != torch.float32 or distmat.dim() != 2:
+        raise L.CreidError("distance_histogram_matrix needs a dense fp32 matrix [m, n]")
+    m, n = distmat.shape
+    labels, tail, out = _hist_args(junk, m, n, prefix, prefix_bits, bits, out, distmat.device)
+    L.check(L.lib().creid_dist_hist_matrix(L.ptr(distmat), m, n, *labels, *tail), "creid_dist_hist_matrix")
+    return out
+
+
+def roc_rates(far):
+    """The target false-accept rates of roc_stream / roc_matrix / R1_mAP(roc=...) as a tuple of floats: True = ROC_DEFAULT_FAR;
+    CreidError for a rate outside (0, 1], for none and for more than ROC_MAX_RATES."""
+    if far is True:
+        return ROC_DEFAULT_FAR
+    try:
+        rates = tuple(float(f) for f in ([far] if isinstance(far, (int, float)) and not isinstance(far, bool) else far))
+    except (TypeError, ValueError):
+        raise L.CreidError(f"roc: the target rates must be numbers in (0, 1], got {far!r}") from None
+    if not 1 <= len(rates) <= ROC_MAX_RATES:
+        raise L.CreidError(f"roc: 1 .. {ROC_MAX_RATES} target rates, got {len(rates)}")
+    for f in rates:
+        if not 0.0 < f <= 1.0:                                      # (NaN fails both comparisons)
+            raise L.CreidError(f"roc: target rate {f!r} outside (0, 1]")
+    return rates
+
+
+def _roc_select(pass_fn, far, device, first_hist=None, stats=None):
+    """The radix select behind roc_stream / roc_matrix.  pass_fn(prefix, prefix_bits, bits, out) adds one pass's counts into
+    out; first_hist: the first pass's counts int64 [1, 2, 2048] when the caller has accumulated them already.  Per group of
+    four targets: three passes and three select steps (creid_roc_descend), all enqueued; one read-back at the end."""
+    rates = roc_rates(far)
+    lib = L.lib()
+    pb0, bits0 = _ROC_PASSES[0]
+    hist0 = first_hist
+    launches = 0
+    if hist0 is None:
+        hist0 = torch.zeros((1, 2, 1 << bits0), dtype=torch.int64, device=device)
+        pass_fn(None, pb0, bits0, hist0)
+        launches += 1
+    states = []
+    for t0 in range(0, len(rates), _ROC_GROUP):
+        grp = rates[t0:t0 + _ROC_GROUP]
+        nt = len(grp)
+        far_d = torch.tensor(grp, dtype=torch.float64).to(device)
+        state = torch.zeros((nt, 8), dtype=torch.int64, device=device)
+        prefix = torch.zeros(nt, dtype=torch.int32, device=device)
+        hist = hist0
+        for level, (pb, bits) in enumerate(_ROC_PASSES):
+            if level > 0:
+                hist = torch.zeros((nt, 2, 1 << bits), dtype=torch.int64, device=device)
+                pass_fn(prefix, pb, bits, hist)
+                launches += 1
+            L.check(lib.creid_roc_descend(L.ptr(hist), nt, bits, level, L.ptr(far_d), L.ptr(state), L.ptr(prefix), L.stream()),
+                    "creid_roc_descend")
+        states.append(state)
+    back = torch.cat([s.flatten() for s in states] + [hist0.flatten()]).cpu().numpy()      # the one host synchronisation
+    st = back[:8 * len(rates)].reshape(len(rates), 8)
+    h0 = back[8 * len(rates):].reshape(2, 1 << bits0)
+    if (st[:, 7] & 1).any():
+        raise L.CreidError("roc: no impostor pair (every gallery entry has its query's pid, or the sets are empty): a false-accept "
+                           "rate is undefined")
+    if (st[:, 7] & 2).any() or ((st[:, 7] >> 8) & 0xff != 32).any():
+        raise L.CreidError("roc: the passes' counts do not add up (the distances or labels changed between the passes)")
+    fa, ta, n_imp, n_gen = st[:, 2], st[:, 3], st[:, 4], st[:, 5]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        tar = np.where(n_gen > 0, ta / np.maximum(n_gen, 1).astype(np.float64), np.nan)
+    if stats is not None:
+        stats.update(passes=launches, groups=len(states))
+    edges = key_to_distance(np.arange(1 << bits0, dtype=np.uint32) << np.uint32(32 - bits0))
+    return dict(target=np.asarray(rates, dtype=np.float64), threshold=key_to_distance(st[:, 6].astype(np.uint32)),
+                false_accepts=fa.copy(), true_accepts=ta.copy(), n_impostor=n_imp.copy(), n_genuine=n_gen.copy(),
+                far=fa / n_imp.astype(np.float64), tar=tar, hist=h0.copy(), edges=edges)
+
+
+def roc_stream(q: torch.Tensor, g: torch.Tensor, junk: JunkFilter, far=ROC_DEFAULT_FAR, qq=None, gg=None, *, stats=None) -> dict:
+    """Open-set operating points of a query set against a gallery with NO m x n matrix: for every target false-accept rate f
+    the exact distance threshold, by a three-pass radix select on the keys distance_histogram counts.
+    Pair classes: junk (what `junk` drops: the query's pid seen by its camera, or by a camera set that holds it) belongs to no
+    class; genuine = the same pid and not junk; impostor = another pid.  With N_imp / N_gen the class sizes,
+    k = min(floor(f * N_imp), N_imp - 1) and tau = the impostor distance of 0-based rank k in ascending order, a pair is
+    ACCEPTED iff its distance is STRICTLY below tau, so false_accepts <= k whatever the ties.  Distances compare by the bits
+    get_euclidean(q, g, qq, gg) gives them in the rows' dtype (fp32, bf16 or f16).
+    Returns numpy arrays with one entry per target: target (the rates asked for), threshold (fp32, tau in the matrix's own unit
+    -- SQUARED L2 here), false_accepts, true_accepts, n_impostor, n_genuine (int64), far = false_accepts / N_imp, tar =
+    true_accepts / N_gen (nan when there is no genuine pair); and hist int64 [2, 2048] (genuine, impostor), edges fp32 [2048]:
+    the first pass's counts and the lowest distance of each of its bins (an exact, coarse pair of distributions; the bins of
+    NaN bit patterns have NaN edges).  CreidError when there is no impostor pair, for a rate outside (0, 1] and for more than
+    16 rates.  Up to four targets share the three contractions; the only host synchronisation is the final read-back.  NaN
+    distances are outside the contract."""
+    qq = row_sqnorm(q) if qq is None else qq
+    gg = row_sqnorm(g) if gg is None else gg
+    return _roc_select(lambda prefix, pb, bits, out: distance_histogram(q, g, junk, qq, gg, prefix=prefix, prefix_bits=pb, bits=bits,
+                                                                        out=out), far, q.device, stats=stats)
+
+
+def roc_matrix(distmat: torch.Tensor, junk: JunkFilter, far=ROC_DEFAULT_FAR, *, stats=None) -> dict:
+    """roc_stream over an existing fp32 matrix [m, n] (cosine, re-ranked, or any other distance): the same definitions on its
+    entries; threshold is in the matrix's own unit."""
+    return _roc_select(lambda prefix, pb, bits, out: distance_histogram_matrix(distmat, junk, prefix=prefix, prefix_bits=pb, bits=bits,
+                                                                               out=out), far, distmat.device, stats=stats)
+
+
 STREAM_RESCORE_CAPACITY = 1024        # entries of one query creid_stream_topk_rescore re-scores (RS_CAP, csrc/stream_prefilter.hip)
 _PREFILTER_INFLATE = 2.0 ** -20       # relative inflation of the margin: covers the float64 arithmetic it is computed with
 
@@ -1320,7 +1490,7 @@ class R1_mAP:
 
     def __init__(self, pl_module=None, num_query=0, max_rank=50, feat_norm=True, dist_func="euclidean",
                  compute_dtype=torch.float32, streamed=False, reranking=False, prefilter=None, prefilter_capacity=None,
-                 query_expansion=False, ranked_topk=None):
+                 query_expansion=False, ranked_topk=None, roc=None):
         """streamed=True: metric-only evaluation that never materialises the distance / index matrices (euclidean; plain
         camera ids or, with compute(respect_camids=True), camera sets; compute_dtype fp32, bf16 or f16 -- the 16-bit modes
         run the 16-bit MFMA and return exactly what their materialised evaluation returns); `last` then holds the per-query
@@ -1352,7 +1522,17 @@ class R1_mAP:
         matched bool [nq, K'] (the entry has the query's pid) and count int32 [nq] (the real entries).  On every route and with
         every other option; streamed routes build them with topk_stream(junk=...) on the rows the evaluation multiplied (no
         matrix; with prefilter= too, by the plain streamed kernels), materialised ones with rank_keep_topk on `last["indices"]`.
-        The metrics returned are those of the same call without the keyword."""
+        The metrics returned are those of the same call without the keyword.
+        roc=True (the rates ROC_DEFAULT_FAR = 1e-4, 1e-3, 1e-2) or a tuple of up to 16 false-accept rates in (0, 1] (default
+        None: nothing changes): after the metrics, `last["roc"]` holds the open-set operating points of the evaluation's own
+        distances -- the dict of roc_stream: per rate the exact threshold (in the unit of the route's matrix: squared L2 on the
+        euclidean routes), false / true accepts under the STRICT test distance < threshold, the class sizes, far and tar, and
+        the first pass's genuine / impostor histograms.  Junk pairs belong to no class.  On every route and with every other
+        option: streamed routes run roc_stream on the rows and norms the evaluation multiplied (no matrix; with prefilter= by the
+        plain fp32 kernels), materialised ones roc_matrix on their own `distmat` (cosine, re-ranked, streamed=False); the cosine
+        loop of compute_chunked counts the first pass chunk by chunk and forms every chunk's matrix again for the two later
+        passes.  The metrics returned are those of the same call without the keyword, bit for bit."""
+        self.roc = None if roc is None or roc is False else roc_rates(roc)
         if ranked_topk is not None and not (_is_int(ranked_topk) and 1 <= ranked_topk <= 1024):
             raise L.CreidError(f"R1_mAP(ranked_topk=...) must be an int, 1 .. 1024, got {ranked_topk!r}")
         self.ranked_topk = None if ranked_topk is None else int(ranked_topk)
@@ -1426,6 +1606,10 @@ class R1_mAP:
         idx, matched, count = rank_keep_topk(indices, min(self.ranked_topk, indices.shape[1]), junk)
         return dict(indices=idx, distances=gather_ranked(distmat, idx), matched=matched, count=count)
 
+    def _roc_from_matrix(self, distmat, junk):
+        """The materialised routes' `last["roc"]`: the operating points of their own matrix."""
+        return roc_matrix(distmat, junk, self.roc)
+
     def compute(self, feats, pids, camids, respect_camids=False):
         if not isinstance(feats, torch.Tensor) or not feats.is_cuda:
             raise L.CreidError("R1_mAP.compute needs device features (no CPU fallback)")
@@ -1451,6 +1635,9 @@ class R1_mAP:
             if self.ranked_topk is not None:
                 self.last["ranked"] = self._ranked_from_indices(
                     indices, distmat, JunkFilter.from_labels(pids, camids, nq, feats.device, respect_camids=True))
+            if self.roc is not None:
+                self.last["roc"] = self._roc_from_matrix(
+                    distmat, JunkFilter.from_labels(pids, camids, nq, feats.device, respect_camids=True))
             self._keep_expansion_info()
             return cmc, mAP, all_topk
         # np.argsort + eval_func's per-query loop in ONE pass: the ranked rows are evaluated while they are still in LDS
@@ -1465,6 +1652,8 @@ class R1_mAP:
         self.last = dict(distmat=distmat, indices=indices, single_performance=single, valid=valid, ap=ap, first=first)
         if self.ranked_topk is not None:
             self.last["ranked"] = self._ranked_from_indices(indices, distmat, JunkFilter.from_labels(pids, camids, nq, feats.device))
+        if self.roc is not None:
+            self.last["roc"] = self._roc_from_matrix(distmat, JunkFilter.from_labels(pids, camids, nq, feats.device))
         self._keep_expansion_info()
         return cmc_h, mAP_h, topk_h
 
@@ -1569,6 +1758,10 @@ class R1_mAP:
             ridx, rdist = topk_stream(fq, fg, min(self.ranked_topk, fg.shape[0]), qq, gg, junk=junk)
             self.last["ranked"] = dict(indices=ridx, distances=rdist, matched=junk.matched(ridx),
                                        count=(ridx >= 0).sum(1, dtype=torch.int32))
+        if self.roc is not None:
+            # the operating points of the distances the metrics above rank by, from the same rows and norms: no matrix either
+            junk = JunkFilter(plan.q_pids, plan.q_cams, plan.g_pids, plan.g_cams, camsets=plan.camsets)
+            self.last["roc"] = roc_stream(fq, fg, junk, self.roc, qq, gg)
         self._keep_expansion_info()
         return cmc_h, mAP_h, topk_h
 
@@ -1601,20 +1794,34 @@ class R1_mAP:
         dev = feats.device
         gp, gc = _dev_i64(pids[nq:], dev), _dev_i64(camids[nq:], dev)
         vs, aps, firsts = [], [], []
-        junk = JunkFilter.from_labels(pids, camids, nq, dev) if self.ranked_topk is not None else None
+        junk = JunkFilter.from_labels(pids, camids, nq, dev) if self.ranked_topk is not None or self.roc is not None else None
         ranked = []
+        chunk_dist = lambda lo, hi: (get_euclidean(f[lo:hi], g, sq[lo:hi].contiguous(), gg) if euclid
+                                     else self.dist_func(f[lo:hi].contiguous(), g))
+        roc_hist0 = torch.zeros((1, 2, 1 << _ROC_PASSES[0][1]), dtype=torch.int64, device=dev) if self.roc is not None else None
         for lo in range(0, nq, query_chunk):
             hi = min(nq, lo + query_chunk)
-            d = get_euclidean(f[lo:hi], g, sq[lo:hi].contiguous(), gg) if euclid else self.dist_func(f[lo:hi].contiguous(), g)
+            d = chunk_dist(lo, hi)
             idx = rank_rows(d)
-            if junk is not None:                                  # per chunk, before its matrix and indices are freed
+            if self.ranked_topk is not None:                      # per chunk, before its matrix and indices are freed
                 ranked.append(self._ranked_from_indices(idx, d, junk.rows(slice(lo, hi))))
+            if roc_hist0 is not None:                             # the first radix pass rides along
+                distance_histogram_matrix(d, junk.rows(slice(lo, hi)), bits=_ROC_PASSES[0][1], out=roc_hist0)
             del d
             _, _, _, _, v, a, fr = eval_func_device(idx, pids[lo:hi], gp, camids[lo:hi], gc, self.max_rank)
             vs.append(v); aps.append(a); firsts.append(fr)
             del idx
         v = torch.cat(vs).cpu().numpy() > 0; a = torch.cat(aps).cpu().numpy(); fr = torch.cat(firsts).cpu().numpy()
         if junk is not None:
-            self.last = dict(ranked={key: torch.cat([r[key] for r in ranked]) for key in ranked[0]})
+            self.last = {}
+        if self.ranked_topk is not None:
+            self.last["ranked"] = {key: torch.cat([r[key] for r in ranked]) for key in ranked[0]}
+        if self.roc is not None:
+            def later_pass(prefix, pb, bits, out):                # the two later passes: every chunk's matrix once more
+                for lo in range(0, nq, query_chunk):
+                    hi = min(nq, lo + query_chunk)
+                    distance_histogram_matrix(chunk_dist(lo, hi), junk.rows(slice(lo, hi)), prefix=prefix, prefix_bits=pb, bits=bits,
+                                              out=out)
+            self.last["roc"] = _roc_select(later_pass, self.roc, dev, first_hist=roc_hist0)
         self._keep_expansion_info()
         return merge_eval_results(v, a, fr, min(self.max_rank, g.shape[0]))

@@ -259,6 +259,45 @@ int creid_rank_keep_topk(const int64_t* idx, int64_t m, int64_t n, int64_t ng, i
 int creid_junk_mask_rows(float* dist, int64_t m, int64_t n, int64_t ld, const int64_t* q_pids, const int64_t* g_pids,
                          const int64_t* q_cams, const int64_t* g_cams, int32_t camsets, void* stream);
 
+/* ---- open-set operating points (TAR @ FAR) with NO m x n matrix (csrc/stream_consume.hpp EPI_HIST, csrc/roc.hip): a radix
+ * select over key(i, j), the order-preserving 32-bit key of the distance (sign bit set: key = bits ^ 0xffffffff, else
+ * bits ^ 0x80000000).  Pair (i, j) is junk as for the ranked lists above (q_pids / g_pids / q_cams / g_cams / camsets: the same
+ * arrays and the same caller-side camera check) and counts nowhere; else it is genuine (class 0: the same pid) or an impostor
+ * (class 1: another pid).
+ *  hist passes: hist uint64 [nsel][2][2^bits]; for selector s a non-junk pair counts when prefix_bits == 0 or
+ *            key >> (32 - prefix_bits) == prefix[s] (uint32 [nsel] on the device; may be NULL without prefix bits), in bin
+ *            (key >> (32 - prefix_bits - bits)) & (2^bits - 1) of hist[s][class].  The call ADDS into hist: the caller zeroes
+ *            it, and calls over chunks of the queries accumulate.  Integer atomics only: the counts depend on nothing but the
+ *            keys.  1 <= bits <= 11, prefix_bits + bits <= 32, 1 <= nsel, nsel << bits <= 8192, nsel == 1 without prefix bits,
+ *            else CREID_E_SHAPE.  NaN distances are counted under whatever key their bits give.
+ *            creid_stream_dist_hist / _h16: the keys of the distances creid_stream_count / _h16 forms from the same rows
+ *            (the bits of creid_sqdist_matrix of the same dtype), with those entry points' limits on D, m, n and dtype; every
+ *            refusal of a shape or dtype comes first, then m == 0 returns 0, then the pointer checks.
+ *            creid_dist_hist_matrix: the keys of an existing dense fp32 matrix dist [m][n].
+ *  creid_roc_descend: the select step after a pass, one workgroup per target t < nsel (the first pass, level == 0, has one
+ *            selector that every target reads; later passes selector t).  state int64 [nsel][8] = { rank left inside the
+ *            prefix, prefix, impostors below, genuines below, N_imp, N_gen, lowest key of the prefix, flags }.  level == 0
+ *            initialises it: N_imp / N_gen = the class totals, rank k = min(floor(far[t] * N_imp), N_imp - 1) (far float64
+ *            [nsel] on the device; the one floating-point operation).  Every level walks the impostor counts to the digit that
+ *            holds the rank, adds the counts of both classes below it, appends the digit to the prefix and writes prefix[t]
+ *            for the next pass.  Once the passes' bits add up to 32 the key slot is the impostor key of 0-based rank k, and
+ *            the two counts are the impostor / genuine keys STRICTLY below it.  flags bit 0: N_imp == 0; bit 1: the counts do
+ *            not hold the rank (hist is not this state's pass); bits 8..15: the key bits fixed so far.  No host
+ *            synchronisation. */
+int creid_stream_dist_hist(const float* q, const float* g, const float* qq, const float* gg, int64_t m, int64_t n, int64_t D,
+                           const int64_t* q_pids, const int64_t* g_pids, const int64_t* q_cams, const int64_t* g_cams,
+                           int32_t camsets, const uint32_t* prefix, int32_t nsel, int32_t prefix_bits, int32_t bits,
+                           uint64_t* hist, void* stream);
+int creid_stream_dist_hist_h16(const void* q, const void* g, const float* qq, const float* gg, int64_t m, int64_t n,
+                               int64_t D, int dtype, const int64_t* q_pids, const int64_t* g_pids, const int64_t* q_cams,
+                               const int64_t* g_cams, int32_t camsets, const uint32_t* prefix, int32_t nsel,
+                               int32_t prefix_bits, int32_t bits, uint64_t* hist, void* stream);
+int creid_dist_hist_matrix(const float* dist, int64_t m, int64_t n, const int64_t* q_pids, const int64_t* g_pids,
+                           const int64_t* q_cams, const int64_t* g_cams, int32_t camsets, const uint32_t* prefix,
+                           int32_t nsel, int32_t prefix_bits, int32_t bits, uint64_t* hist, void* stream);
+int creid_roc_descend(const uint64_t* hist, int32_t nsel, int32_t bits, int32_t level, const double* far, int64_t* state,
+                      uint32_t* prefix, void* stream);
+
 /* ---- exact fp32 top-k with the contraction on the 16-bit MFMA (csrc/stream_prefilter.hip): the 16-bit streamed contraction
  * only pre-filters, with a proven margin; the pairs it keeps are re-scored with the fp32 kernels' arithmetic, so the result has
  * the indices and the distance bits of creid_stream_topk_collect + creid_stream_topk_select on the fp32 rows.
