@@ -120,6 +120,7 @@ SIGNATURES = {
     "creid_conv2d_bn_partial_rows": (_i64, [_p]),
     "creid_igemm_halo_launches": (_i64, []),
     "creid_wgrad_taps_launches": (_i64, []),
+    "creid_conv_route_describe": (C.c_int, [_p, C.c_int, C.c_int, C.c_int, _p, _sz]),
     "creid_conv2d_fwd_nhwc": (C.c_int, [_p, _p, _p, _p, _p, C.c_int, _p]),
     "creid_conv2d_fwd_affine_nhwc": (C.c_int, [_p, _p, _p, _p, _p, _p, C.c_int, C.c_int, _p]),
     "creid_conv1x1_bnrelu_fwd": (C.c_int, [_p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, C.c_int, _p]),

@@ -20,23 +20,8 @@
 #include "conv_epilogue.hpp"
 #include <type_traits>
 #include <atomic>
-#include "wgrad_reduce.hpp"
-#include "tune.hpp"
+#include "conv_route.hpp"
 #include <stdlib.h>
-
-// defined in conv_wgrad.hip
-bool wgrad_make_reduce_job(const creid_conv_desc* d, int dtype, const void* ws, size_t ws_bytes, float* dw, int accumulate,
-                           WRedJob& j);
-int wgrad_reduce_job_launch(const WRedJob& j, hipStream_t s);
-// defined in conv_stream.hip
-int launch_stream1x1(int M, int K, int N, const void* src, const void* wgt, void* out, float* bn_part, hipStream_t s);
-int launch_stream2(int M, int K, int N, const void* src, const void* wgt, void* out, float* bn_part, const void* add_src,
-                   const float* epi_scale, const float* epi_shift, int epi_relu, int bn_cap, int dtype, hipStream_t s);
-int launch_conv3x3_c64(int M, int H, int Wd, const void* src, const void* wgt, void* out, float* bn_part, const float* epi_scale,
-                       const float* epi_shift, int epi_relu, int dtype, hipStream_t s);
-// defined in conv_pipe.hip
-int launch_igemm_pp(const IGemmGeom& g, const void* src, const void* wgt, void* out, const void* add_src, float* bn_part,
-                    int variant, int dtype, hipStream_t s);
 
 // Out-of-image taps read this 128-byte page of zeros instead of selecting zeros per dword (saves 3 VALU
 // per load in the gather path).
@@ -1170,14 +1155,49 @@ __global__ __launch_bounds__(256) void igemm_f32_kernel(IGemmGeom g, const float
 }
 
 // ------------------------------------------------------------------------------------ host
-static int use_dma_env() {
-  static const int v = [] { const char* e = getenv("CREID_IGEMM_DMA"); return e ? atoi(e) : 1; }();
-  return v;
+// Every switch of the forward / data-gradient dispatch, gathered here and nowhere else.  CREID_KNOB_ENV ones: read once in
+// production, per call under CREID_DEBUG_KNOBS=1 (tests, the tuner and the probes flip them inside one process); the rest once.
+static int env_int(const char* e, int dflt) { return e ? atoi(e) : dflt; }
+static int env_pos(const char* name, int dflt) { const int v = env_int(getenv(name), 0); return v > 0 ? v : dflt; }
+int conv_stem_dma_env() { static const int v = env_int(getenv("CREID_STEM_DMA"), 1); return v; }
+
+static IGemmKnobs read_igemm_knobs() {
+  IGemmKnobs k{};
+#ifdef CREID_ABL_BUILD
+  k.abl = env_int(CREID_KNOB_ENV("CREID_IGEMM_ABL"), 0);                  // per call: the probes sweep it inside one process
+  { static int warned = -1; if (k.abl && k.abl != warned) { warned = k.abl; creid_ablation_env("CREID_IGEMM_ABL"); } }
+  k.c64_abl = env_int(CREID_KNOB_ENV("CREID_C64_ABL"), 0);
+  static const int stream2_abl = creid_ablation_env("CREID_STREAM2_ABL");
+  k.stream2_abl = stream2_abl;
+#endif
+  k.c64_on = env_int(CREID_KNOB_ENV("CREID_C64_3X3"), 1) != 0;
+  const char* pe = CREID_KNOB_ENV("CREID_IGEMM_PP");
+  k.force_pp = pe ? (int)strtol(pe, nullptr, 0) : 0;
+  k.pp_off = pe && k.force_pp == 0;                                     // CREID_IGEMM_PP=0: never, not even where a plan selects it
+  k.pp_wgs = env_int(CREID_KNOB_ENV("CREID_PP_WGS"), 0);
+  k.force_stream1 = env_int(CREID_KNOB_ENV("CREID_STREAM1X1"), 0);
+  k.force_stream2 = env_int(CREID_KNOB_ENV("CREID_STREAM2"), 0);
+  k.stream2_bn = env_int(CREID_KNOB_ENV("CREID_STREAM2_BN"), 0);
+  k.stream_wgs = env_int(CREID_KNOB_ENV("CREID_STREAM1X1_WGS"), 0);
+  k.stream1_dbg = env_int(CREID_KNOB_ENV("CREID_STREAM1X1_DBG"), 0);
+  k.force_bm = env_int(CREID_KNOB_ENV("CREID_IGEMM_BM"), 0);
+  k.halo_on = env_int(CREID_KNOB_ENV("CREID_IGEMM_HALO"), 1) != 0;
+  static const int min_wgs = env_pos("CREID_IGEMM_BN128_MIN_WGS", 384), use_dma = env_int(getenv("CREID_IGEMM_DMA"), 1),
+                   use_ws = env_int(getenv("CREID_IGEMM_WS"), 1), ws_min_k = env_pos("CREID_IGEMM_WS_MIN_K", 1024),
+                   parity_on = env_int(getenv("CREID_DGRAD_PARITY"), 1), bm256_min = env_pos("CREID_IGEMM_BM256_MIN_WGS", 256);
+  static const int ws_stages = [] { const int x = env_int(getenv("CREID_IGEMM_WS_STAGES"), 0); return (x == 2 || x == 4) ? x : 3; }();
+  static const int stages = [] { const int v = env_int(getenv("CREID_IGEMM_STAGES"), 0); return (v >= 2 && v <= 5) ? v : 2; }();
+  k.min_wgs = min_wgs; k.use_dma = use_dma; k.use_ws = use_ws; k.ws_min_k = ws_min_k; k.parity_on = parity_on;
+  k.bm256_min = bm256_min; k.ws_stages = ws_stages; k.stages = stages;
+  return k;
 }
 
-static int ws_stages_env() {
-  static const int v = [] { const char* e = getenv("CREID_IGEMM_WS_STAGES"); int x = e ? atoi(e) : 0; return (x == 2 || x == 4) ? x : 3; }();
-  return v;
+const IGemmKnobs& conv_igemm_knobs() {
+  static const IGemmKnobs once = read_igemm_knobs();
+  if (!creid_knobs_live()) return once;
+  static thread_local IGemmKnobs live;
+  live = read_igemm_knobs();
+  return live;
 }
 
 // What igemm_bf16_halo_kernel covers: 3x3, stride 1, pad 1 (forward or transposed) over C = 64 | 128 | 256 channels per tap,
@@ -1196,231 +1216,217 @@ static bool igemm_halo_covers(const IGemmGeom& g, int bn, int stages) {
 }
 static std::atomic<long long> g_halo_launches{0};
 
-static int launch_igemm(const IGemmGeom& g_in, const void* src, const void* wgt, void* out, const void* add_src,
-                        float* bn_part, int dtype, hipStream_t s, BnRedArgs bnred = BnRedArgs{},
-                        const WRedJob* wred_in = nullptr) {
-#ifdef CREID_ABL_BUILD
-  const char* abl_e = CREID_KNOB_ENV("CREID_IGEMM_ABL");                  // per call: the probes sweep it inside one process
-  const int abl_env = abl_e ? atoi(abl_e) : 0;
-  { static int warned = -1; if (abl_env && abl_env != warned) { warned = abl_env; creid_ablation_env("CREID_IGEMM_ABL"); } }
-#else
-  const int abl_env = 0;
-#endif
-  if (!creid_is_storage(dtype)) return CREID_E_DTYPE;     // (CREID_BF16X3 forward convolutions go to launch_igemm_x3)
-  IGemmGeom g = g_in;
-  g.abl = abl_env;
-  WRedJob wred{};
-  if (wred_in) wred = *wred_in;
-  static_assert(sizeof(float) * (4 * 512 + 8192) <= 2 * (128 + 64) * 64 * 2, "reduce scratch must fit the smallest LDS ring");
+static ConvRoute conv_refuse(ConvRoute r, int err) { r.family = CONV_NONE; r.err = err; return r; }
+
+// Which kernel runs a forward convolution or a data gradient, in precedence order.
+ConvRoute route_igemm(const IGemmGeom& g, const ConvFeat& f, const IGemmKnobs& k, bool peek) {
+  ConvRoute r;
+  const int dtype = r.dtype = f.dtype;
+  if (!creid_is_storage(dtype)) return conv_refuse(r, CREID_E_DTYPE);     // (CREID_BF16X3 forward convolutions go to launch_igemm_x3)
+  const bool is16 = creid_is16(dtype);
   const int tiles_m = (g.M + 127) / 128;
   // pick the N tile: 128 unless that leaves the chip (256 CUs) under-filled or N is only 64
   int bn = 128;
-  static const int min_wgs = [] { const char* e = getenv("CREID_IGEMM_BN128_MIN_WGS"); int v = e ? atoi(e) : 0; return v > 0 ? v : 384; }();
-  if (g.N % 128 != 0 || (int64_t)tiles_m * (g.N / 128) < min_wgs) bn = 64;
+  if (g.N % 128 != 0 || (int64_t)tiles_m * (g.N / 128) < k.min_wgs) bn = 64;
   // measured plan for this GEMM shape (tune.hpp): N tile and ring depth of the producer/consumer kernel; the 4th key slot is
-  // transposed | stride << 1 (a stride-2 and a stride-1 3x3 layer can share M, N, K but not their gather pattern)
+  // transposed | stride << 1 (a stride-2 and a stride-1 3x3 layer can share M, N, K but not their gather pattern).  Folded
+  // eval-mode launches look for a plan measured with THAT epilogue first: key bit 3; plans recorded before the bit existed carry
+  // no mode and serve both.
   TunePlan tp;
   int tuned_stages = 0, tuned_dma = 0, tuned_stream = 0, tuned_bm256 = 0, tuned_stream2 = 0, tuned_pp = -1;
-  // (folded eval-mode launches -- epi_scale set -- look for a plan measured with THAT epilogue first: key bit 3; plans recorded
-  // before the bit existed carry no mode and serve both)
+  const auto lookup = peek ? creid_tune_peek : creid_tune_lookup;
   const int plan_d = g.transposed | (g.stride << 1);
-  const bool plan_eval = creid_is16(dtype) && g.epi_scale && creid_tune_lookup(CREID_TUNE_IGEMM, g.M, g.N, g.K, plan_d | 8, tp);
-  const bool have_plan = plan_eval || (creid_is16(dtype) && creid_tune_lookup(CREID_TUNE_IGEMM, g.M, g.N, g.K, plan_d, tp));
-  // the plan's kernel (tp.p2) once its word passed the checks below, else -1; `ran` records a launch that found a plan and took
-  // another kernel (creid_tune_count, what = 1).  Kernel ids: the plan kinds 0..5, 6 = the 3 x 3 c64 kernel, -2 = the rest.
-  int planned = -1;
-  auto ran = [&](int kernel) {
-    if (have_plan && kernel != planned) creid_tune_declined(CREID_TUNE_IGEMM, g.M, g.N, g.K, plan_eval ? (plan_d | 8) : plan_d);
-  };
-  if (have_plan && dtype == CREID_F16 && tp.p2 == 2) {
+  const bool plan_eval = is16 && f.affine && lookup(CREID_TUNE_IGEMM, g.M, g.N, g.K, plan_d | 8, tp);
+  r.have_plan = plan_eval || (is16 && lookup(CREID_TUNE_IGEMM, g.M, g.N, g.K, plan_d, tp));
+  r.plan_key = plan_eval ? (plan_d | 8) : plan_d;
+  if (r.have_plan && dtype == CREID_F16 && tp.p2 == 2) {
     // (the first persistent 1x1 kernel of conv_stream.hip is bf16 only: f16 launches of those shapes take the built-in rule)
-  } else if (have_plan && tp.p2 == 5) {
+  } else if (r.have_plan && tp.p2 == 5) {
     tuned_pp = tp.p0;                                              // plan kind 5: all-waves-multiply persistent kernel, p0 = its variant word
-    planned = 5;
-  } else if (have_plan && (tp.p0 == 64 || tp.p0 == 128) && g.N % tp.p0 == 0 && (tp.p1 == 2 || tp.p1 == 3 || tp.p1 == 4)) {
+    r.planned = 5;
+  } else if (r.have_plan && (tp.p0 == 64 || tp.p0 == 128) && g.N % tp.p0 == 0 && (tp.p1 == 2 || tp.p1 == 3 || tp.p1 == 4)) {
     bn = tp.p0; tuned_stages = tp.p1; tuned_dma = tp.p2 == 1; tuned_stream = tp.p2 == 2; tuned_bm256 = tp.p2 == 3; tuned_stream2 = tp.p2 == 4;
-    planned = (tp.p2 >= 1 && tp.p2 <= 4) ? tp.p2 : 0;            // (any other word: the producer/consumer kernel)
+    r.planned = (tp.p2 >= 1 && tp.p2 <= 4) ? tp.p2 : 0;          // (any other word: the producer/consumer kernel)
   }
-  // layer1's 3 x 3, 64 -> 64 forward: halo tile in LDS, weights in registers (conv_stream.hip conv3x3_c64_kernel); CREID_C64_3X3=0:
-  // the tile kernels
-  {
-    const char* ce = CREID_KNOB_ENV("CREID_C64_3X3");                       // read per call: tests toggle it
-    const bool c64_on = !ce || atoi(ce) != 0;
-    if (c64_on && creid_is16(dtype) && !g.transposed && g.N == 64 && g.K == 576 && g.log2span == 6 && g.kw == 3 && g.stride == 1 &&
-        g.pad == 1 && g.pitch == 64 && g.check_bounds && !add_src && !bnred.x && !wred.ws && g.SH == g.OH && g.SW == g.OW &&
-        !(bn_part && g.epi_scale)) {
-      const int rc = launch_conv3x3_c64(g.M, g.OH, g.OW, src, wgt, out, bn_part, g.epi_scale, g.epi_shift, g.epi_relu, dtype, s);
-      if (rc != CREID_E_SHAPE) { ran(6); return rc; }
-    }
+  const bool no_jobs = !f.bnred && !f.wred;
+  // layer1's 3 x 3, 64 -> 64 forward: halo tile in LDS, weights in registers (conv_stream.hip); CREID_C64_3X3=0: the tile kernels
+  if (k.c64_on && is16 && !g.transposed && g.N == 64 && g.K == 576 && g.log2span == 6 && g.kw == 3 && g.stride == 1 && g.pad == 1 &&
+      g.pitch == 64 && g.check_bounds && !f.add_src && no_jobs && g.SH == g.OH && g.SW == g.OW && !(f.stats && f.affine) &&
+      conv3x3_c64_route(g, f, k, r)) {
+    r.kernel_id = 6;
+    return r;
   }
   // all-waves-multiply persistent kernel (conv_pipe.hip): plan kind 5, or CREID_IGEMM_PP = 0x1000 | variant for every launch it covers
-  {
-    const char* pe = CREID_KNOB_ENV("CREID_IGEMM_PP");                     // read per call: tests and the tuner toggle it
-    const int force_pp = pe ? (int)strtol(pe, nullptr, 0) : 0;
-    const bool pp_off = pe && force_pp == 0;                              // CREID_IGEMM_PP=0: never, not even where a plan selects it
-    if (creid_is16(dtype) && !bnred.x && !wred.ws && g.log2span >= 6 && !pp_off && (force_pp || tuned_pp >= 0)) {
-      const int rc = launch_igemm_pp(g, src, wgt, out, add_src, bn_part, force_pp ? (force_pp & 0xfff) : tuned_pp, dtype, s);
-      if (rc != CREID_E_SHAPE) { ran(force_pp ? -2 : 5); return rc; }
-    }
+  if (is16 && no_jobs && g.log2span >= 6 && !k.pp_off && (k.force_pp || tuned_pp >= 0) &&
+      igemm_pp_route(g, f, k.force_pp ? (k.force_pp & 0xfff) : tuned_pp, k, r)) {
+    r.kernel_id = k.force_pp ? -2 : 5;
+    return r;
   }
-  // persistent streaming kernel for the small-K 1x1 stride-1 forward convolutions (conv_stream.hip): plan kind 2, or
-  // CREID_STREAM1X1=1 for every GEMM it covers
-  {
-    const char* fe = CREID_KNOB_ENV("CREID_STREAM1X1");                    // read per call: tests toggle it
-    const int force_stream = fe ? atoi(fe) : 0;
-    const bool plain_1x1 = dtype == CREID_BF16 && !g.transposed && g.K == (1 << g.log2span) && g.stride == 1 && g.pad == 0 &&
-                           g.kw == 1 && g.check_bounds && !add_src && !bnred.x && !wred.ws && g.pitch == g.K && !g.epi_scale;
-    if (plain_1x1 && (force_stream || tuned_stream)) {
-      const int rc = launch_stream1x1(g.M, g.K, g.N, src, wgt, out, bn_part, s);
-      if (rc != CREID_E_SHAPE) { ran(tuned_stream ? 2 : -2); return rc; }
-    }
-    // second form (plan kind 4 / CREID_STREAM2=1): also the folded eval-mode epilogue with the block's residual
-    const char* f2 = CREID_KNOB_ENV("CREID_STREAM2");
-    const int force2 = f2 ? atoi(f2) : 0;
-    const bool fwd_1x1 = creid_is16(dtype) && !g.transposed && g.K == (1 << g.log2span) && g.stride == 1 && g.pad == 0 &&
-                         g.kw == 1 && g.check_bounds && !bnred.x && !wred.ws && g.pitch == g.K && !g.add_compact && !g.add_mask &&
-                         !(bn_part && (g.epi_scale || add_src));
-    if (fwd_1x1 && (force2 || tuned_stream2)) {
-      // (plan: p1 = 2 -> widest column slab the LDS allows, 3 -> at most 128 columns, 4 -> 64)
-      const int cap = tuned_stream2 ? (tuned_stages == 3 ? 128 : (tuned_stages == 4 ? 64 : 0)) : 0;
-      const int rc = launch_stream2(g.M, g.K, g.N, src, wgt, out, bn_part, add_src, g.epi_scale, g.epi_shift, g.epi_relu, cap, dtype, s);
-      if (rc != CREID_E_SHAPE) { ran(tuned_stream2 ? 4 : -2); return rc; }
-    }
+  // persistent streaming kernels for the small-K 1x1 stride-1 forward convolutions (conv_stream.hip).  First form: plan kind 2, or
+  // CREID_STREAM1X1=1 for every GEMM it covers (bf16, plain epilogue).  Second form (plan kind 4 / CREID_STREAM2=1): also the folded
+  // eval-mode epilogue with the block's residual; the plan's p1 = 2 -> widest column slab the LDS allows, 3 -> at most 128, 4 -> 64
+  const bool fwd_1x1 = !g.transposed && g.K == (1 << g.log2span) && g.stride == 1 && g.pad == 0 && g.kw == 1 && g.check_bounds &&
+                       no_jobs && g.pitch == g.K;
+  if (fwd_1x1 && dtype == CREID_BF16 && !f.add_src && !f.affine && (k.force_stream1 || tuned_stream) && stream1_route(g, k, r)) {
+    r.kernel_id = tuned_stream ? 2 : -2;
+    return r;
   }
-  if (g.N % bn != 0) return CREID_E_SHAPE;
-  const int tiles_n = g.N / bn;
-  const dim3 grid((unsigned)(tiles_m * tiles_n)), block(256);
-  const int use_dma = use_dma_env();
-  const bool stem_geom = g.log2span == 5 && !g.transposed && !g.check_bounds && g.kw == 1 && g.stride == 2 && g.pad == 0;
-  static const int stem_dma = [] { const char* e = getenv("CREID_STEM_DMA"); return e ? atoi(e) : 1; }();
-  if (creid_is16(dtype) && use_dma && (g.log2span >= 6 || (stem_geom && stem_dma))) {
-    if (g.K % 64 != 0) return CREID_E_SHAPE;
-    static const int use_ws = [] { const char* e = getenv("CREID_IGEMM_WS"); return e ? atoi(e) : 1; }();
-
+  if (fwd_1x1 && is16 && !f.add_compact && !f.add_mask && !(f.stats && (f.affine || f.add_src)) && (k.force_stream2 || tuned_stream2) &&
+      stream2_route(g, tuned_stream2 ? (tuned_stages == 3 ? 128 : (tuned_stages == 4 ? 64 : 0)) : 0, k, r)) {
+    r.kernel_id = tuned_stream2 ? 4 : -2;
+    return r;
+  }
+  if (g.N % bn != 0) return conv_refuse(r, CREID_E_SHAPE);
+  r.bn = bn; r.tiles_m = tiles_m; r.tiles_n = g.N / bn;
+  r.grid = (unsigned)(tiles_m * r.tiles_n); r.block = 256;
+  if (is16 && k.use_dma && (g.log2span >= 6 || conv_is_stem_geom(g))) {
+    if (g.K % 64 != 0) return conv_refuse(r, CREID_E_SHAPE);
     // Producer / consumer split everywhere (single-stream step, r01: +4 % from the long-k 64-wide tiles with a
     // 3-deep ring, +2.4 % more from 2-deep rings -- two workgroups per CU -- on all other tiles; standalone sweeps in
     // profiles/r01_igemm_ws_sweep.md).  CREID_IGEMM_WS=0: the 4-wave DMA kernel; =2: force CREID_IGEMM_WS_STAGES.
-    static const int ws_min_k = [] { const char* e = getenv("CREID_IGEMM_WS_MIN_K"); int v = e ? atoi(e) : 0; return v > 0 ? v : 1024; }();
-    if (g.log2span >= 6 && use_ws >= 1 && !(tuned_dma && !wred.ws && !bnred.x)) {
+    if (g.log2span >= 6 && k.use_ws >= 1 && !(tuned_dma && no_jobs)) {
       // stride-2 3x3 data gradients: parity-class row order, 9 tap-tiles per 4 output pixels instead of 36
-      static const int parity_on = [] { const char* e = getenv("CREID_DGRAD_PARITY"); return e ? atoi(e) : 1; }();
-      IGemmGeom gp = g;
-      if (parity_on && g.transposed && g.stride == 2 && g.kw == 3 && g.pad == 1 && (g.K >> g.log2span) == 9 &&
-          g.OH % 2 == 0 && g.OW % 2 == 0 && (g.M / 4) % 128 == 0 && !g.add_compact && bnred.tiles_per_image == 0)
-        gp.parity = 1;
-      int ws_stages = use_ws == 2 ? ws_stages_env() : ((bn == 64 && g.K >= ws_min_k) ? 3 : 2);
-      if (tuned_stages && use_ws != 2) ws_stages = tuned_stages;
-      const dim3 block_ws(512);
+      if (k.parity_on && g.transposed && g.stride == 2 && g.kw == 3 && g.pad == 1 && (g.K >> g.log2span) == 9 &&
+          g.OH % 2 == 0 && g.OW % 2 == 0 && (g.M / 4) % 128 == 0 && !f.add_compact && f.tiles_per_image == 0)
+        r.parity = 1;
+      int ws_stages = k.use_ws == 2 ? k.ws_stages : ((bn == 64 && g.K >= k.ws_min_k) ? 3 : 2);
+      if (tuned_stages && k.use_ws != 2) ws_stages = tuned_stages;
+      r.block = 512;
+      r.wred_rides = f.wred;
+      const unsigned ride = f.wred ? (unsigned)f.wred_nblocks : 0u;
       // 256-row tiles (128 x 64 consumer sub-tiles, one workgroup per CU): plan kind 3, or CREID_IGEMM_BM=256 wherever the grid
       // still has >= CREID_IGEMM_BM256_MIN_WGS (default 256) workgroups; not with the fused BN reduction / parity-class rows
-      {
-        const char* be = CREID_KNOB_ENV("CREID_IGEMM_BM");                 // read per call: tests and the tuner toggle it
-        const int force_bm = be ? atoi(be) : 0;
-        static const int bm256_min = [] { const char* e = getenv("CREID_IGEMM_BM256_MIN_WGS"); int v = e ? atoi(e) : 0; return v > 0 ? v : 256; }();
-        const bool can256 = g.N % 128 == 0 && !bnred.x && !gp.parity;
-        const int64_t wgs256 = (int64_t)((g.M + 255) / 256) * (g.N / 128);
-        if (can256 && force_bm != 128 && (tuned_bm256 || (force_bm == 256 && wgs256 >= bm256_min))) {
-          const int st256 = (ws_stages >= 3 || g.K >= 256) ? 3 : 2;
-          const dim3 grid256((unsigned)(wgs256 + (wred.ws ? wred.nblocks : 0)));
-          const int tn256 = g.N / 128;
-#define CREID_WS256_LAUNCH(NS_, ET_)                                                                                  \
-  hipLaunchKernelGGL((igemm_bf16_ws_kernel<128, NS_, 256, ET_>), grid256, block_ws, 0, s, gp, (const unsigned short*)src, \
-                     (const unsigned short*)wgt, (unsigned short*)out, (const unsigned short*)add_src, bn_part, tn256, bnred, wred)
-          if (dtype == CREID_F16) { if (st256 == 3) CREID_WS256_LAUNCH(3, F16T); else CREID_WS256_LAUNCH(2, F16T); }
-          else { if (st256 == 3) CREID_WS256_LAUNCH(3, Bf16T); else CREID_WS256_LAUNCH(2, Bf16T); }
-#undef CREID_WS256_LAUNCH
-          ran(tuned_bm256 ? 3 : -2);
-          return (int)hipGetLastError();
-        }
+      const int64_t wgs256 = (int64_t)((g.M + 255) / 256) * (g.N / 128);
+      if (g.N % 128 == 0 && !f.bnred && !r.parity && k.force_bm != 128 && (tuned_bm256 || (k.force_bm == 256 && wgs256 >= k.bm256_min))) {
+        r.family = CONV_WS256; r.bm = 256; r.bn = 128; r.ns = (ws_stages >= 3 || g.K >= 256) ? 3 : 2;
+        r.tiles_m = (g.M + 255) / 256; r.tiles_n = g.N / 128;
+        r.grid = (unsigned)wgs256 + ride;
+        r.kernel_id = tuned_bm256 ? 3 : -2;
+        return r;
       }
       // 4 x 32 KB at BN = 128 is one workgroup per CU (the C staging reuses the ring): only on request of a measured plan
-      if (ws_stages == 4 && bn == 128 && !(tuned_stages == 4 && use_ws != 2)) ws_stages = 3;
-      const dim3 grid_ws((unsigned)(tiles_m * tiles_n + (wred.ws ? wred.nblocks : 0)));
+      if (ws_stages == 4 && bn == 128 && !(tuned_stages == 4 && k.use_ws != 2)) ws_stages = 3;
+      r.ns = ws_stages == 4 ? 4 : (ws_stages == 2 ? 2 : 3);
+      r.grid += ride;
+      r.kernel_id = 0;
       // stride-1 3x3 on whole-image-row tiles: the same tile, ring depth and epilogue with the A operand resident in LDS
-      // (igemm_bf16_halo_kernel; identical bits).  CREID_IGEMM_HALO=0: the launches below
-      {
-        const char* he = CREID_KNOB_ENV("CREID_IGEMM_HALO");               // read per call: tests toggle it
-        if ((!he || atoi(he) != 0) && igemm_halo_covers(gp, bn, ws_stages)) {
-          const int hc = 1 << gp.log2span;
-#define CREID_HALO_LAUNCH1(C_, BN_, NS_, ET_)                                                                             \
-  hipLaunchKernelGGL((igemm_bf16_halo_kernel<C_, BN_, NS_, ET_>), grid_ws, block_ws, 0, s, gp, (const unsigned short*)src, \
-                     (const unsigned short*)wgt, (unsigned short*)out, (const unsigned short*)add_src, bn_part, tiles_n,  \
-                     bnred, wred)
-#define CREID_HALO_LAUNCH(C_, BN_, NS_) do { if (dtype == CREID_F16) CREID_HALO_LAUNCH1(C_, BN_, NS_, F16T); else CREID_HALO_LAUNCH1(C_, BN_, NS_, Bf16T); } while (0)
-          // (a 4-deep ring that does not fit beside the halo image is refused by igemm_halo_covers: that name is never launched)
-#define CREID_HALO_STAGES(C_, BN_) do { constexpr int NS4 = halo_lds_bytes(C_, BN_, 4) < 160 * 1024 ? 4 : 3;            \
-                                        if (ws_stages == 4) CREID_HALO_LAUNCH(C_, BN_, NS4);                            \
-                                        else if (ws_stages == 2) CREID_HALO_LAUNCH(C_, BN_, 2); else CREID_HALO_LAUNCH(C_, BN_, 3); } while (0)
-#define CREID_HALO_BN(C_) do { if (bn == 128) CREID_HALO_STAGES(C_, 128); else CREID_HALO_STAGES(C_, 64); } while (0)
-          if (hc == 64) CREID_HALO_BN(64); else if (hc == 128) CREID_HALO_BN(128); else CREID_HALO_BN(256);
+      // (igemm_bf16_halo_kernel; identical bits).  CREID_IGEMM_HALO=0: the plain producer/consumer kernel
+      IGemmGeom gp = g;
+      gp.parity = r.parity;
+      const bool halo = k.halo_on && igemm_halo_covers(gp, bn, ws_stages);
+      r.family = halo ? CONV_HALO : CONV_WS;
+      r.chan = halo ? (1 << g.log2span) : 0;
+      return r;
+    }
+    // 4-wave DMA kernel; LDS ring depth CREID_IGEMM_STAGES = 2..5, default 2 -- measured r01: deeper rings LOSE, the k-loop is
+    // bound by the LDS->MFMA chain and by workgroups/CU, not by DMA latency; 3+ stages cost occupancy (5 x 32 KB would not fit)
+    const int stages = (tuned_dma && tuned_stages) ? tuned_stages : k.stages;
+    r.family = CONV_DMA4; r.wred_first = f.wred;
+    r.ns = (stages < 2 || stages > 5) ? 2 : ((bn == 128 && stages == 5) ? 4 : stages);
+    r.kernel_id = 1;
+    return r;
+  }
+  // the fused reduction / masked add / folded BatchNorm (and f16) exist only in the 16-bit LDS-DMA kernels
+  if (f.bnred || f.add_mask || (f.affine && is16) || dtype == CREID_F16) return conv_refuse(r, CREID_E_DTYPE);
+  if (g.K % (dtype == CREID_BF16 ? 64 : 16) != 0) return conv_refuse(r, CREID_E_SHAPE);
+  r.family = dtype == CREID_BF16 ? CONV_REG_BF16 : CONV_F32;
+  r.wred_first = f.wred;
+  return r;
+}
+
+// The switch from a route to its template instantiation: decides nothing.
+static void launch_igemm_tiles(const ConvRoute& r, const IGemmGeom& g, const ConvPtrs& p, const BnRedArgs& bnred, const WRedJob& wred,
+                               hipStream_t s) {
+  const dim3 grid(r.grid), block(r.block);
+  const unsigned short *src = (const unsigned short*)p.src, *wgt = (const unsigned short*)p.wgt, *add_src = (const unsigned short*)p.add_src;
+  unsigned short* out = (unsigned short*)p.out;
+  const bool f16 = r.dtype == CREID_F16;
+#define CREID_ET_LAUNCH(K_, ...) do { if (f16) hipLaunchKernelGGL((K_<__VA_ARGS__, F16T>), grid, block, 0, s, g, src, wgt, out, add_src, p.bn_part, r.tiles_n, bnred, wred); \
+                                      else hipLaunchKernelGGL((K_<__VA_ARGS__, Bf16T>), grid, block, 0, s, g, src, wgt, out, add_src, p.bn_part, r.tiles_n, bnred, wred); } while (0)
+#define CREID_DMA_LAUNCH(BN_, NS_) do { if (f16) hipLaunchKernelGGL((igemm_bf16_dma_kernel<BN_, NS_, F16T>), grid, block, 0, s, g, src, wgt, out, add_src, p.bn_part, r.tiles_n, bnred); \
+                                        else hipLaunchKernelGGL((igemm_bf16_dma_kernel<BN_, NS_, Bf16T>), grid, block, 0, s, g, src, wgt, out, add_src, p.bn_part, r.tiles_n, bnred); } while (0)
+  // (a 4-deep ring that does not fit beside the halo image is refused by igemm_halo_covers: that name is never launched)
+#define CREID_HALO_STAGES(C_, BN_) do { constexpr int NS4 = halo_lds_bytes(C_, BN_, 4) < 160 * 1024 ? 4 : 3;                        \
+                                        if (r.ns == 4) CREID_ET_LAUNCH(igemm_bf16_halo_kernel, C_, BN_, NS4);                       \
+                                        else if (r.ns == 2) CREID_ET_LAUNCH(igemm_bf16_halo_kernel, C_, BN_, 2);                    \
+                                        else CREID_ET_LAUNCH(igemm_bf16_halo_kernel, C_, BN_, 3); } while (0)
+#define CREID_HALO_BN(C_) do { if (r.bn == 128) CREID_HALO_STAGES(C_, 128); else CREID_HALO_STAGES(C_, 64); } while (0)
+#define CREID_NS_LAUNCH(L_, BN_) do { switch (r.ns) { case 2: L_(BN_, 2); break; case 3: L_(BN_, 3); break; case 4: L_(BN_, 4); break; default: L_(BN_, 5); break; } } while (0)
+#define CREID_WS_LAUNCH(BN_, NS_) CREID_ET_LAUNCH(igemm_bf16_ws_kernel, BN_, NS_, 128)
+  switch (r.family) {
+    case CONV_WS256:
+      if (r.ns == 3) CREID_ET_LAUNCH(igemm_bf16_ws_kernel, 128, 3, 256); else CREID_ET_LAUNCH(igemm_bf16_ws_kernel, 128, 2, 256);
+      break;
+    case CONV_HALO:
+      if (r.chan == 64) CREID_HALO_BN(64); else if (r.chan == 128) CREID_HALO_BN(128); else CREID_HALO_BN(256);
+      break;
+    case CONV_WS:
+      if (r.bn == 128) { if (r.ns == 4) CREID_WS_LAUNCH(128, 4); else if (r.ns == 2) CREID_WS_LAUNCH(128, 2); else CREID_WS_LAUNCH(128, 3); }
+      else { if (r.ns == 4) CREID_WS_LAUNCH(64, 4); else if (r.ns == 2) CREID_WS_LAUNCH(64, 2); else CREID_WS_LAUNCH(64, 3); }
+      break;
+    case CONV_DMA4:
+      if (r.bn == 128) { if (r.ns == 4) CREID_DMA_LAUNCH(128, 4); else if (r.ns == 3) CREID_DMA_LAUNCH(128, 3); else CREID_DMA_LAUNCH(128, 2); }
+      else CREID_NS_LAUNCH(CREID_DMA_LAUNCH, 64);
+      break;
+    case CONV_REG_BF16:
+      if (r.bn == 128) hipLaunchKernelGGL(igemm_bf16_kernel<128>, grid, block, 0, s, g, src, wgt, out, add_src, p.bn_part, r.tiles_n);
+      else hipLaunchKernelGGL(igemm_bf16_kernel<64>, grid, block, 0, s, g, src, wgt, out, add_src, p.bn_part, r.tiles_n);
+      break;
+    default:
+      if (r.bn == 128) hipLaunchKernelGGL(igemm_f32_kernel<128>, grid, block, 0, s, g, (const float*)p.src, (const float*)p.wgt, (float*)p.out,
+                                          (const float*)p.add_src, p.bn_part, r.tiles_n);
+      else hipLaunchKernelGGL(igemm_f32_kernel<64>, grid, block, 0, s, g, (const float*)p.src, (const float*)p.wgt, (float*)p.out,
+                              (const float*)p.add_src, p.bn_part, r.tiles_n);
+      break;
+  }
+#undef CREID_WS_LAUNCH
+#undef CREID_NS_LAUNCH
 #undef CREID_HALO_BN
 #undef CREID_HALO_STAGES
-#undef CREID_HALO_LAUNCH
-#undef CREID_HALO_LAUNCH1
-          g_halo_launches.fetch_add(1, std::memory_order_relaxed);
-          ran(0);
-          return (int)hipGetLastError();
-        }
-      }
-#define CREID_WS_LAUNCH1(BN_, NS_, ET_)                                                                               \
-  hipLaunchKernelGGL((igemm_bf16_ws_kernel<BN_, NS_, 128, ET_>), grid_ws, block_ws, 0, s, gp, (const unsigned short*)src, \
-                     (const unsigned short*)wgt, (unsigned short*)out, (const unsigned short*)add_src, bn_part, tiles_n, \
-                     bnred, wred)
-#define CREID_WS_LAUNCH(BN_, NS_) do { if (dtype == CREID_F16) CREID_WS_LAUNCH1(BN_, NS_, F16T); else CREID_WS_LAUNCH1(BN_, NS_, Bf16T); } while (0)
-      if (bn == 128) { if (ws_stages == 4) CREID_WS_LAUNCH(128, 4); else if (ws_stages == 2) CREID_WS_LAUNCH(128, 2); else CREID_WS_LAUNCH(128, 3); }
-      else { if (ws_stages == 4) CREID_WS_LAUNCH(64, 4); else if (ws_stages == 2) CREID_WS_LAUNCH(64, 2); else CREID_WS_LAUNCH(64, 3); }
-#undef CREID_WS_LAUNCH
-#undef CREID_WS_LAUNCH1
-      ran(0);
-      return (int)hipGetLastError();
-    }
-    if (wred.ws) { const int rc = wgrad_reduce_job_launch(wred, s); if (rc) return rc; wred.ws = nullptr; }
-    // LDS ring depth (CREID_IGEMM_STAGES = 2..5, default 2 -- measured r01: deeper rings LOSE, the k-loop is bound
-    // by the LDS->MFMA chain and by workgroups/CU, not by DMA latency; 3+ stages cost occupancy)
-    static const int stages_env = [] { const char* e = getenv("CREID_IGEMM_STAGES"); int v = e ? atoi(e) : 0; return (v >= 2 && v <= 5) ? v : 2; }();
-    const int stages = (tuned_dma && tuned_stages) ? tuned_stages : stages_env;
-#define CREID_DMA_LAUNCH1(BN_, NS_, ET_)                                                                               \
-  hipLaunchKernelGGL((igemm_bf16_dma_kernel<BN_, NS_, ET_>), grid, block, 0, s, g, (const unsigned short*)src,         \
-                     (const unsigned short*)wgt, (unsigned short*)out, (const unsigned short*)add_src, bn_part, tiles_n, \
-                     bnred)
-#define CREID_DMA_LAUNCH(BN_, NS_) do { if (dtype == CREID_F16) CREID_DMA_LAUNCH1(BN_, NS_, F16T); else CREID_DMA_LAUNCH1(BN_, NS_, Bf16T); } while (0)
-    if (bn == 128) {
-      switch (stages) { case 2: CREID_DMA_LAUNCH(128, 2); break; case 3: CREID_DMA_LAUNCH(128, 3); break;
-                        case 4: case 5: CREID_DMA_LAUNCH(128, 4); break;   // 5 x 32 KB would not fit
-                        default: CREID_DMA_LAUNCH(128, 2); break; }
-    } else {
-      switch (stages) { case 2: CREID_DMA_LAUNCH(64, 2); break; case 3: CREID_DMA_LAUNCH(64, 3); break;
-                        case 4: CREID_DMA_LAUNCH(64, 4); break; case 5: CREID_DMA_LAUNCH(64, 5); break;
-                        default: CREID_DMA_LAUNCH(64, 2); break; }
-    }
 #undef CREID_DMA_LAUNCH
-#undef CREID_DMA_LAUNCH1
-    ran(1);
-    return (int)hipGetLastError();
-  } else if (bnred.x || g.add_mask || (g.epi_scale && creid_is16(dtype)) || dtype == CREID_F16) {
-    return CREID_E_DTYPE;          // the fused reduction / masked add / folded BatchNorm (and f16) exist only in the 16-bit LDS-DMA kernels
-  } else if (wred.ws && wgrad_reduce_job_launch(wred, s) != 0) {
-    return (int)hipGetLastError();
-  } else if (dtype == CREID_BF16) {
-    if (g.K % 64 != 0) return CREID_E_SHAPE;
-    if (bn == 128)
-      hipLaunchKernelGGL(igemm_bf16_kernel<128>, grid, block, 0, s, g, (const unsigned short*)src,
-                         (const unsigned short*)wgt, (unsigned short*)out, (const unsigned short*)add_src, bn_part, tiles_n);
-    else
-      hipLaunchKernelGGL(igemm_bf16_kernel<64>, grid, block, 0, s, g, (const unsigned short*)src,
-                         (const unsigned short*)wgt, (unsigned short*)out, (const unsigned short*)add_src, bn_part, tiles_n);
-  } else if (dtype == CREID_F32) {
-    if (g.K % 16 != 0) return CREID_E_SHAPE;
-    if (bn == 128)
-      hipLaunchKernelGGL(igemm_f32_kernel<128>, grid, block, 0, s, g, (const float*)src, (const float*)wgt, (float*)out,
-                         (const float*)add_src, bn_part, tiles_n);
-    else
-      hipLaunchKernelGGL(igemm_f32_kernel<64>, grid, block, 0, s, g, (const float*)src, (const float*)wgt, (float*)out,
-                         (const float*)add_src, bn_part, tiles_n);
-  } else {
-    return CREID_E_DTYPE;
+#undef CREID_ET_LAUNCH
+}
+
+static void launch_route(const ConvRoute& r, const IGemmGeom& g, const ConvPtrs& p, const BnRedArgs& bnred, const WRedJob& wred,
+                         hipStream_t s) {
+  switch (r.family) {
+    case CONV_C64: return launch_conv3x3_c64(r, g, p, s);
+    case CONV_PP: return launch_igemm_pp(r, g, p, s);
+    case CONV_STREAM1: return launch_stream1(r, g, p, s);
+    case CONV_STREAM2: return launch_stream2(r, g, p, s);
+    default: return launch_igemm_tiles(r, g, p, bnred, wred, s);
   }
-  ran(-2);
+}
+
+static ConvFeat conv_feat_of(const IGemmGeom& g, const void* add_src, const float* bn_part, const BnRedArgs& bnred, const WRedJob* wred,
+                             int dtype) {
+  ConvFeat f;
+  f.dtype = dtype; f.add_src = add_src != nullptr; f.add_compact = g.add_compact != 0; f.add_mask = g.add_mask != nullptr;
+  f.stats = bn_part != nullptr; f.affine = g.epi_scale != nullptr; f.bnred = bnred.x != nullptr; f.tiles_per_image = bnred.tiles_per_image;
+  f.wred = wred && wred->ws; f.wred_nblocks = f.wred ? wred->nblocks : 0;
+  return f;
+}
+
+static int launch_igemm(const IGemmGeom& g_in, const void* src, const void* wgt, void* out, const void* add_src,
+                        float* bn_part, int dtype, hipStream_t s, BnRedArgs bnred = BnRedArgs{},
+                        const WRedJob* wred_in = nullptr) {
+  static_assert(sizeof(float) * (4 * 512 + 8192) <= 2 * (128 + 64) * 64 * 2, "reduce scratch must fit the smallest LDS ring");
+  const IGemmKnobs& k = conv_igemm_knobs();
+  const ConvRoute r = route_igemm(g_in, conv_feat_of(g_in, add_src, bn_part, bnred, wred_in, dtype), k);
+  if (r.err) return r.err;
+  IGemmGeom g = g_in;
+  g.abl = k.abl;
+  g.parity = r.parity;
+  WRedJob wred{};
+  if (wred_in) wred = *wred_in;
+  if (r.wred_first) {                                  // kernels without the carrier: the reduce job as its own launch first
+    if (const int rc = wgrad_reduce_job_launch(wred, s)) return rc;
+    wred.ws = nullptr;
+  }
+  // a launch that found a plan and takes another kernel (creid_tune_count, what = 1)
+  if (r.have_plan && r.kernel_id != r.planned) creid_tune_declined(CREID_TUNE_IGEMM, g.M, g.N, g.K, r.plan_key);
+  if (r.family == CONV_HALO) g_halo_launches.fetch_add(1, std::memory_order_relaxed);
+  launch_route(r, g, ConvPtrs{src, wgt, out, add_src, bn_part}, bnred, wred, s);
   return (int)hipGetLastError();
 }
 
@@ -1435,6 +1441,18 @@ static int check_desc(const creid_conv_desc* d) {
 }
 
 int conv_check_desc(const creid_conv_desc* d) { return check_desc(d); }
+
+// What a fused data-gradient call may combine (creid_conv2d_dgrad_fused_nhwc and creid_conv_route_describe): the compact add needs
+// even extents, the fused BatchNorm reduction and the masked add exist only in the 16-bit LDS-DMA kernels.
+int conv_dgrad_check(const creid_conv_desc* d, const ConvFeat& f, int64_t bn_stat_image_rows, int add_src_stride) {
+  if (bn_stat_image_rows % 128 != 0) return CREID_E_SHAPE;
+  if (add_src_stride != 1 && add_src_stride != 2) return CREID_E_ARG;
+  if (add_src_stride == 2 && (!f.add_src || d->in_h % 2 || d->in_w % 2)) return CREID_E_SHAPE;
+  const bool dma16 = creid_is16(f.dtype) && conv_igemm_knobs().use_dma;
+  if (f.bnred && !dma16) return CREID_E_DTYPE;
+  if (f.add_mask && (!f.add_src || add_src_stride != 1 || !dma16)) return CREID_E_ARG;
+  return 0;
+}
 
 extern "C" {
 
@@ -1515,12 +1533,9 @@ int creid_conv2d_dgrad_fused_nhwc(const creid_conv_desc* d, const void* dy, cons
   if (!creid_is_storage(dtype)) return CREID_E_DTYPE;     // (before the piggy-backed weight-gradient reduction is planned)
   CREID_CHECK_ARG(dy && w_crsk && dx && bn_stat_image_rows >= 0);
   if (bn_x) CREID_CHECK_ARG(bn_mean && bn_invstd && bn_partial);
-  if (bn_stat_image_rows % 128 != 0) return CREID_E_SHAPE;
-  if (add_src_stride != 1 && add_src_stride != 2) return CREID_E_ARG;
-  if (add_src_stride == 2 && (!add_src || d->in_h % 2 || d->in_w % 2)) return CREID_E_SHAPE;
-  const int use_dma = use_dma_env();
-  if (bn_x && (!creid_is16(dtype) || !use_dma)) return CREID_E_DTYPE;
-  if (add_mask && (!add_src || add_src_stride != 1 || !creid_is16(dtype) || !use_dma)) return CREID_E_ARG;
+  ConvFeat f;
+  f.dtype = dtype; f.add_src = add_src != nullptr; f.add_mask = add_mask != nullptr; f.bnred = bn_x != nullptr;
+  if (const int rc = conv_dgrad_check(d, f, bn_stat_image_rows, add_src_stride)) return rc;
   WRedJob job{};
   bool have_job = false;
   if (wred_desc) {

@@ -19,7 +19,7 @@
 // Arithmetic per output element is that of the tile kernels (same k order inside v_mfma_f32_32x32x16_bf16, same epilogue
 // operations): outputs are bit-identical (tests/test_conv_pipe_gpu.py).
 #include "conv_epilogue.hpp"
-#include "tune.hpp"
+#include "conv_route.hpp"
 #include <type_traits>
 #include <stdlib.h>
 
@@ -419,68 +419,71 @@ __global__ __launch_bounds__(512, (BM * BN <= 128 * 128) ? 4 : 2) void igemm_bf1
 }  // namespace creid_pp
 using namespace creid_pp;
 
-// Launch plan kind 5 (tune.hpp) / CREID_IGEMM_PP: returns CREID_E_SHAPE when the launch is not covered (the caller falls back to
-// the tile kernels).  variant = BM / 128 | (BN / 128) << 2 | KPH << 4 | MODE << 8 (MODE 2: free-running form; 0: 256 x 256, 2 slices per phase, pieces beside
+// Launch plan kind 5 (tune.hpp) / CREID_IGEMM_PP: igemm_pp_route answers false when the launch is not covered (route_igemm then
+// goes on to the tile kernels).  variant = BM / 128 | (BN / 128) << 2 | KPH << 4 | MODE << 8 (MODE 2: free-running form; 0: 256 x 256, 2 slices per phase, pieces beside
 // the fragment reads).
 static unsigned long long* g_pp_trace_buf = nullptr;
 #ifdef CREID_ABL_BUILD
 extern "C" int creid_dbg_pp_trace(void* buf) { g_pp_trace_buf = (unsigned long long*)buf; return PP_TRACE_N; }
 #endif
 
-int launch_igemm_pp(const IGemmGeom& g, const void* src, const void* wgt, void* out, const void* add_src, float* bn_part,
-                    int variant, int dtype, hipStream_t s) {
-  if (!creid_is16(dtype)) return CREID_E_SHAPE;
-  if (g.log2span < 6 || g.K % 64 != 0 || g.parity || g.add_compact || g.add_mask) return CREID_E_SHAPE;
-  if (bn_part && (g.epi_scale || add_src)) return CREID_E_SHAPE;
+bool igemm_pp_route(const IGemmGeom& g, const ConvFeat& f, int variant, const IGemmKnobs& k, ConvRoute& r) {
+  if (!creid_is16(f.dtype)) return false;
+  if (g.log2span < 6 || g.K % 64 != 0 || g.parity || f.add_compact || f.add_mask) return false;
+  if (f.stats && (f.affine || f.add_src)) return false;
   int bm = (variant & 3) * 128, bn = ((variant >> 2) & 3) * 128, kph = (variant >> 4) & 7, glm = (variant >> 8) & 3;
   if (bm == 0) bm = 256;
   if (bn == 0) bn = 256;
   if (kph == 0) kph = 2;
-  if (g.N % bn != 0) return CREID_E_SHAPE;
-  PipeArgs pa{g_pp_trace_buf, (const unsigned short*)src, (const unsigned short*)wgt, (unsigned short*)out, (const unsigned short*)add_src, bn_part,
-              (g.M + bm - 1) / bm, g.N / bn};
-  const int ntiles = pa.tiles_m * pa.tiles_n;
+  if (g.N % bn != 0 || (bm != 128 && bm != 256) || (bn != 128 && bn != 256)) return false;
+  const int epi = f.affine ? 2 : (f.stats ? 1 : 0);
+  if (glm == 2) {
+    // the free-running 256 x 256 form with the BatchNorm-partials epilogue needs 257 registers (one spill): that one
+    // combination runs the ping-pong form (bit-identical results, tests/test_conv_pipe_gpu.py) and is never instantiated
+    kph = 1;
+    if (bm == 256 && bn == 256 && epi == 1) glm = 0;
+  } else if (glm != 0 || (kph != 1 && kph != 2)) {
+    return false;
+  }
+  const int tiles_m = (g.M + bm - 1) / bm, tiles_n = g.N / bn, ntiles = tiles_m * tiles_n;
   static const int ncu = [] { int dev = 0, n = 256; hipGetDevice(&dev); hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
   int cap = (bm * bn <= 128 * 128) ? 2 * ncu : ncu;
-  { const char* e = CREID_KNOB_ENV("CREID_PP_WGS"); const int v = e ? atoi(e) : 0; if (v > 0) cap = v; }   // tests: few workgroups walk many tiles
-  const dim3 grid((unsigned)(ntiles < cap ? ntiles : cap)), block(512);
-  const int epi = g.epi_scale ? 2 : (bn_part ? 1 : 0);
+  if (k.pp_wgs > 0) cap = k.pp_wgs;                                  // tests: few workgroups walk many tiles
+  r.family = CONV_PP; r.bm = bm; r.bn = bn; r.wn = (bm == 256 && bn == 128) ? 2 : 4; r.kph = kph; r.glm = glm; r.epi = epi;
+  r.tiles_m = tiles_m; r.tiles_n = tiles_n;
+  r.grid = (unsigned)(ntiles < cap ? ntiles : cap); r.block = 512;
+  return true;
+}
+
+void launch_igemm_pp(const ConvRoute& r, const IGemmGeom& g, const ConvPtrs& p, hipStream_t s) {
+  PipeArgs pa{g_pp_trace_buf, (const unsigned short*)p.src, (const unsigned short*)p.wgt, (unsigned short*)p.out,
+              (const unsigned short*)p.add_src, p.bn_part, r.tiles_m, r.tiles_n};
+  const dim3 grid(r.grid), block(r.block);
 #define CREID_PP_LAUNCH_E(BM_, BN_, WN_, KPH_, GLM_, EPI_)                                                  \
   do {                                                                                                      \
-    if (dtype == CREID_F16) hipLaunchKernelGGL((igemm_bf16_pp_kernel<BM_, BN_, WN_, KPH_, GLM_, EPI_, F16T>), grid, block, 0, s, g, pa); \
+    if (r.dtype == CREID_F16) hipLaunchKernelGGL((igemm_bf16_pp_kernel<BM_, BN_, WN_, KPH_, GLM_, EPI_, F16T>), grid, block, 0, s, g, pa); \
     else hipLaunchKernelGGL((igemm_bf16_pp_kernel<BM_, BN_, WN_, KPH_, GLM_, EPI_, Bf16T>), grid, block, 0, s, g, pa); \
   } while (0)
 #define CREID_PP_LAUNCH(BM_, BN_, WN_, KPH_, GLM_)                                                          \
   do {                                                                                                      \
-    if (dtype == CREID_F16) {                                                                               \
-      /* f16: eval-mode forward (folded affine), plain forward and (round 5: f16 training) the forward with BatchNorm partials */ \
-      if (epi == 2) hipLaunchKernelGGL((igemm_bf16_pp_kernel<BM_, BN_, WN_, KPH_, GLM_, 2, F16T>), grid, block, 0, s, g, pa); \
-      else if (epi == 1) hipLaunchKernelGGL((igemm_bf16_pp_kernel<BM_, BN_, WN_, KPH_, GLM_, 1, F16T>), grid, block, 0, s, g, pa); \
-      else hipLaunchKernelGGL((igemm_bf16_pp_kernel<BM_, BN_, WN_, KPH_, GLM_, 0, F16T>), grid, block, 0, s, g, pa);        \
-    }                                                                                                       \
-    else if (epi == 2) hipLaunchKernelGGL((igemm_bf16_pp_kernel<BM_, BN_, WN_, KPH_, GLM_, 2, Bf16T>), grid, block, 0, s, g, pa); \
-    else if (epi == 1) hipLaunchKernelGGL((igemm_bf16_pp_kernel<BM_, BN_, WN_, KPH_, GLM_, 1, Bf16T>), grid, block, 0, s, g, pa); \
-    else hipLaunchKernelGGL((igemm_bf16_pp_kernel<BM_, BN_, WN_, KPH_, GLM_, 0, Bf16T>), grid, block, 0, s, g, pa);        \
+    if (r.epi == 2) CREID_PP_LAUNCH_E(BM_, BN_, WN_, KPH_, GLM_, 2);                                        \
+    else if (r.epi == 1) CREID_PP_LAUNCH_E(BM_, BN_, WN_, KPH_, GLM_, 1);                                   \
+    else CREID_PP_LAUNCH_E(BM_, BN_, WN_, KPH_, GLM_, 0);                                                   \
   } while (0)
 #define CREID_PP_KPH(BM_, BN_, WN_)                                                                        \
   do {                                                                                                     \
-    /* the free-running 256 x 256 form with the BatchNorm-partials epilogue needs 257 registers (one spill): that one     \
-       combination runs the ping-pong form (bit-identical results, tests/test_conv_pipe_gpu.py) and is never instantiated */ \
-    if (glm == 2 && BM_ == 256 && BN_ == 256 && epi == 1) { if constexpr (BM_ == 256 && BN_ == 256) CREID_PP_LAUNCH_E(BM_, BN_, WN_, 1, 0, 1); } \
-    else if (glm == 2 && BM_ == 256 && BN_ == 256) { if constexpr (BM_ == 256 && BN_ == 256) { if (epi == 2) CREID_PP_LAUNCH_E(BM_, BN_, WN_, 1, 2, 2); else CREID_PP_LAUNCH_E(BM_, BN_, WN_, 1, 2, 0); } } \
-    else if (glm == 2) { if constexpr (!(BM_ == 256 && BN_ == 256)) CREID_PP_LAUNCH(BM_, BN_, WN_, 1, 2); }   \
-    else if (glm != 0) return CREID_E_SHAPE;                                                               \
-    else if (kph == 1) CREID_PP_LAUNCH(BM_, BN_, WN_, 1, 0);                                               \
-    else if (kph == 2) CREID_PP_LAUNCH(BM_, BN_, WN_, 2, 0);                                               \
-    else return CREID_E_SHAPE;                                                                             \
+    if (r.glm == 2) {                                                                                      \
+      if constexpr (BM_ == 256 && BN_ == 256) { if (r.epi == 2) CREID_PP_LAUNCH_E(BM_, BN_, WN_, 1, 2, 2); else CREID_PP_LAUNCH_E(BM_, BN_, WN_, 1, 2, 0); } \
+      else CREID_PP_LAUNCH(BM_, BN_, WN_, 1, 2);                                                           \
+    }                                                                                                      \
+    else if (r.kph == 1) CREID_PP_LAUNCH(BM_, BN_, WN_, 1, 0);                                             \
+    else CREID_PP_LAUNCH(BM_, BN_, WN_, 2, 0);                                                             \
   } while (0)
-  if (bm == 256 && bn == 256) CREID_PP_KPH(256, 256, 4);
-  else if (bm == 128 && bn == 256) CREID_PP_KPH(128, 256, 4);
-  else if (bm == 256 && bn == 128) CREID_PP_KPH(256, 128, 2);
-  else if (bm == 128 && bn == 128) CREID_PP_KPH(128, 128, 4);
-  else return CREID_E_SHAPE;
+  if (r.bm == 256 && r.bn == 256) CREID_PP_KPH(256, 256, 4);
+  else if (r.bm == 128 && r.bn == 256) CREID_PP_KPH(128, 256, 4);
+  else if (r.bm == 256 && r.bn == 128) CREID_PP_KPH(256, 128, 2);
+  else CREID_PP_KPH(128, 128, 4);
 #undef CREID_PP_KPH
 #undef CREID_PP_LAUNCH
 #undef CREID_PP_LAUNCH_E
-  return (int)hipGetLastError();
 }

@@ -15,6 +15,7 @@
 // Every wave executes the same sequence of s_barrier's by construction: one per k-chunk, then a fixed number per
 // epilogue; all loop bounds are workgroup-uniform.
 #include "conv_epilogue.hpp"
+#include "conv_route.hpp"
 #include <stdlib.h>
 
 __device__ __attribute__((aligned(128))) unsigned g_stream_zero_page[32];   // rows >= M fetch this page of zeros
@@ -205,36 +206,34 @@ __global__ __launch_bounds__(512, 1) void igemm1x1_stream_kernel(const unsigned 
 }
 
 // ------------------------------------------------------------------------------------ host
-// Returns CREID_E_SHAPE when the GEMM is outside the kernel's scope (the caller then uses conv_igemm.hip's kernels).
-int launch_stream1x1(int M, int K, int N, const void* src, const void* wgt, void* out, float* bn_part, hipStream_t s) {
-  if (K != 64 && K != 128 && K != 256) return CREID_E_SHAPE;
+// Coverage and shape of the first form: K = 64 / 128 / 256, 64- / 128- / 256-column slabs whose weights fit 32 K elements.
+bool stream1_route(const IGemmGeom& g, const IGemmKnobs& k, ConvRoute& r) {
+  const int K = g.K, N = g.N;
+  if (K != 64 && K != 128 && K != 256) return false;
   int bn = N >= 256 ? 256 : N;
-  if (bn != 64 && bn != 128 && bn != 256) return CREID_E_SHAPE;
-  if (N % bn != 0) return CREID_E_SHAPE;
+  if (bn != 64 && bn != 128 && bn != 256) return false;
+  if (N % bn != 0) return false;
   if (K == 256 && bn == 256) bn = 128;                 // the weight slab must fit: BN * K <= 32 K elements
-  if ((int64_t)bn * K > 32768) return CREID_E_SHAPE;
-  const int tiles_m = (M + 127) / 128, tiles_n = N / bn;
-  // persistent grid: one workgroup per CU (the LDS budget allows one), split evenly over the column slabs
-  int wgs = 256;                                       // read per call (tests shrink it to force many tiles per workgroup)
-  { const char* e = CREID_KNOB_ENV("CREID_STREAM1X1_WGS"); const int v = e ? atoi(e) : 0; if (v > 0) wgs = v; }
-  int dbg = 0;
-  { const char* e = CREID_KNOB_ENV("CREID_STREAM1X1_DBG"); if (e) dbg = atoi(e); }
-  int groups = wgs / tiles_n;
-  if (groups < 1) groups = 1;
-  if (groups > tiles_m) groups = tiles_m;
-  const dim3 grid((unsigned)(groups * tiles_n)), block(512);
+  if ((int64_t)bn * K > 32768) return false;
+  r.family = CONV_STREAM1; r.bn = bn; r.kch = K / 64; r.ns = (K == 256 && bn == 64) ? 4 : 3;
+  r.tiles_m = (g.M + 127) / 128; r.tiles_n = N / bn;
+  r.grid = conv_stream_slab_grid(k.stream_wgs, r.tiles_m, r.tiles_n); r.block = 512;
+  r.abl = k.stream1_dbg;
+  return true;
+}
+
+void launch_stream1(const ConvRoute& r, const IGemmGeom& g, const ConvPtrs& p, hipStream_t s) {
 #define CREID_ST_LAUNCH(BN_, KCH_, NSA_)                                                                              \
-  hipLaunchKernelGGL((igemm1x1_stream_kernel<BN_, KCH_, NSA_>), grid, block, 0, s, (const unsigned short*)src, M, K, N, \
-                     (const unsigned short*)wgt, (unsigned short*)out, bn_part, tiles_m, tiles_n, dbg)
-  if (K == 64) {
-    if (bn == 256) CREID_ST_LAUNCH(256, 1, 3); else if (bn == 128) CREID_ST_LAUNCH(128, 1, 3); else CREID_ST_LAUNCH(64, 1, 3);
-  } else if (K == 128) {
-    if (bn == 256) CREID_ST_LAUNCH(256, 2, 3); else if (bn == 128) CREID_ST_LAUNCH(128, 2, 3); else CREID_ST_LAUNCH(64, 2, 3);
+  hipLaunchKernelGGL((igemm1x1_stream_kernel<BN_, KCH_, NSA_>), dim3(r.grid), dim3(r.block), 0, s, (const unsigned short*)p.src, \
+                     g.M, g.K, g.N, (const unsigned short*)p.wgt, (unsigned short*)p.out, p.bn_part, r.tiles_m, r.tiles_n, r.abl)
+  if (r.kch == 1) {
+    if (r.bn == 256) CREID_ST_LAUNCH(256, 1, 3); else if (r.bn == 128) CREID_ST_LAUNCH(128, 1, 3); else CREID_ST_LAUNCH(64, 1, 3);
+  } else if (r.kch == 2) {
+    if (r.bn == 256) CREID_ST_LAUNCH(256, 2, 3); else if (r.bn == 128) CREID_ST_LAUNCH(128, 2, 3); else CREID_ST_LAUNCH(64, 2, 3);
   } else {
-    if (bn == 128) CREID_ST_LAUNCH(128, 4, 3); else CREID_ST_LAUNCH(64, 4, 4);
+    if (r.bn == 128) CREID_ST_LAUNCH(128, 4, 3); else CREID_ST_LAUNCH(64, 4, 4);
   }
 #undef CREID_ST_LAUNCH
-  return (int)hipGetLastError();
 }
 
 // ------------------------------------------------------------------------------------ second form (round 3)
@@ -537,44 +536,39 @@ __global__ __launch_bounds__(512, 2) void igemm1x1_stream2_kernel(const unsigned
   store_out(n_iter - 1);
 }
 
-// Returns CREID_E_SHAPE when the GEMM is outside the kernel's scope (the caller then uses conv_igemm.hip's kernels).
-int launch_stream2(int M, int K, int N, const void* src, const void* wgt, void* out, float* bn_part, const void* add_src,
-                   const float* epi_scale, const float* epi_shift, int epi_relu, int bn_cap, int dtype, hipStream_t s) {
-  if (K != 64 && K != 128 && K != 256) return CREID_E_SHAPE;
+// Coverage and shape of the second form; bn_cap = 64 / 128: at most that many columns per slab (a plan's p1, CREID_STREAM2_BN).
+bool stream2_route(const IGemmGeom& g, int bn_cap, const IGemmKnobs& k, ConvRoute& r) {
+  const int K = g.K, N = g.N;
+  if (K != 64 && K != 128 && K != 256) return false;
   int bn = N >= 256 ? 256 : N;
   if (K == 256 && bn > 64) bn = 64;                    // LDS: weight slab + one 64 KB tile slot + staging
-  if (bn != 64 && bn != 128 && bn != 256) return CREID_E_SHAPE;
-  if (N % bn != 0) return CREID_E_SHAPE;
-  { const char* e = CREID_KNOB_ENV("CREID_STREAM2_BN"); const int v = e ? atoi(e) : 0; if (v == 64 || v == 128) bn_cap = v; }   // (experiments)
+  if (bn != 64 && bn != 128 && bn != 256) return false;
+  if (N % bn != 0) return false;
+  if (k.stream2_bn == 64 || k.stream2_bn == 128) bn_cap = k.stream2_bn;   // (experiments)
   if ((bn_cap == 64 || bn_cap == 128) && bn_cap < bn && N % bn_cap == 0) bn = bn_cap;
-  const int tiles_m = (M + 127) / 128, tiles_n = N / bn;
-  int wgs = 256;
-  { const char* e = CREID_KNOB_ENV("CREID_STREAM1X1_WGS"); const int v = e ? atoi(e) : 0; if (v > 0) wgs = v; }   // read per call (tests)
-  int groups = wgs / tiles_n;
-  if (groups < 1) groups = 1;
-  if (groups > tiles_m) groups = tiles_m;
-  const dim3 grid((unsigned)(groups * tiles_n)), block(512);
-#ifdef CREID_ABL_BUILD
-  static const int abl = creid_ablation_env("CREID_STREAM2_ABL");   // 1 no stores, 2 no residual loads, 4 no A loads, 8 no copy-out
-#else
-  const int abl = 0;
-#endif
+  r.family = CONV_STREAM2; r.bn = bn; r.kch = K / 64; r.ns = (K == 256 || (K == 128 && bn == 256)) ? 1 : 2;
+  r.tiles_m = (g.M + 127) / 128; r.tiles_n = N / bn;
+  r.grid = conv_stream_slab_grid(k.stream_wgs, r.tiles_m, r.tiles_n); r.block = 512;
+  r.abl = k.stream2_abl;                               // 1 no stores, 2 no residual loads, 4 no A loads, 8 no copy-out
+  return true;
+}
+
+void launch_stream2(const ConvRoute& r, const IGemmGeom& g, const ConvPtrs& p, hipStream_t s) {
 #define CREID_ST2_LAUNCH1(BN_, KCH_, RT_, ET_)                                                                          \
-  hipLaunchKernelGGL((igemm1x1_stream2_kernel<BN_, KCH_, RT_, ET_>), grid, block, 0, s, (const unsigned short*)src, M, K, N, \
-                     (const unsigned short*)wgt, (unsigned short*)out, bn_part, (const unsigned short*)add_src, epi_scale, \
-                     epi_shift, epi_relu, tiles_m, tiles_n, abl)
+  hipLaunchKernelGGL((igemm1x1_stream2_kernel<BN_, KCH_, RT_, ET_>), dim3(r.grid), dim3(r.block), 0, s, (const unsigned short*)p.src, \
+                     g.M, g.K, g.N, (const unsigned short*)p.wgt, (unsigned short*)p.out, p.bn_part, (const unsigned short*)p.add_src, \
+                     g.epi_scale, g.epi_shift, g.epi_relu, r.tiles_m, r.tiles_n, r.abl)
 #define CREID_ST2_LAUNCH(BN_, KCH_, RT_) \
-  do { if (dtype == CREID_F16) CREID_ST2_LAUNCH1(BN_, KCH_, RT_, F16T); else CREID_ST2_LAUNCH1(BN_, KCH_, RT_, Bf16T); } while (0)
-  if (K == 64) {
-    if (bn == 256) CREID_ST2_LAUNCH(256, 1, 2); else if (bn == 128) CREID_ST2_LAUNCH(128, 1, 2); else CREID_ST2_LAUNCH(64, 1, 2);
-  } else if (K == 128) {
-    if (bn == 256) CREID_ST2_LAUNCH(256, 2, 1); else if (bn == 128) CREID_ST2_LAUNCH(128, 2, 2); else CREID_ST2_LAUNCH(64, 2, 2);
+  do { if (r.dtype == CREID_F16) CREID_ST2_LAUNCH1(BN_, KCH_, RT_, F16T); else CREID_ST2_LAUNCH1(BN_, KCH_, RT_, Bf16T); } while (0)
+  if (r.kch == 1) {
+    if (r.bn == 256) CREID_ST2_LAUNCH(256, 1, 2); else if (r.bn == 128) CREID_ST2_LAUNCH(128, 1, 2); else CREID_ST2_LAUNCH(64, 1, 2);
+  } else if (r.kch == 2) {
+    if (r.bn == 256) CREID_ST2_LAUNCH(256, 2, 1); else if (r.bn == 128) CREID_ST2_LAUNCH(128, 2, 2); else CREID_ST2_LAUNCH(64, 2, 2);
   } else {
     CREID_ST2_LAUNCH(64, 4, 1);
   }
 #undef CREID_ST2_LAUNCH
 #undef CREID_ST2_LAUNCH1
-  return (int)hipGetLastError();
 }
 
 // creid_conv1x1_bnrelu_fwd: the training forward of a 1 x 1 stride-1 convolution whose input is still RAW (BatchNorm + ReLU applied
@@ -589,14 +583,10 @@ static int launch_stream2_axf(int M, int K, int N, const void* src, const void* 
   if (K == 128 && bn > 128) bn = 128;
   if (bn != 64 && bn != 128 && bn != 256) return CREID_E_SHAPE;
   if (N % bn != 0) return CREID_E_SHAPE;
-  { const char* e = CREID_KNOB_ENV("CREID_STREAM2_BN"); const int v = e ? atoi(e) : 0; if ((v == 64 || v == 128) && v < bn && N % v == 0) bn = v; }
+  const IGemmKnobs& k = conv_igemm_knobs();
+  { const int v = k.stream2_bn; if ((v == 64 || v == 128) && v < bn && N % v == 0) bn = v; }
   const int tiles_m = (M + 127) / 128, tiles_n = N / bn;
-  int wgs = 256;
-  { const char* e = CREID_KNOB_ENV("CREID_STREAM1X1_WGS"); const int v = e ? atoi(e) : 0; if (v > 0) wgs = v; }
-  int groups = wgs / tiles_n;
-  if (groups < 1) groups = 1;
-  if (groups > tiles_m) groups = tiles_m;
-  const dim3 grid((unsigned)(groups * tiles_n)), block(512);
+  const dim3 grid(conv_stream_slab_grid(k.stream_wgs, tiles_m, tiles_n)), block(512);
 #define CREID_AXF_LAUNCH1(BN_, KCH_, RT_, ET_)                                                                          \
   hipLaunchKernelGGL((igemm1x1_stream2_kernel<BN_, KCH_, RT_, ET_, true>), grid, block, 0, s, (const unsigned short*)src, M, K, N, \
                      (const unsigned short*)wgt, (unsigned short*)out, bn_part, (const unsigned short*)nullptr, (const float*)nullptr, \
@@ -830,29 +820,29 @@ __global__ __launch_bounds__(512, 2) void conv3x3_c64_kernel(const unsigned shor
   store_out(n_iter - 1);
 }
 
-// Returns CREID_E_SHAPE when the convolution is outside the kernel's scope.
-int launch_conv3x3_c64(int M, int H, int Wd, const void* src, const void* wgt, void* out, float* bn_part, const float* epi_scale,
-                       const float* epi_shift, int epi_relu, int dtype, hipStream_t s) {
+// Coverage and shape: whole 128-pixel row blocks of a 32 / 64 wide image, or 16 x 8 blocks (80 x 80: 50 per image).
+bool conv3x3_c64_route(const IGemmGeom& g, const ConvFeat& f, const IGemmKnobs& k, ConvRoute& r) {
+  const int M = g.M, H = g.OH, Wd = g.OW;
   const bool full_rows = (Wd == 32 || Wd == 64) && H > 0 && (H * Wd) % 128 == 0;
-  const bool tile2d = !full_rows && Wd > 0 && Wd % 16 == 0 && H > 0 && H % 8 == 0;      // 16 x 8 tiles (80 x 80: 50 per image)
-  if ((!full_rows && !tile2d) || M % (H * Wd) != 0 || !creid_is16(dtype)) return CREID_E_SHAPE;
+  const bool tile2d = !full_rows && Wd > 0 && Wd % 16 == 0 && H > 0 && H % 8 == 0;
+  if ((!full_rows && !tile2d) || M % (H * Wd) != 0 || !creid_is16(f.dtype)) return false;
   const int n_tiles = M / 128;
-  int wgs = 256;
-  { const char* e = CREID_KNOB_ENV("CREID_STREAM1X1_WGS"); const int v = e ? atoi(e) : 0; if (v > 0) wgs = v; }   // read per call (tests)
+  int wgs = k.stream_wgs > 0 ? k.stream_wgs : 256;
   if (wgs > n_tiles) wgs = n_tiles;
-  const dim3 grid((unsigned)wgs), block(512);
-#ifdef CREID_ABL_BUILD
-  const char* ae = CREID_KNOB_ENV("CREID_C64_ABL");             // 1 no multiplies, 2 no input loads, 4 no staging / copy-out, 8 no stores
-  const int abl = ae ? atoi(ae) : 0;
-#else
-  const int abl = 0;
-#endif
+  r.family = CONV_C64; r.bn = 64; r.tw = tile2d ? 16 : Wd; r.t2d = tile2d ? 1 : 0;
+  r.tiles_m = n_tiles; r.tiles_n = 1;
+  r.grid = (unsigned)wgs; r.block = 512;
+  r.abl = k.c64_abl;                                   // 1 no multiplies, 2 no input loads, 4 no staging / copy-out, 8 no stores
+  return true;
+}
+
+void launch_conv3x3_c64(const ConvRoute& r, const IGemmGeom& g, const ConvPtrs& p, hipStream_t s) {
 #define CREID_C64_LAUNCH(W_, ET_, T2D_)                                                                             \
-  hipLaunchKernelGGL((conv3x3_c64_kernel<W_, ET_, T2D_>), grid, block, 0, s, (const unsigned short*)src, M, H, Wd,   \
-                     (const unsigned short*)wgt, (unsigned short*)out, bn_part, epi_scale, epi_shift, epi_relu, n_tiles, abl)
-  if (tile2d) { if (dtype == CREID_F16) CREID_C64_LAUNCH(16, F16T, true); else CREID_C64_LAUNCH(16, Bf16T, true); }
-  else if (Wd == 32) { if (dtype == CREID_F16) CREID_C64_LAUNCH(32, F16T, false); else CREID_C64_LAUNCH(32, Bf16T, false); }
-  else { if (dtype == CREID_F16) CREID_C64_LAUNCH(64, F16T, false); else CREID_C64_LAUNCH(64, Bf16T, false); }
+  hipLaunchKernelGGL((conv3x3_c64_kernel<W_, ET_, T2D_>), dim3(r.grid), dim3(r.block), 0, s, (const unsigned short*)p.src, g.M, g.OH, \
+                     g.OW, (const unsigned short*)p.wgt, (unsigned short*)p.out, p.bn_part, g.epi_scale, g.epi_shift, g.epi_relu,    \
+                     r.tiles_m, r.abl)
+  if (r.t2d) { if (r.dtype == CREID_F16) CREID_C64_LAUNCH(16, F16T, true); else CREID_C64_LAUNCH(16, Bf16T, true); }
+  else if (r.tw == 32) { if (r.dtype == CREID_F16) CREID_C64_LAUNCH(32, F16T, false); else CREID_C64_LAUNCH(32, Bf16T, false); }
+  else { if (r.dtype == CREID_F16) CREID_C64_LAUNCH(64, F16T, false); else CREID_C64_LAUNCH(64, Bf16T, false); }
 #undef CREID_C64_LAUNCH
-  return (int)hipGetLastError();
 }

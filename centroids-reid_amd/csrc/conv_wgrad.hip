@@ -16,10 +16,7 @@
 // f32 (parity mode): K-major LDS is the natural layout for v_mfma_f32_32x32x2_f32.
 // The pixel range is split over gridDim.y workgroups; fp32 partial tiles go to the workspace and
 // wgrad_reduce_kernel<SL> sums them in a fixed order (deterministic) and scatters into the OIHW fp32 gradient.
-#include "conv_common.hpp"
-#include "wgrad_reduce.hpp"
-#include "bn_fin.hpp"
-#include "tune.hpp"
+#include "conv_route.hpp"
 #include <stdlib.h>
 #include <atomic>
 
@@ -1053,11 +1050,10 @@ __global__ __launch_bounds__(256) void wgrad_reduce_taps_kernel(const float* __r
 }
 
 // ------------------------------------------------------------------------------------ host
-static int ilog2x(int64_t v) { int l = 0; while ((1LL << l) < v) ++l; return ((1LL << l) == v) ? l : -1; }
+int wgrad_dma_env() { static const int v = [] { const char* e = getenv("CREID_WGRAD_DMA"); return e ? atoi(e) : 1; }(); return v; }
 
-struct WgradPlan { int tm, tn, tiles, tiles_k, splits, m_per_split, xcd, stages, ws, kg, taps; };   // stages / ws / kg: 0 = default; taps: wgrad_bf16_taps_kernel
-
-static WgradPlan plan_wgrad(int M, int NCO, int K, int dtype, int stride = 1) {
+// tile, split count and XCD form: from a measured plan, else the built-in rule (family, ring and grid: plan_wgrad_route)
+static WgradPlan plan_wgrad(int M, int NCO, int K, int dtype, int stride = 1, bool peek = false) {
   // The fp32 partial tiles cost  workgroups x TM x TN x 8 bytes  of traffic per layer (write + re-read by the
   // reduce).  Measured (r01): shrinking the tile to cut that traffic LOSES (6147 vs 6370 img/s) -- the larger
   // tile's MFMA/LDS efficiency matters more and the partials mostly stay in the 256 MB Infinity Cache -- so the
@@ -1068,13 +1064,15 @@ static WgradPlan plan_wgrad(int M, int NCO, int K, int dtype, int stride = 1) {
   static const int max_splits_pref = [] { const char* e = getenv("CREID_WGRAD_MAX_SPLITS"); int v = e ? atoi(e) : 0; return v > 0 ? v : (1 << 30); }();
   const int ks = creid_is16(dtype) ? WKS : WKF;
   const int cand[3][2] = {{128, 128}, {128, 64}, {64, 64}};
-  WgradPlan p;
-  p.stages = 0; p.ws = 0; p.kg = 0; p.taps = 0;
+  static const int xcd_mode = [] { const char* e = getenv("CREID_WGRAD_XCD"); return e ? atoi(e) : 1; }();
+  WgradPlan p{};
   TunePlan tp;
-  const bool have_plan = creid_is16(dtype) && creid_tune_lookup(CREID_TUNE_WGRAD, M, NCO, K, stride << 1, tp);
-  if (have_plan && !((tp.p0 == 64 || tp.p0 == 128) && (tp.p1 == 64 || tp.p1 == 128) && NCO % tp.p0 == 0 && K % tp.p1 == 0 && tp.p2 >= 1))
-    creid_tune_declined(CREID_TUNE_WGRAD, M, NCO, K, stride << 1);      // a word this shape cannot run: the built-in rule below
-  else if (have_plan) {
+  const bool have_plan = creid_is16(dtype) && (peek ? creid_tune_peek : creid_tune_lookup)(CREID_TUNE_WGRAD, M, NCO, K, stride << 1, tp);
+  p.plan_state = have_plan ? 1 : 0;
+  if (have_plan && !((tp.p0 == 64 || tp.p0 == 128) && (tp.p1 == 64 || tp.p1 == 128) && NCO % tp.p0 == 0 && K % tp.p1 == 0 && tp.p2 >= 1)) {
+    p.plan_state = 2;                                                   // a word this shape cannot run: the built-in rule below
+    if (!peek) creid_tune_declined(CREID_TUNE_WGRAD, M, NCO, K, stride << 1);
+  } else if (have_plan) {
     // measured plan for this shape: tile tp.p0 x tp.p1, tp.p2 = pixel splits | ring depth << 16 | producer/consumer << 20 |
     // two k-groups << 21
     p.tm = tp.p0; p.tn = tp.p1;
@@ -1087,7 +1085,6 @@ static WgradPlan plan_wgrad(int M, int NCO, int K, int dtype, int stride = 1) {
     if (splits > max_splits) splits = max_splits;
     p.m_per_split = ((M + splits - 1) / splits + ks - 1) / ks * ks;
     p.splits = (M + p.m_per_split - 1) / p.m_per_split;
-    static const int xcd_mode = [] { const char* e = getenv("CREID_WGRAD_XCD"); return e ? atoi(e) : 1; }();
     p.xcd = (xcd_mode && p.splits >= 8) ? 1 : 0;
     return p;
   }
@@ -1101,7 +1098,6 @@ static WgradPlan plan_wgrad(int M, int NCO, int K, int dtype, int stride = 1) {
     int splits = (target + p.tiles - 1) / p.tiles;
     // XCD placement (see wgrad_bf16_dma_kernel): a multiple of 8 splits, at least 8, so that every XCD owns whole
     // pixel ranges; CREID_WGRAD_XCD=0 keeps the round-1 rule
-    static const int xcd_mode = [] { const char* e = getenv("CREID_WGRAD_XCD"); return e ? atoi(e) : 1; }();
     p.xcd = 0;
     if (xcd_mode && creid_is16(dtype)) {
       if (splits >= 8) { splits = (splits + 4) / 8 * 8; p.xcd = 1; }                     // nearest multiple of 8
@@ -1120,12 +1116,6 @@ static WgradPlan plan_wgrad(int M, int NCO, int K, int dtype, int stride = 1) {
 
 // ---- the tap-fused route (wgrad_bf16_taps_kernel): coverage, split count and workspace are decided HERE for every caller
 // (creid_conv2d_wgrad_workspace_bytes, wgrad_make_reduce_job, run_wgrad), so the three always agree
-struct WgradShape { int kh, kw, pad, cin, OH, OW, SH, SW; };
-
-static WgradShape wgrad_shape_of(const creid_conv_desc* d) {
-  return WgradShape{d->kh, d->kw, d->pad, (int)d->in_c, (int)d->out_h, (int)d->out_w, (int)d->in_h, (int)d->in_w};
-}
-
 static std::atomic<int64_t> g_taps_launches{0};
 
 static bool wgrad_taps_covers(int M, int NCO, int dtype, int stride, const WgradShape& sh) {
@@ -1137,49 +1127,76 @@ static bool wgrad_taps_covers(int M, int NCO, int dtype, int stride, const Wgrad
   return (sh.OH * sh.OW) % TPK == 0 && M > 0 && M % (sh.OH * sh.OW) == 0;
 }
 
-static WgradPlan plan_wgrad_route(int M, int NCO, int K, int dtype, int stride, const WgradShape& sh) {
-  WgradPlan p = plan_wgrad(M, NCO, K, dtype, stride);      // (the registry lookup counts its hit / decline on either route)
-  const char* e = CREID_KNOB_ENV("CREID_WGRAD_TAPS");      // read per call: tests toggle it
-  if ((e && atoi(e) == 0) || !wgrad_taps_covers(M, NCO, dtype, stride, sh)) return p;
-  // One workgroup per CU (its LDS ring is > 80 KB), each writing 9 x 64 x 64 fp32 partials (147 KB) that the split reduction --
-  // carried by the next data-gradient launch -- reads back.  Measured (profiles/wgrad_taps.md): with 1 or 4 tile-groups (64 and 128
-  // channels) 256 workgroups of 4 k-steps make that launch 2-8 us slower than the tile kernel's partials did; ~170 workgroups of
-  // 6 k-steps keep the kernel's gain and leave the carrier where it was.  16 and 64 tile-groups: one workgroup per CU.
-  p.taps = 1; p.tm = 64; p.tn = 64; p.stages = 3; p.ws = 0; p.kg = 0; p.xcd = 1;
-  p.tiles_k = sh.cin / 64;
-  p.tiles = (NCO / 64) * p.tiles_k;
-  const int steps = M / TPK;
-  // CREID_WGRAD_TAPS_WGS: the workgroup target, for experiments and for tests that need many k-steps per workgroup at small shapes
-  const char* we = CREID_KNOB_ENV("CREID_WGRAD_TAPS_WGS");
-  const int target = (we && atoi(we) > 0) ? atoi(we) : (p.tiles <= 4 ? 192 : 256);
-  int splits = (target + p.tiles / 2) / p.tiles;
-  if (splits > steps) splits = steps;
-  if (splits < 1) splits = 1;
-  const int per = (steps + splits - 1) / splits;
-  p.m_per_split = per * TPK;
-  p.splits = (steps + per - 1) / per;
+// 1-D XCD grid: every XCD owns whole pixel ranges (>= 8 splits, or a split count that does not divide 8), else shares them
+static unsigned wgrad_xcd_grid(const WgradPlan& p, bool ranged) {
+  const int share = ranged ? 1 : 8 / p.splits;
+  return ranged ? (unsigned)(p.tiles * ((p.splits + 7) / 8) * 8) : (unsigned)(8 * ((p.tiles + share - 1) / share));
+}
+
+// Everything about a weight-gradient launch: the tile plan, then kernel family, ring, k-groups, grid and whether the BatchNorm
+// finalize job can ride.  creid_conv2d_wgrad_workspace_bytes, wgrad_make_reduce_job and run_wgrad all ask here, so they agree.
+WgradPlan plan_wgrad_route(int M, int NCO, int K, int dtype, int stride, const WgradShape& sh, int fin_nblocks, bool peek) {
+  WgradPlan p = plan_wgrad(M, NCO, K, dtype, stride, peek);      // (the registry lookup counts its hit / decline on either route)
+  const unsigned nf8 = (unsigned)((fin_nblocks + 7) & ~7);
+  const char* e = CREID_KNOB_ENV("CREID_WGRAD_TAPS");            // read per call: tests toggle it
+  if (!(e && atoi(e) == 0) && wgrad_taps_covers(M, NCO, dtype, stride, sh)) {
+    // One workgroup per CU (its LDS ring is > 80 KB), each writing 9 x 64 x 64 fp32 partials (147 KB) that the split reduction --
+    // carried by the next data-gradient launch -- reads back.  Measured (profiles/wgrad_taps.md): with 1 or 4 tile-groups (64 and 128
+    // channels) 256 workgroups of 4 k-steps make that launch 2-8 us slower than the tile kernel's partials did; ~170 workgroups of
+    // 6 k-steps keep the kernel's gain and leave the carrier where it was.  16 and 64 tile-groups: one workgroup per CU.
+    p.taps = 1; p.tm = 64; p.tn = 64; p.stages = 3; p.ws = 0; p.kg = 0; p.xcd = 1;
+    p.tiles_k = sh.cin / 64;
+    p.tiles = (NCO / 64) * p.tiles_k;
+    const int steps = M / TPK;
+    // CREID_WGRAD_TAPS_WGS: the workgroup target, for experiments and for tests that need many k-steps per workgroup at small shapes
+    const char* we = CREID_KNOB_ENV("CREID_WGRAD_TAPS_WGS");
+    const int target = (we && atoi(we) > 0) ? atoi(we) : (p.tiles <= 4 ? 192 : 256);
+    int splits = (target + p.tiles / 2) / p.tiles;
+    if (splits > steps) splits = steps;
+    if (splits < 1) splits = 1;
+    const int per = (steps + splits - 1) / splits;
+    p.m_per_split = per * TPK;
+    p.splits = (steps + per - 1) / per;
+    p.family = WGRAD_TAPS; p.ns = 3; p.kgroups = 1;
+    p.fin_rides = fin_nblocks > 0;                               // always: the grid is 1-D
+    p.gx = wgrad_xcd_grid(p, p.splits >= 8 || (8 % p.splits) != 0) + nf8; p.gy = 1; p.block = 512;
+  } else if (creid_is16(dtype) && wgrad_dma_env() && (sh.span >= p.tn || sh.stem)) {
+    static const int use_ws_env = [] { const char* e = getenv("CREID_WGRAD_WS"); return e ? atoi(e) : 0; }();
+    static const int stages_env = [] { const char* e = getenv("CREID_WGRAD_STAGES"); int v = e ? atoi(e) : 0; return (v >= 2 && v <= 4) ? v : 2; }();
+    static const int kg_env = [] { const char* e = getenv("CREID_WGRAD_KG"); return e ? atoi(e) : 0; }();
+    const int use_ws = p.ws ? 1 : use_ws_env;
+    const int stages = (p.stages >= 2 && p.stages <= 4) ? p.stages : stages_env;
+    const bool kg2 = (p.kg || kg_env == 2) && !use_ws && !sh.stem;
+    const bool kg3_fits = 2 * 3 * (p.tm + p.tn) * 128 <= 160 * 1024;
+    p.family = WGRAD_DMA;
+    p.wsk = !kg2 && use_ws && !sh.stem;
+    p.kgroups = kg2 ? 2 : 1;
+    p.ns = kg2 ? ((stages >= 3 && kg3_fits) ? 3 : 2) : (p.wsk ? 2 : stages);
+    p.block = (kg2 || p.wsk) ? 512 : 256;
+    p.fin_rides = fin_nblocks > 0 && p.xcd;                      // the carried job needs the 1-D grid
+    if (p.xcd) { p.gx = wgrad_xcd_grid(p, p.splits >= 8) + (p.fin_rides ? nf8 : 0u); p.gy = 1; }
+    else { p.gx = (unsigned)p.tiles; p.gy = (unsigned)p.splits; }
+  } else if (dtype == CREID_F16) {
+    p.family = WGRAD_NONE; p.err = CREID_E_SHAPE;                // (no register-staged f16 fallback: refused, not mis-run)
+  } else {
+    p.family = dtype == CREID_BF16 ? WGRAD_REG_BF16 : WGRAD_F32;
+    p.gx = (unsigned)p.tiles; p.gy = (unsigned)p.splits; p.block = 256;
+  }
+  if (dtype == CREID_F16 && !wgrad_dma_env()) { p.family = WGRAD_NONE; p.err = CREID_E_DTYPE; }   // f16: the LDS-DMA kernels only
   return p;
 }
 
-// returns true when the launch carried the BatchNorm-backward finalize job (always, when one is given: the grid is 1-D)
-static bool launch_wgrad_taps(const IGemmGeom& g, const void* dy, const void* x, int NCO, float* ws, const WgradPlan& p, int dtype,
-                              hipStream_t s, const BnBwdFinJob* fin_in) {
-  BnBwdFinJob fin{};
-  if (fin_in) fin = *fin_in;
-  const unsigned nf8 = fin.partial ? (unsigned)((fin.nblocks + 7) & ~7) : 0u;
-  const bool ranged = p.splits >= 8 || (8 % p.splits) != 0;
-  const int share = ranged ? 1 : 8 / p.splits;
-  const unsigned nwg = ranged ? (unsigned)(p.tiles * ((p.splits + 7) / 8) * 8) : (unsigned)(8 * ((p.tiles + share - 1) / share));
+static void launch_wgrad_taps(const IGemmGeom& g, const void* dy, const void* x, int NCO, float* ws, const WgradPlan& p, int dtype,
+                              hipStream_t s, const BnBwdFinJob& fin) {
   const int cin = 1 << g.log2span;
 #define CREID_WT_LAUNCH(OW_, ET_)                                                                                          \
-  hipLaunchKernelGGL((wgrad_bf16_taps_kernel<OW_, ET_>), dim3(nwg + nf8), dim3(512), 0, s, (const unsigned short*)dy,      \
+  hipLaunchKernelGGL((wgrad_bf16_taps_kernel<OW_, ET_>), dim3(p.gx), dim3(p.block), 0, s, (const unsigned short*)dy,       \
                      (const unsigned short*)x, g.M, g.OH, cin, NCO, ws, p.tiles, p.tiles_k, p.splits, p.m_per_split, fin)
 #define CREID_WT_OW(OW_) do { if (dtype == CREID_F16) CREID_WT_LAUNCH(OW_, F16T); else CREID_WT_LAUNCH(OW_, Bf16T); } while (0)
   if (g.OW == 8) CREID_WT_OW(8); else if (g.OW == 16) CREID_WT_OW(16); else CREID_WT_OW(32);
 #undef CREID_WT_OW
 #undef CREID_WT_LAUNCH
   g_taps_launches.fetch_add(1, std::memory_order_relaxed);
-  return fin.partial != nullptr;
 }
 
 __global__ __launch_bounds__(256) void bn_bwd_finalize_job_kernel(BnBwdFinJob j) {
@@ -1187,62 +1204,43 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_job_kernel(BnBwdFinJob j)
   bn_bwd_finalize_block<256>(j, (int)blockIdx.x, fin_lds);
 }
 
+// fin: the BatchNorm-backward finalize job (bn_fin.hpp) where the plan says it rides in the first workgroups, else an empty job
 template <int TM, int TN>
-// returns true when the launch carried the BatchNorm-backward finalize job `fin_in` (bn_fin.hpp) in its first workgroups
-static bool launch_wgrad_t(const IGemmGeom& g, const void* dy, const void* x, int NCO, float* ws, const WgradPlan& p,
-                           int dtype, hipStream_t s, const BnBwdFinJob* fin_in = nullptr) {
-  dim3 grid((unsigned)p.tiles, (unsigned)p.splits), block(256);
-  const bool xcd_on = p.xcd != 0;
-  const int xt = xcd_on ? p.tiles : 0;
-  const int share = p.splits >= 8 ? 1 : 8 / p.splits;
-  BnBwdFinJob fin{};
-  if (fin_in && xcd_on) fin = *fin_in;                            // the carried job needs the 1-D grid
-  const unsigned nf8 = fin.partial ? (unsigned)((fin.nblocks + 7) & ~7) : 0u;
-  const dim3 grid_x((p.splits >= 8 ? (unsigned)(p.tiles * ((p.splits + 7) / 8) * 8) : (unsigned)(8 * ((p.tiles + share - 1) / share))) + nf8);
-  const dim3 grid_dma = xcd_on ? grid_x : grid;
-  static const int use_dma = [] { const char* e = getenv("CREID_WGRAD_DMA"); return e ? atoi(e) : 1; }();
+static void launch_wgrad_t(const IGemmGeom& g, const void* dy, const void* x, int NCO, float* ws, const WgradPlan& p,
+                           int dtype, hipStream_t s, const BnBwdFinJob& fin) {
+  const dim3 grid(p.gx, p.gy), block(p.block);
+  const int xt = p.xcd ? p.tiles : 0;
 #ifdef CREID_ABL_BUILD
   static const int wg_abl = creid_ablation_env("CREID_WGRAD_ABL");   // 1: no MFMA, 2: no DMA after the first k-tile, 4: no fragment reads either
 #else
   const int wg_abl = 0;                                              // (the switches exist in the ablation build only: conv_common.hpp)
 #endif
-  static const int stages_env = [] { const char* e = getenv("CREID_WGRAD_STAGES"); int v = e ? atoi(e) : 0; return (v >= 2 && v <= 4) ? v : 2; }();
-  static const int stem_dma = [] { const char* e = getenv("CREID_STEM_DMA"); return e ? atoi(e) : 1; }();
-  const bool stem_geom = g.log2span == 5 && !g.check_bounds && g.kw == 1 && g.stride == 2 && g.pad == 0 && stem_dma;
-  if (creid_is16(dtype) && use_dma && ((1 << g.log2span) >= TN || stem_geom)) {
-    static const int use_ws_env = [] { const char* e = getenv("CREID_WGRAD_WS"); return e ? atoi(e) : 0; }();
-    const int use_ws = p.ws ? 1 : use_ws_env;
-    const int stages = (p.stages >= 2 && p.stages <= 4) ? p.stages : stages_env;
-    static const int kg_env = [] { const char* e = getenv("CREID_WGRAD_KG"); return e ? atoi(e) : 0; }();
-    const bool kg2 = (p.kg || kg_env == 2) && !use_ws && !stem_geom;
+  if (p.family == WGRAD_DMA) {
     constexpr bool kg3_fits = 2 * 3 * (TM + TN) * 128 <= 160 * 1024;
-#define CREID_WG_LAUNCH(NS_, WS_, KG_, BLOCK_)                                                                                   \
+#define CREID_WG_LAUNCH(NS_, WS_, KG_)                                                                                            \
     do {                                                                                                                          \
       if (dtype == CREID_F16)                                                                                                     \
-        hipLaunchKernelGGL((wgrad_bf16_dma_kernel<TM, TN, NS_, WS_, KG_, F16T>), grid_dma, BLOCK_, 0, s, g, (const unsigned short*)dy, \
+        hipLaunchKernelGGL((wgrad_bf16_dma_kernel<TM, TN, NS_, WS_, KG_, F16T>), grid, block, 0, s, g, (const unsigned short*)dy, \
                            (const unsigned short*)x, NCO, ws, p.tiles_k, p.m_per_split, xt, p.splits, fin, wg_abl);               \
       else                                                                                                                        \
-        hipLaunchKernelGGL((wgrad_bf16_dma_kernel<TM, TN, NS_, WS_, KG_, Bf16T>), grid_dma, BLOCK_, 0, s, g, (const unsigned short*)dy, \
+        hipLaunchKernelGGL((wgrad_bf16_dma_kernel<TM, TN, NS_, WS_, KG_, Bf16T>), grid, block, 0, s, g, (const unsigned short*)dy, \
                            (const unsigned short*)x, NCO, ws, p.tiles_k, p.m_per_split, xt, p.splits, fin, wg_abl);               \
     } while (0)
-    if (kg2 && stages >= 3 && kg3_fits) {
-      if constexpr (kg3_fits) CREID_WG_LAUNCH(3, false, 2, dim3(512));
-    } else if (kg2) CREID_WG_LAUNCH(2, false, 2, dim3(512));
-    else if (use_ws && !stem_geom) CREID_WG_LAUNCH(2, true, 1, dim3(512));
-    else if (stages == 2) CREID_WG_LAUNCH(2, false, 1, block);
-    else if (stages == 3) CREID_WG_LAUNCH(3, false, 1, block);
-    else CREID_WG_LAUNCH(4, false, 1, block);
+    if (p.kgroups == 2 && p.ns == 3) {
+      if constexpr (kg3_fits) CREID_WG_LAUNCH(3, false, 2);
+    } else if (p.kgroups == 2) CREID_WG_LAUNCH(2, false, 2);
+    else if (p.wsk) CREID_WG_LAUNCH(2, true, 1);
+    else if (p.ns == 2) CREID_WG_LAUNCH(2, false, 1);
+    else if (p.ns == 3) CREID_WG_LAUNCH(3, false, 1);
+    else CREID_WG_LAUNCH(4, false, 1);
 #undef CREID_WG_LAUNCH
-    return fin.partial != nullptr;
   }
-  else if (dtype == CREID_F16) return false;                     // (run_wgrad refuses f16 shapes the DMA kernels do not cover)
-  else if (dtype == CREID_BF16)
+  else if (p.family == WGRAD_REG_BF16)
     hipLaunchKernelGGL((wgrad_bf16_kernel<TM, TN>), grid, block, 0, s, g, (const unsigned short*)dy,
                        (const unsigned short*)x, NCO, ws, p.tiles_k, p.m_per_split);
   else
     hipLaunchKernelGGL((wgrad_f32_kernel<TM, TN>), grid, block, 0, s, g, (const float*)dy, (const float*)x, NCO, ws,
                        p.tiles_k, p.m_per_split);
-  return false;
 }
 
 static int run_wgrad(const IGemmGeom& g, const void* dy, const void* x, int NCO, float* dw, int kw_taps, int cpitch,
@@ -1250,30 +1248,24 @@ static int run_wgrad(const IGemmGeom& g, const void* dy, const void* x, int NCO,
                      int phases = 3, const BnBwdFinJob* fin = nullptr) {
   if (!creid_is16(dtype) && dtype != CREID_F32) return CREID_E_DTYPE;
   // f16 exists in the LDS-DMA kernels only (no register-staged fallback): shapes those do not cover are refused, not mis-run
-  if (dtype == CREID_F16) {
-    static const int dma_on = [] { const char* e = getenv("CREID_WGRAD_DMA"); return e ? atoi(e) : 1; }();
-    if (!dma_on) return CREID_E_DTYPE;
-  }
+  if (dtype == CREID_F16 && !wgrad_dma_env()) return CREID_E_DTYPE;
   // (the tap-fused route needs the plain NHWC gather: the stem's packed kernel rows and pre-padded image stay on the tile kernels)
-  const WgradShape shp{(cpitch == cin && kw_taps == kw && g.check_bounds && (1 << g.log2span) == cin) ? kh : 0, kw, g.pad, cin, g.OH, g.OW, g.SH, g.SW};
-  const WgradPlan p = plan_wgrad_route(g.M, NCO, g.K, dtype, g.stride, shp);
-  if (dtype == CREID_F16 && (phases & 1) && !p.taps) {
-    // (the same predicate launch_wgrad_t routes by, CREID_STEM_DMA included: with the stem's DMA path switched off an f16 stem has
-    // no kernel at all -- refuse it here instead of summing an unwritten workspace into dw)
-    static const int stem_dma = [] { const char* e = getenv("CREID_STEM_DMA"); return e ? atoi(e) : 1; }();
-    const bool stem_geom = g.log2span == 5 && !g.check_bounds && g.kw == 1 && g.stride == 2 && g.pad == 0 && stem_dma;
-    if (!((1 << g.log2span) >= p.tn || stem_geom)) return CREID_E_SHAPE;
-  }
+  const WgradShape shp{(cpitch == cin && kw_taps == kw && g.check_bounds && (1 << g.log2span) == cin) ? kh : 0, kw, g.pad, cin, g.OH, g.OW,
+                       g.SH, g.SW, 1 << g.log2span, conv_is_stem_geom(g)};
+  const WgradPlan p = plan_wgrad_route(g.M, NCO, g.K, dtype, g.stride, shp, fin ? fin->nblocks : 0);
+  // (a shape without a kernel -- an f16 stem with its DMA path switched off -- is refused here instead of summing an unwritten
+  // workspace into dw)
+  if ((phases & 1) && p.family == WGRAD_NONE) return p.err;
   const size_t need = (size_t)p.splits * NCO * g.K * sizeof(float);
   if (ws_bytes < need) return CREID_E_WS;
   if (phases & 1) {
-    bool carried;
-    if (p.taps) carried = launch_wgrad_taps(g, dy, x, NCO, (float*)ws, p, dtype, s, fin);
-    else if (p.tm == 128 && p.tn == 128) carried = launch_wgrad_t<128, 128>(g, dy, x, NCO, (float*)ws, p, dtype, s, fin);
-    else if (p.tm == 128 && p.tn == 64) carried = launch_wgrad_t<128, 64>(g, dy, x, NCO, (float*)ws, p, dtype, s, fin);
-    else if (p.tm == 64 && p.tn == 128) carried = launch_wgrad_t<64, 128>(g, dy, x, NCO, (float*)ws, p, dtype, s, fin);
-    else carried = launch_wgrad_t<64, 64>(g, dy, x, NCO, (float*)ws, p, dtype, s, fin);
-    if (fin && !carried)                                         // kernel variants without the carrier: stand-alone launch
+    const BnBwdFinJob ride = (fin && p.fin_rides) ? *fin : BnBwdFinJob{};
+    if (p.family == WGRAD_TAPS) launch_wgrad_taps(g, dy, x, NCO, (float*)ws, p, dtype, s, ride);
+    else if (p.tm == 128 && p.tn == 128) launch_wgrad_t<128, 128>(g, dy, x, NCO, (float*)ws, p, dtype, s, ride);
+    else if (p.tm == 128 && p.tn == 64) launch_wgrad_t<128, 64>(g, dy, x, NCO, (float*)ws, p, dtype, s, ride);
+    else if (p.tm == 64 && p.tn == 128) launch_wgrad_t<64, 128>(g, dy, x, NCO, (float*)ws, p, dtype, s, ride);
+    else launch_wgrad_t<64, 64>(g, dy, x, NCO, (float*)ws, p, dtype, s, ride);
+    if (fin && !p.fin_rides)                                     // kernel variants without the carrier: stand-alone launch
       hipLaunchKernelGGL(bn_bwd_finalize_job_kernel, dim3((unsigned)fin->nblocks), dim3(256), 0, s, *fin);
   }
   if (!(phases & 2)) return (int)hipGetLastError();
@@ -1412,7 +1404,7 @@ int creid_conv2d_wgrad_reduce_job(const creid_conv_desc* d, float* dw_oihw, int 
 static int conv_wgrad_phases(const creid_conv_desc* d, const void* x, const void* dy, float* dw_oihw, int accumulate,
                              void* ws, size_t ws_bytes, int dtype, void* stream, int phases, const BnBwdFinJob* fin) {
   CREID_CHECK_ARG(d && ws);
-  if (ilog2x(d->in_c) < 0 || d->in_c < 64 || d->out_c % 64 != 0) return CREID_E_SHAPE;
+  if (igemm_ilog2(d->in_c) < 0 || d->in_c < 64 || d->out_c % 64 != 0) return CREID_E_SHAPE;
   IGemmGeom g = fwd_geom(d);
   { static const int noinc = [] { const char* e = getenv("CREID_WGRAD_NOINC"); return e ? atoi(e) : 0; }(); if (noinc) g.check_bounds = 2; }
   return run_wgrad(g, dy, x, (int)d->out_c, dw_oihw, d->kw, (int)d->in_c, (int)d->in_c, d->kh, d->kw, accumulate, ws,

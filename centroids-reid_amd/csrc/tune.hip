@@ -25,6 +25,13 @@ bool creid_tune_lookup(int kind, int64_t a, int64_t b, int64_t c, int64_t d, Tun
   return true;
 }
 
+bool creid_tune_peek(int kind, int64_t a, int64_t b, int64_t c, int64_t d, TunePlan& out) {
+  std::lock_guard<std::mutex> g(mu());
+  const Entry* e = find(kind, a, b, c, d);
+  if (e) out = e->plan;
+  return e != nullptr;
+}
+
 void creid_tune_declined(int kind, int64_t a, int64_t b, int64_t c, int64_t d) {
   std::lock_guard<std::mutex> g(mu());
   if (Entry* e = find(kind, a, b, c, d)) ++e->declines;

@@ -11,5 +11,7 @@ struct TunePlan { int p0, p1, p2; };
 
 // returns true and fills `out` when (kind, a, b, c, d) has a registered plan
 bool creid_tune_lookup(int kind, int64_t a, int64_t b, int64_t c, int64_t d, TunePlan& out);
+// the same answer without counting a hit (creid_conv_route_describe: tests measure counter deltas around launches)
+bool creid_tune_peek(int kind, int64_t a, int64_t b, int64_t c, int64_t d, TunePlan& out);
 // records that a plan creid_tune_lookup returned for this key was not applied (creid_tune_count, what = 1)
 void creid_tune_declined(int kind, int64_t a, int64_t b, int64_t c, int64_t d);

@@ -694,6 +694,23 @@ int64_t creid_igemm_halo_launches(void);
  * per (64 co x 64 ci x nine taps) over its pixel range.  CREID_WGRAD_TAPS=0 (read per call) restores the per-tap tile launches
  * with their split counts and workspace sizes. */
 int64_t creid_wgrad_taps_launches(void);
+/* Which kernel a convolution call would run, as one line of text -- decided by the same code the launchers run, without
+ * launching: host only, no device API, the plan registry is peeked at (creid_tune_count does not move), so it answers in a
+ * process that has no GPU (the CU count behind the persistent grids then falls back to the MI355X's 256).
+ *   op: CREID_ROUTE_FWD / DGRAD / WGRAD take d; CREID_ROUTE_STEM_FWD / STEM_WGRAD read (batch, in_h, in_w) = (B, H, W) of d.
+ *   feat_bits: the facts of the call that steer routing, CREID_ROUTE_* below.  CREID_ROUTE_JOB: a carried job comes with the
+ *     call, of (feat_bits >> 16) workgroups -- the previous weight gradient's split reduction for a data gradient, the
+ *     BatchNorm-backward finalize job for a weight gradient (its partials launch).
+ *   buf[n] receives, NUL-terminated,
+ *       [pre=wred(N) ; ]<kernel instantiation> grid=(x,y,1) block=B lds=L[ parity=1][ wred=N][ fin=N][ ; post=fin(N)] | plan=...
+ *     or  rc=<CREID_E_*> | plan=...  where no kernel covers the call.  pre / post: a job that cannot ride runs as its own launch
+ *     before / after; wred / fin: it rides in the grid.  plan=none | hit | declined (what creid_tune_count would record), then
+ *     the key slot, the planned and the running kernel id (forward / data gradient) or the split plan (weight gradient).
+ * Returns 0, CREID_E_ARG, or CREID_E_WS when n is too small (the text is then truncated). */
+enum { CREID_ROUTE_FWD = 0, CREID_ROUTE_DGRAD = 1, CREID_ROUTE_WGRAD = 2, CREID_ROUTE_STEM_FWD = 3, CREID_ROUTE_STEM_WGRAD = 4 };
+enum { CREID_ROUTE_ADD = 1, CREID_ROUTE_ADD_COMPACT = 2, CREID_ROUTE_ADD_MASK = 4, CREID_ROUTE_STATS = 8, CREID_ROUTE_AFFINE = 16,
+       CREID_ROUTE_BNRED = 32, CREID_ROUTE_BNRED_PER_IMAGE = 64, CREID_ROUTE_JOB = 128 };
+int creid_conv_route_describe(const creid_conv_desc* d, int op, int feat_bits, int dtype, char* buf, size_t n);
 int creid_conv2d_fwd_nhwc(const creid_conv_desc* d, const void* x, const void* w_krsc, void* y,
                           float* bn_partial, int dtype, void* stream);
 /* Eval-mode forward of conv -> BatchNorm -> (+ residual) -> (ReLU) in ONE launch (modelling/backbones/resnet.py:67-87 under
