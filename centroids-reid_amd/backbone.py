@@ -10,8 +10,8 @@ wgrad); torch only provides memory, the stream and the autograd hook at the modu
 """
 from __future__ import annotations
 
-import contextlib
 import ctypes as C
+import dataclasses
 import math
 import os
 import weakref
@@ -245,6 +245,95 @@ class _ConvUnit:
         self.fold = None               # eval mode: BatchNorm as a per-channel affine, float [2][cout] (view of one flat buffer)
 
 
+@dataclasses.dataclass(frozen=True)
+class Schedule:
+    """Which launches the engine issues and in which order, decided once per engine by resolve_schedule()."""
+    # training forward writes each ReLU's mask as bits (1 byte per 8 channels); the BatchNorm backward and the fused
+    # data-gradient epilogue read that instead of re-reading the activation (CREID_RELU_BITMASK=0: read the activation)
+    relu_bitmask: bool
+    stem_fuse_pool: bool           # CREID_STEM_FUSE: bn1 + maxpool in one pass (38 vs 51 us)
+    stem_pool_fused: bool          # CREID_STEM_POOL, eval: conv1 + bn1 + maxpool in one launch
+    pair_fused: bool               # CREID_PAIR_FUSE, eval, layer1: conv3 of block i + conv1 of block i + 1
+    # CREID_STEM_FUSE_BWD: the backward counterpart (max-pool gradient gathered inside the BN backward passes) is correct but
+    # slower: the gather is VALU-bound and runs twice (146 vs 116 us, tools/debug/stem_tail_probe.py) -- off by default
+    stem_fuse_pool_bwd: bool
+    drop_gm: bool                  # CREID_DROP_GM, A/B knob: 0 = bn3's backward still writes the masked copy
+    fuse_bn_reduce: bool           # CREID_FUSE_BN_REDUCE: BatchNorm-backward column sums in the data-gradient epilogue (16-bit, DMA)
+    # eval-mode forward: BatchNorm (running statistics = constants) folded into the producing convolution's epilogue --
+    # one launch per conv instead of conv -> finalize -> apply (CREID_EVAL_FOLD=0: the three-launch schedule).  The folded epilogue
+    # of the 16-bit types lives in the LDS-DMA kernels only: with CREID_IGEMM_DMA=0 a bf16 forward takes the three-launch schedule
+    # instead of failing.  bf16x3 exists as the folded forward only: no statistics / apply schedule
+    eval_fold: bool
+    # training forward: bn2 + ReLU applied inside conv3's operand path (creid_conv1x1_bnrelu_fwd) for the bottlenecks whose
+    # width (conv3's input channels, 64 or 128) is listed in CREID_C3_AXF -- the stand-alone apply pass of bn2 disappears; "" = never.
+    # Measured (profiles/r06_bn_apply_in_conv3.md): layer2 (128) gains ~8 us per block, layer1 (64) loses ~3 us per block
+    c3_axf: frozenset
+    ds_reduce2: bool               # CREID_DS_REDUCE2: bn3's backward apply also sums the downsample BatchNorm's columns
+    dual_apply: bool               # CREID_DUAL_APPLY, A/B knob: 0 = separate downsample-BN apply launch
+    # training forward: BatchNorm finalize + apply as ONE launch on layers with at most CREID_FIN_APPLY statistic rows (M <= 8192
+    # by default: 24 launches less per B = 64 step at the same step time -- captured and eager --, bit-identical:
+    # profiles/r05_fin_apply.md; 0 = never); CREID_FIN_APPLY_RB = row blocks of that launch (0 = library rule)
+    fin_apply_rows: int
+    fin_apply_rb: int
+    # weight-gradient split reductions ride in the first workgroups of the NEXT data-gradient launch
+    # (creid_conv2d_dgrad_fused_nhwc) instead of 53 stand-alone 5-25 us launches; CREID_WRED_PIGGYBACK=0: round-1 path.
+    # (bf16x3 weight gradients: partial tiles + the fp32 split reduction in one call, creid_conv2d_wgrad_x3_nhwc)
+    wred_piggyback: bool
+    # CREID_FIN_CARRIER, where a BatchNorm-backward finalize goes between the data gradient that produced its column sums and
+    # the apply that needs them: "wgrad" (the first workgroups of a weight-gradient launch) | "wred" (finalize and the pending split
+    # reduction share one launch; launch order wgrad -> dgrad) | "none" (own launch).  16-bit engines with carried reductions only
+    bnfin_piggyback: bool
+    fin_with_wred: bool
+    wgrad_first: bool              # launch order per convolution: weight gradient, then data gradient (every carrier but "wgrad")
+    heads_bnred: bool              # CREID_HEADS_BNRED: creid_ctl_heads_fused produces the deepest bn3's backward column sums
+
+
+# schedule switches that no longer exist, with the value that still passes (what retired each: docs/history/)
+RETIRED_SWITCHES = (("CREID_WGRAD_STREAM", "0"), ("CREID_REDUCE_STREAM", "0"), ("CREID_EVAL_DS_SIDE", "0"), ("CREID_WPREP_SIDE", "0"),
+                    ("CREID_BN_APPLY_DRY", "0"), ("CREID_WGRAD_FIRST", "0"), ("CREID_CARRIER_MAX_MB", "1e9"),
+                    ("CREID_BNFIN_PIGGYBACK", "1"))
+
+
+def resolve_schedule(dtype, mode=None, trainable=False, env=os.environ):
+    """The Schedule of an engine with activation type `dtype` in compute mode `mode` (None or "bf16x3"): every environment
+    switch is read here, once, and every rule that ties two of them together is applied here."""
+    for name, default in RETIRED_SWITCHES:
+        if env.get(name, default) != default:
+            raise L.CreidError(f"{name}={env[name]} selects a schedule that was retired (docs/history/backbone_schedule_switches.md "
+                               "has the measurement that retired it): unset it")
+
+    def on(name, default="1"):
+        return env.get(name, default) == "1"
+
+    x3 = mode == "bf16x3"
+    is16 = dtype in (torch.bfloat16, torch.float16)
+    dma = on("CREID_IGEMM_DMA")
+    if dtype == torch.float16 and not dma:
+        raise L.CreidError("compute dtype float16 needs the LDS-DMA convolution kernels: unset CREID_IGEMM_DMA=0 "
+                           "(the register-staged fallback kernels exist for bfloat16 and float32 only)")
+    wred_piggyback = on("CREID_WRED_PIGGYBACK") and not (x3 and trainable)
+    carrier = env.get("CREID_FIN_CARRIER", "wgrad") if wred_piggyback and is16 else "none"
+    return Schedule(
+        relu_bitmask=is16 and on("CREID_RELU_BITMASK"),
+        stem_fuse_pool=on("CREID_STEM_FUSE"),
+        stem_pool_fused=on("CREID_STEM_POOL"),
+        pair_fused=on("CREID_PAIR_FUSE"),
+        stem_fuse_pool_bwd=on("CREID_STEM_FUSE_BWD", "0"),
+        drop_gm=on("CREID_DROP_GM"),
+        fuse_bn_reduce=is16 and on("CREID_FUSE_BN_REDUCE") and dma,
+        eval_fold=x3 or (on("CREID_EVAL_FOLD") and (dtype == torch.float32 or dma)),
+        c3_axf=frozenset(int(v) for v in env.get("CREID_C3_AXF", "64,128").split(",") if v.strip()),
+        ds_reduce2=on("CREID_DS_REDUCE2"),
+        dual_apply=on("CREID_DUAL_APPLY"),
+        fin_apply_rows=int(env.get("CREID_FIN_APPLY", "64")),
+        fin_apply_rb=int(env.get("CREID_FIN_APPLY_RB", "64")),
+        wred_piggyback=wred_piggyback,
+        bnfin_piggyback=carrier == "wgrad",
+        fin_with_wred=carrier == "wred",
+        wgrad_first=carrier != "wgrad",
+        heads_bnred=on("CREID_HEADS_BNRED"))
+
+
 class BackboneEngine:
     """Explicit forward / backward schedule for one backbone instance.
 
@@ -271,10 +360,11 @@ class BackboneEngine:
         self.dtype = dtype
         self.dt = L._DT[dtype]
         self.conv_dt = L.BF16X3 if self.x3 else self.dt     # dtype code of the forward convolutions and their weight copies
+        # tests and tools select another schedule with dataclasses.replace(eng.sched, field=value): the raw field, no re-resolution
+        self.sched = resolve_schedule(dtype, self.mode, trainable)
         # engines of the same network share a weight-change flag: an optimiser step announced to the training engine also
         # makes an eval-mode engine (Baseline eval_precision) re-derive its copies
         net.__dict__.setdefault("_creid_engines", weakref.WeakSet()).add(self)
-        self.eval_ds_side = os.environ.get("CREID_EVAL_DS_SIDE", "0") == "1"   # eval forward: downsample conv on a side stream
         self.units = []
         self.stem = _ConvUnit(net.conv1, net.bn1)
         self.blocks = []
@@ -291,41 +381,13 @@ class BackboneEngine:
         self.weights_dirty = True      # set by writers torch cannot see (our ctypes optimiser kernels)
         self._wsig = None              # (data_ptr, _version) of every conv weight at the last prep_weights()
         self._wprep_key = None
-        self.wprep_side = os.environ.get("CREID_WPREP_SIDE", "0") == "1"   # measured r06: +0.17 ms (both branches are HBM-bound; profiles/r06_graph_branches.md)
         # nn.Module.load_state_dict copies through `param.copy_` under no_grad (bumps _version), but a post-hook makes
         # the refresh independent of how a loader writes
         net.register_load_state_dict_post_hook(lambda *_a: setattr(self, "weights_dirty", True))
         self._ws = None
-        # CREID_WGRAD_STREAM=1: weight gradients on a second HIP stream (a parallel branch of the captured graph).
-        # Measured r01: the concurrent dgrad / wgrad kernels contend for LDS and L2 and the step gets 6 % SLOWER
-        # (7970 vs 8480 img/s), so the default is one stream.
-        self.wgrad_stream = os.environ.get("CREID_WGRAD_STREAM", "0") == "1"
-        self._side = None
-        self._keep = []
-        self.reduce_stream = os.environ.get("CREID_REDUCE_STREAM", "0") == "1"
-        self._ws2 = [None, None]
-        # weight-gradient split reductions ride in the first workgroups of the NEXT data-gradient launch
-        # (creid_conv2d_dgrad_fused_nhwc) instead of 53 stand-alone 5-25 us launches; CREID_WRED_PIGGYBACK=0: round-1 path
-        if self.x3_train:
-            # bf16x3 weight gradients: partial tiles + the fp32 split reduction in one call (creid_conv2d_wgrad_x3_nhwc), on the
-            # main stream -- the carried and side-stream reduction forms are fp32 / 16-bit schedules
-            self.wgrad_stream = self.reduce_stream = False
-        self.wred_piggyback = os.environ.get("CREID_WRED_PIGGYBACK", "1") == "1" and not self.wgrad_stream \
-            and not self.reduce_stream and not self.x3_train
-        # BatchNorm-backward finalizes ride in the first workgroups of a weight-gradient launch issued between the data
-        # gradient that produced their column sums and the apply that needs them (CREID_BNFIN_PIGGYBACK=0: own launches)
-        # CREID_FIN_CARRIER: "wgrad" (above) | "wred" (finalize and the pending split reduction share one launch between the data
-        # gradient and the apply; launch order wgrad -> dgrad as before) | "none"
-        carrier = os.environ.get("CREID_FIN_CARRIER", "wgrad")
-        is16 = dtype in (torch.bfloat16, torch.float16)
+        self._keep = []                # replaced workspaces, kept until backward() ends
         self.loss_scaler = None        # f16 training: solver.LossScaler; backward() multiplies the incoming head gradient by its scale
-        if os.environ.get("CREID_BNFIN_PIGGYBACK", "1") != "1" or not (self.wred_piggyback and is16):
-            carrier = "none"
-        self.bnfin_piggyback = carrier == "wgrad"
-        self.fin_with_wred = carrier == "wred"
         self._bn_sums = {}             # id(unit) -> coefficient tensor whose finalize has already been issued
-        self.wgrad_first = os.environ.get("CREID_WGRAD_FIRST", "0") == "1" or not self.bnfin_piggyback   # launch order
-        self.carrier_max_bytes = int(float(os.environ.get("CREID_CARRIER_MAX_MB", "1e9")) * (1 << 20))
         self._wred_pending = []        # FIFO of (desc, grad tensor, workspace, nbytes)
         self._wred_ws = [None, None, None]
         self._wred_flip = 0
@@ -335,51 +397,8 @@ class BackboneEngine:
             self._group_first[o] = k
             o += len(layer)
         self.saved = None
-        # training forward writes each ReLU's mask as bits (1 byte per 8 channels); the BatchNorm backward and the fused
-        # data-gradient epilogue read that instead of re-reading the activation (CREID_RELU_BITMASK=0: read the activation)
-        self.relu_bitmask = is16 and os.environ.get("CREID_RELU_BITMASK", "1") == "1"
-        self.stem_fuse_pool = os.environ.get("CREID_STEM_FUSE", "1") == "1"    # bn1 + maxpool in one pass (38 vs 51 us)
-        self.stem_pool_fused = os.environ.get("CREID_STEM_POOL", "1") == "1"   # eval: conv1 + bn1 + maxpool in one launch
-        self.pair_fused = os.environ.get("CREID_PAIR_FUSE", "1") == "1"        # eval, layer1: conv3 of block i + conv1 of block i + 1
-        # the backward counterpart (max-pool gradient gathered inside the BN backward passes) is correct but slower:
-        # the gather is VALU-bound and runs twice (146 vs 116 us, tools/debug/stem_tail_probe.py) -- off by default
-        self.stem_fuse_pool_bwd = os.environ.get("CREID_STEM_FUSE_BWD", "0") == "1"
-        self.drop_gm = os.environ.get("CREID_DROP_GM", "1") == "1"     # A/B knob: 0 = bn3's backward still writes the masked copy
-        self.fuse_bn_reduce = is16 and os.environ.get("CREID_FUSE_BN_REDUCE", "1") == "1" \
-            and os.environ.get("CREID_IGEMM_DMA", "1") == "1"
         self._pending_steps = None     # device counter of training forwards not yet folded into num_batches_tracked
-        # eval-mode forward: BatchNorm (running statistics = constants) folded into the producing convolution's epilogue --
-        # one launch per conv instead of conv -> finalize -> apply (CREID_EVAL_FOLD=0: the three-launch schedule)
-        # (the folded epilogue of the 16-bit types lives in the LDS-DMA kernels only: with CREID_IGEMM_DMA=0 a bf16 forward takes
-        # the three-launch schedule instead of failing; float16 has no register-staged kernels at all)
-        if dtype == torch.float16 and os.environ.get("CREID_IGEMM_DMA", "1") != "1":
-            raise L.CreidError("compute dtype float16 needs the LDS-DMA convolution kernels: unset CREID_IGEMM_DMA=0 "
-                               "(the register-staged fallback kernels exist for bfloat16 and float32 only)")
-        self.eval_fold = os.environ.get("CREID_EVAL_FOLD", "1") == "1" and \
-            (dtype == torch.float32 or os.environ.get("CREID_IGEMM_DMA", "1") == "1")
-        if self.x3:
-            self.eval_fold = True          # (bf16x3 exists as the folded forward only: no statistics / apply schedule)
         self._fold_key = None
-        # TIMING-ONLY ablation (results are WRONG): bit 0 skips the forward BatchNorm apply launches of bn1 / bn2 (no residual),
-        # bit 1 their backward apply launches -- the upper bound of what fusing those passes into the consuming / producing
-        # convolutions could save (profiles/r03_bn_fusion_bound.md)
-        # training forward: bn2 + ReLU applied inside conv3's operand path (creid_conv1x1_bnrelu_fwd) for the bottlenecks whose
-        # width (conv3's input channels, 64 or 128) is listed here -- the stand-alone apply pass of bn2 disappears; "" = never.
-        # Measured (profiles/r06_bn_apply_in_conv3.md): layer2 (128) gains ~8 us per block, layer1 (64) loses ~3 us per block
-        self.c3_axf = {int(v) for v in os.environ.get("CREID_C3_AXF", "64,128").split(",") if v.strip()}
-        self.ds_reduce2 = os.environ.get("CREID_DS_REDUCE2", "1") == "1"
-        self.dual_apply = os.environ.get("CREID_DUAL_APPLY", "1") == "1"     # A/B knob: 0 = separate downsample-BN apply launch
-        # training forward: BatchNorm finalize + apply as ONE launch on layers with at most this many statistic rows (M <= 8192 by
-        # default: 24 launches less per B = 64 step at the same step time -- captured and eager --, bit-identical:
-        # profiles/r05_fin_apply.md; 0 = never);
-        # CREID_FIN_APPLY_RB = row blocks of that launch (0 = library rule)
-        self.fin_apply_rows = int(os.environ.get("CREID_FIN_APPLY", "64"))
-        self.fin_apply_rb = int(os.environ.get("CREID_FIN_APPLY_RB", "64"))
-        self._apply_dry = int(os.environ.get("CREID_BN_APPLY_DRY", "0"))
-        if self._apply_dry:
-            import sys
-            print(f"[creid] WARNING: CREID_BN_APPLY_DRY={self._apply_dry} is a timing-only ablation switch -- results are WRONG",
-                  file=sys.stderr)
 
     # ---- helpers
     @property
@@ -402,23 +421,9 @@ class BackboneEngine:
 
     def _workspace(self, nbytes):
         if self._ws is None or self._ws.numel() < nbytes:
-            self._keep.append(self._ws)          # a launch on the side stream may still be reading the old one
+            self._keep.append(self._ws)
             self._ws = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=self.device)
         return self._ws
-
-    def _fork_side(self, *tensors):
-        """Side-stream context for work that depends on everything enqueued so far on the current stream; the
-        tensors it reads are kept alive until _join_side()."""
-        if self._side is None:
-            self._side = torch.cuda.Stream(device=self.device)
-        self._side.wait_stream(torch.cuda.current_stream())
-        self._keep.extend(tensors)
-        return torch.cuda.stream(self._side)
-
-    def _join_side(self):
-        if self._side is not None:
-            torch.cuda.current_stream().wait_stream(self._side)
-        self._keep.clear()
 
     def all_units(self):
         yield self.stem
@@ -427,10 +432,9 @@ class BackboneEngine:
                 if b[k] is not None:
                     yield b[k]
 
-    def prep_weights(self, side=False):
+    def prep_weights(self):
         """fp32 OIHW master weights -> compute-dtype [O][r][s][I] and [I][r][s][O] copies (ONE launch for all
-        52 non-stem convolutions through a device descriptor table, rebuilt only if a pointer moved).  side=True: that launch
-        goes to the side stream (the caller joins it before the first non-stem convolution); returns whether it did."""
+        52 non-stem convolutions through a device descriptor table, rebuilt only if a pointer moved)."""
         import numpy as np
         lib, st = L.lib(), L.stream()
         units = [u for u in self.all_units() if u is not self.stem]
@@ -462,25 +466,14 @@ class BackboneEngine:
             self._wprep_key = key
         L.check(lib.creid_stem_weight_prep(L.ptr(self.stem.conv.weight), self.dt, L.ptr(self.stem.w_krsc), st),
                 "stem_weight_prep")
-        def multi(stream):
-            if self.x3_train:              # both two-plane copies (forward and data gradient) in one launch
-                L.check(lib.creid_weight_prep_x3_train_multi(L.ptr(self._wprep_tab), L.ptr(self._wprep_tiles), len(units),
-                                                             self._wprep_total, stream), "weight_prep_x3_train_multi")
-            else:
-                L.check(lib.creid_weight_prep_multi(L.ptr(self._wprep_tab), L.ptr(self._wprep_tiles), len(units), self._wprep_total,
-                                                    self.conv_dt, stream), "weight_prep_multi")
-        if side:
-            # the 52 non-stem copies (~50 us at ResNet50 size) are needed by layer1 only: inside a captured graph they run as a
-            # parallel branch beside the stem (image layout pass, 7 x 7 convolution, BatchNorm, max-pool: ~95 us that depend on the
-            # stem copy alone); forward() joins the branch in front of the first bottleneck.  One fork / join costs ~6 us of graph
-            # signalling (tools/probes/anyorder_probe.hip) against ~45 us hidden.
-            with self._fork_side():
-                multi(L.stream())
+        if self.x3_train:              # both two-plane copies (forward and data gradient) in one launch
+            L.check(lib.creid_weight_prep_x3_train_multi(L.ptr(self._wprep_tab), L.ptr(self._wprep_tiles), len(units),
+                                                         self._wprep_total, st), "weight_prep_x3_train_multi")
         else:
-            multi(st)
+            L.check(lib.creid_weight_prep_multi(L.ptr(self._wprep_tab), L.ptr(self._wprep_tiles), len(units), self._wprep_total,
+                                                self.conv_dt, st), "weight_prep_multi")
         self.weights_dirty = False
         self._wsig = self._weight_signature()
-        return side
 
     def _weight_signature(self):
         """Changes whenever torch-visible code rewrites or re-homes a convolution weight after the compute-dtype
@@ -555,7 +548,7 @@ class BackboneEngine:
         H2, W2 = H1 // 2, W1 // 2
         a = self._empty(B * H2 * W2, 64)
         rc = -4
-        if self.stem_pool_fused and self.dtype != torch.float32:
+        if self.sched.stem_pool_fused and self.dtype != torch.float32:
             # conv1 + folded bn1 (+ ReLU) + max-pool in one launch: the full-resolution tensor is never written (conv_stem.hip)
             rc = lib.creid_stem_conv_pool_fwd_affine(B, H, W, L.ptr(xpad), L.ptr(self.stem.w_krsc), L.ptr(a), L.ptr(self.stem.fold),
                                                      1 if self.net.stem_relu else 0, self.dt, st)
@@ -577,12 +570,6 @@ class BackboneEngine:
                 r = a_in if b["ds"] is None else self._conv_fold(b["ds"], a_in, B, hin, win, False)[0]
                 a, h, w = self._conv_fold(b["c2"], a1, B, h1, w1, True, residual=r)
                 continue
-            side = b["ds"] is not None and self.eval_ds_side
-            if side:
-                # the downsample convolution depends on the block input only: it runs on a side stream (a parallel branch of a
-                # captured graph) beside conv1 / conv2 and is joined before conv3, whose epilogue adds it
-                with self._fork_side(a_in):
-                    r = self._conv_fold(b["ds"], a_in, B, hin, win, False)[0]
             if a1_next is not None:
                 a1, h1, w1, a1_next = a1_next, hin, win, None
             elif b["c1"].ibn is not None:
@@ -590,13 +577,9 @@ class BackboneEngine:
             else:
                 a1, h1, w1 = self._conv_fold(b["c1"], a_in, B, hin, win, True)
             a2, h2, w2 = self._conv_fold(b["c2"], a1, B, h1, w1, True)
-            if side:
-                self._join_side()
-                r.record_stream(torch.cuda.current_stream())
-            else:
-                r = a_in if b["ds"] is None else self._conv_fold(b["ds"], a_in, B, hin, win, False)[0]
-            nb = self.blocks[bi + 1] if bi + 1 < len(self.blocks) else None
-            pair = (self.pair_fused and nb is not None and nb["ds"] is None and self.dtype != torch.float32
+            r = a_in if b["ds"] is None else self._conv_fold(b["ds"], a_in, B, hin, win, False)[0]
+            nb =self.blocks[bi + 1] if bi + 1 < len(self.blocks) else None
+            pair = (self.sched.pair_fused and nb is not None and nb["ds"] is None and self.dtype != torch.float32
                     and (b["c3"].cin, b["c3"].cout, nb["c1"].cout) == (64, 256, 64) and nb["c1"].stride == 1)
             if pair and nb["c1"].ibn is not None:
                 pair = (h2 * w2) % 128 == 0              # the statistics partials must be per-image row blocks
@@ -681,7 +664,7 @@ class BackboneEngine:
         ss = self._empty(B * 2, u.cout, dtype=torch.float32)
         a = self._empty(B * HW, u.cout)
         mask = None
-        if training and relu and self.relu_bitmask:
+        if training and relu and self.sched.relu_bitmask:
             mask = torch.empty(B * HW * u.cout // 8, dtype=torch.uint8, device=self.device)
         L.check(lib.creid_ibn_fwd_mask(L.ptr(x), B, HW, u.cout, ibn.half, L.ptr(ibn.IN.weight), L.ptr(ibn.IN.bias),
                                        L.ptr(bn.weight), L.ptr(bn.bias), L.ptr(bn.running_mean), L.ptr(bn.running_var),
@@ -714,17 +697,18 @@ class BackboneEngine:
         mean = self._empty(u.cout, dtype=torch.float32)
         invstd = self._empty(u.cout, dtype=torch.float32)
         ss = self._empty(2, u.cout, dtype=torch.float32)
-        if (self.fin_apply_rows and training and apply and residual_ss is None and rows <= self.fin_apply_rows
-                and u.cout % (32 if self.dtype == torch.float32 else 64) == 0 and not self._apply_dry):
+        sched = self.sched
+        if (sched.fin_apply_rows and training and apply and residual_ss is None and rows <= sched.fin_apply_rows
+                and u.cout % (32 if self.dtype == torch.float32 else 64) == 0):
             # finalize + apply in ONE launch (CREID_FIN_APPLY=<max statistic rows>; profiles/r05_fin_apply.md)
             a = self._empty(M, u.cout)
             mask = None
-            if relu and self.relu_bitmask:
+            if relu and sched.relu_bitmask:
                 mask = torch.empty(M * u.cout // 8, dtype=torch.uint8, device=self.device)
             L.check(lib.creid_bn2d_finalize_apply_mask(L.ptr(part), rows, u.cout, M, L.ptr(bn.running_mean), L.ptr(bn.running_var),
                                                        bn.momentum, bn.eps, L.ptr(bn.weight), L.ptr(bn.bias), L.ptr(mean), L.ptr(invstd),
                                                        L.ptr(ss), L.ptr(x), L.ptr(residual), 1 if relu else 0, self.dt, L.ptr(a),
-                                                       L.ptr(mask), self.fin_apply_rb, st), "bn2d_finalize_apply")
+                                                       L.ptr(mask), sched.fin_apply_rb, st), "bn2d_finalize_apply")
             if mask is not None:
                 a._relu_mask = mask
             return a, mean, invstd
@@ -735,12 +719,12 @@ class BackboneEngine:
             return ss, mean, invstd
         a = self._empty(M, u.cout)
         mask = None
-        if training and relu and self.relu_bitmask:
+        if training and relu and sched.relu_bitmask:
             mask = torch.empty(M * u.cout // 8, dtype=torch.uint8, device=self.device)
         if residual_ss is not None:
             L.check(lib.creid_bn2d_apply_dual_mask(L.ptr(x), L.ptr(ss), L.ptr(residual), L.ptr(residual_ss), 1 if relu else 0, M,
                                                    u.cout, self.dt, L.ptr(a), L.ptr(mask), st), "bn2d_apply_dual")
-        elif not (self._apply_dry & 1 and training and relu and residual is None):
+        else:
             L.check(lib.creid_bn2d_apply_mask(L.ptr(x), L.ptr(ss), L.ptr(residual), 1 if relu else 0, M, u.cout, self.dt,
                                               L.ptr(a), L.ptr(mask), st), "bn2d_apply")
         if mask is not None:
@@ -759,16 +743,13 @@ class BackboneEngine:
             raise L.CreidError("compute mode bf16x3 is an eval-mode forward only (validation / inference): train with bfloat16, "
                                "float16 or float32 and pass eval_precision='bf16x3' to Baseline / CTLModel, or train in the mode "
                                "with compute_dtype='bf16x3' (BackboneEngine(net, 'bf16x3', trainable=True))")
-        wprep_pending = False
         if self.weights_dirty or self._wsig != self._weight_signature():
-            # training steps replayed from a hipGraph re-derive the 16-bit weight copies every step (the optimiser has just rewritten
-            # the masters): as a graph branch beside the stem when capturing (CREID_WPREP_SIDE=0: in line)
-            side = (training and self.wprep_side and self._wprep_key is not None and torch.cuda.is_current_stream_capturing()
-                    and not (self.wgrad_stream or self.reduce_stream or self.eval_ds_side))
-            wprep_pending = self.prep_weights(side=side)
-        lib, st = L.lib(), L.stream()
+            # (training steps replayed from a hipGraph re-derive the 16-bit weight copies every step: the optimiser has just
+            # rewritten the masters)
+            self.prep_weights()
+        lib, st, sched = L.lib(), L.stream(), self.sched
         B, _, H, W = x_nchw.shape
-        if not training and self.eval_fold:
+        if not training and sched.eval_fold:
             return self._forward_eval_folded(x_nchw, want_base_out)
         # (f16 -- the reference's precision=16, utils/misc.py:111 -- trains like bf16; its gradients need the dynamic loss scale
         # that ModelBase.configure_optimizers attaches as `loss_scaler`: solver.LossScaler)
@@ -776,8 +757,6 @@ class BackboneEngine:
         if training:      # ONE device counter per step instead of 53 per-layer `num_batches_tracked += 1`; the increment itself
             if self._pending_steps is None:          # rides in the forward's last launch (creid_gap_fwd_count)
                 self._pending_steps = torch.zeros((), dtype=torch.long, device=self.device)
-            if self._side is None and not torch.cuda.is_current_stream_capturing():
-                self._side = torch.cuda.Stream(device=self.device)     # (the weight-copy branch of captured steps forks onto it)
         # stem
         xpad = self._stem_operand(x_nchw, B, H, W)
         H1, W1 = H // 2, W // 2
@@ -790,7 +769,7 @@ class BackboneEngine:
         H2, W2 = H1 // 2, W1 // 2
         p0 = self._empty(B * H2 * W2, 64)
         idx0 = self._empty(B * H2 * W2, 64, dtype=torch.uint8)
-        if self.stem_fuse_pool and not self.net.stem_relu:
+        if sched.stem_fuse_pool and not self.net.stem_relu:
             # bn1 + maxpool in one pass over the raw conv output: the normalised 64-channel full-resolution tensor is read
             # by nothing else (no stem ReLU -> the backward needs no mask of it either) and is never written
             bn = self.stem.bn
@@ -808,8 +787,6 @@ class BackboneEngine:
         sv["stem"] = (xpad, x0, y0, mean0, invstd0, idx0)
         a, h, w = p0, H2, W2
         sv["blocks"] = []
-        if wprep_pending:
-            self._join_side()                                  # the non-stem weight copies (a graph branch beside the stem)
         for b in self.blocks:
             a_in, hin, win = a, h, w
             if self.basic:
@@ -828,14 +805,14 @@ class BackboneEngine:
                 a, h, w = a2, h2, w2
                 continue
             x1, a1, m1, i1, h1, w1 = self._conv_bn(b["c1"], a_in, B, hin, win, training, True)
-            axf = (training and self.dtype != torch.float32 and self.relu_bitmask and not self._apply_dry and b["c3"].k == 1
-                   and b["c3"].stride == 1 and b["c3"].cin in self.c3_axf and b["c3"].cin in (64, 128) and b["c2"].ibn is None)
+            axf = (training and self.dtype != torch.float32 and sched.relu_bitmask and b["c3"].k == 1
+                   and b["c3"].stride == 1 and b["c3"].cin in sched.c3_axf and b["c3"].cin in (64, 128) and b["c2"].ibn is None)
             if axf:      # conv2 + statistics only: bn2's (scale, shift) go to conv3, which normalises its operand itself
                 x2, ss2, m2, i2, h2, w2 = self._conv_bn(b["c2"], a1, B, h1, w1, training, True, apply=False)
             else:
                 x2, a2, m2, i2, h2, w2 = self._conv_bn(b["c2"], a1, B, h1, w1, training, True)
             rss = None
-            if b["ds"] is not None and self.dual_apply:
+            if b["ds"] is not None and sched.dual_apply:
                 # downsample branch: conv + statistics only; its normalisation rides in bn3's apply pass (one launch and
                 # the write + read of the normalised branch tensor less per downsample block)
                 xd, rss, md, idd, _, _ = self._conv_bn(b["ds"], a_in, B, hin, win, training, False, apply=False)
@@ -872,7 +849,7 @@ class BackboneEngine:
             p.grad = torch.zeros_like(p)
         return p.grad
 
-    def _bn_bwd(self, u, x, g, act, mean, invstd, M, want_gm=False, part=None, mask=None, dry=False, reduce2=None):
+    def _bn_bwd(self, u, x, g, act, mean, invstd, M, want_gm=False, part=None, mask=None, reduce2=None):
         """BN backward; `part` = column-reduction partials already produced by a fused dgrad epilogue; `mask` = ReLU bits
         to apply to g (default: the ones that travel with `act`).  reduce2 = (x2, mean2, invstd2): the apply pass also produces
         the column sums of a second BatchNorm backward over the same masked gradient (the downsample branch's); returned in
@@ -892,7 +869,7 @@ class BackboneEngine:
         bn = u.bn
         dgam = self._grad_of(bn.weight) if bn.weight.requires_grad else None
         dbet = self._grad_of(bn.bias) if bn.bias.requires_grad else None
-        if ready == 1 and self.fin_with_wred and self._wred_pending:
+        if ready == 1 and self.sched.fin_with_wred and self._wred_pending:
             # the finalize and the oldest pending split reduction in ONE launch, then apply only
             rd, rgw, rws, rbytes = self._wred_pending.pop(0)
             L.check(lib.creid_bn2d_bwd_finalize_wred(L.ptr(part), rows, u.cout, M, L.ptr(mean), L.ptr(invstd), L.ptr(bn.weight),
@@ -901,8 +878,6 @@ class BackboneEngine:
             ready = 2
         if mask is None and act is not None:
             mask = getattr(act, "_relu_mask", None)
-        if dry and ready == 2:
-            return dx, gm
         if reduce2 is not None:
             x2, mean2, invstd2 = reduce2
             part2 = self._empty(rows * 2, u.cout, dtype=torch.float32)
@@ -921,13 +896,6 @@ class BackboneEngine:
         (ignored -- the BatchNorm backward then runs its own finalize -- where the carrier does not apply)."""
         if not u.conv.weight.requires_grad:
             return
-        if self.wgrad_stream:
-            with self._fork_side(a_in, dy):
-                self._wgrad_launch(u, a_in, dy, B, H, W)
-        else:
-            self._wgrad_launch(u, a_in, dy, B, H, W, fin)
-
-    def _wgrad_launch(self, u, a_in, dy, B, H, W, fin=None):
         lib, st = L.lib(), L.stream()
         d, _, _ = _desc(B, H, W, u.cin, u.cout, u.k, u.stride, u.pad)
         if self.x3_train:
@@ -938,7 +906,7 @@ class BackboneEngine:
             return
         nbytes = lib.creid_conv2d_wgrad_workspace_bytes(C.byref(d), self.dt)
         gw = self._grad_of(u.conv.weight)
-        if self.wred_piggyback:
+        if self.sched.wred_piggyback:
             # partial tiles now; the sum over the splits is carried by the next data-gradient launch.  At most two
             # jobs are ever pending (c1 and the downsample branch), so three rotating workspaces never collide.
             k = self._wred_flip = (self._wred_flip + 1) % 3
@@ -946,7 +914,7 @@ class BackboneEngine:
                 self._keep.append(self._wred_ws[k])
                 self._wred_ws[k] = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=self.device)
             ws = self._wred_ws[k]
-            if fin is not None and self.bnfin_piggyback and fin[1] is not None:
+            if fin is not None and self.sched.bnfin_piggyback and fin[1] is not None:
                 fu, fpart, fM, mean, invstd = fin
                 fbn = fu.bn
                 sums = self._empty(3, fu.cout, dtype=torch.float32)
@@ -963,28 +931,9 @@ class BackboneEngine:
             self._wred_pending.append((d, gw, ws, nbytes))
             assert len(self._wred_pending) <= 3
             return
-        if not self.reduce_stream:
-            ws = self._workspace(nbytes)
-            L.check(lib.creid_conv2d_wgrad_nhwc(C.byref(d), L.ptr(a_in), L.ptr(dy), L.ptr(gw), 1, L.ptr(ws), nbytes, self.dt,
-                                                st), "conv2d_wgrad")
-            return
-        # CREID_REDUCE_STREAM=1: partial tiles on the main stream, the short split reduce on a second stream beside
-        # the data gradient that follows; two workspaces alternate so the next wgrad never waits for this reduce
-        main = torch.cuda.current_stream()
-        if self._side is None:
-            self._side = torch.cuda.Stream(device=self.device)
-        k = self._ws_flip = 1 - getattr(self, "_ws_flip", 0)
-        if self._ws2[k] is None or self._ws2[k].numel() < nbytes:
-            self._keep.append(self._ws2[k])
-            self._ws2[k] = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=self.device)
-        ws = self._ws2[k]
-        main.wait_stream(self._side)            # the reduce that last used this workspace (two wgrads ago) is done
-        L.check(lib.creid_conv2d_wgrad_partials(C.byref(d), L.ptr(a_in), L.ptr(dy), L.ptr(ws), nbytes, self.dt, st),
-                "conv2d_wgrad_partials")
-        self._side.wait_stream(main)
-        with torch.cuda.stream(self._side):
-            L.check(lib.creid_conv2d_wgrad_reduce(C.byref(d), L.ptr(gw), 1, L.ptr(ws), nbytes, self.dt, L.stream()),
-                    "conv2d_wgrad_reduce")
+        ws = self._workspace(nbytes)
+        L.check(lib.creid_conv2d_wgrad_nhwc(C.byref(d), L.ptr(a_in), L.ptr(dy), L.ptr(gw), 1, L.ptr(ws), nbytes, self.dt, st),
+                "conv2d_wgrad")
 
     def _dgrad(self, u, dy, B, H, W, add_src=None, bnred=None, stat_image_rows=0, add_src_stride=1, add_mask=None):
         """Data gradient.  bnred = (x, act, mean, invstd) of the BN layer that consumes the result: its column
@@ -999,8 +948,8 @@ class BackboneEngine:
             L.check(lib.creid_conv2d_dgrad_x3_nhwc(C.byref(d), L.ptr(dy), L.ptr(u.w_crsk), L.ptr(dx), L.ptr(add_src), st),
                     "conv2d_dgrad_x3")
             return dx, None
-        fuse_bn = bnred is not None and self.fuse_bn_reduce
-        carry = len(self._wred_pending) >= (2 if self.fin_with_wred else 1)     # "wred" mode keeps one job for the finalize launch
+        fuse_bn = bnred is not None and self.sched.fuse_bn_reduce
+        carry = len(self._wred_pending) >= (2 if self.sched.fin_with_wred else 1)   # "wred" mode keeps one job for the finalize launch
         if carry or fuse_bn or add_mask is not None:
             rd, rgw, rws, rbytes = self._wred_pending.pop(0) if carry else (None, None, None, 0)
             x, act, mean, invstd = bnred if fuse_bn else (None, None, None, None)
@@ -1020,10 +969,10 @@ class BackboneEngine:
         """What creid_ctl_heads_fused needs to produce the column sums of the FIRST BatchNorm backward (the last bottleneck's bn3)
         while it writes g: (x3, ReLU bits of the block output, mean, invstd, partial-rows buffer), or None when that reduction
         keeps its own launch (fp32 engine, no mask bits, 128-row tiles that straddle images in the general case are fine)."""
-        sv = self.saved
-        if self.basic or sv is None or not sv.get("training") or not (self.fuse_bn_reduce and self.drop_gm and self.relu_bitmask):
+        sv, sched = self.saved, self.sched
+        if self.basic or sv is None or not sv.get("training"):
             return None
-        if os.environ.get("CREID_HEADS_BNRED", "1") != "1":
+        if not (sched.heads_bnred and sched.fuse_bn_reduce and sched.drop_gm and sched.relu_bitmask):
             return None
         s = sv["blocks"][-1]
         mask = getattr(s["a3"], "_relu_mask", None)
@@ -1042,7 +991,7 @@ class BackboneEngine:
         sums of the deepest bn3 backward, produced by that same launch."""
         sv = self.saved
         assert sv is not None and sv["training"], "backward() needs a training-mode forward first"
-        lib, st = L.lib(), L.stream()
+        lib, st, sched = L.lib(), L.stream(), self.sched
         self._bn_sums.clear()
         B = sv["B"]
         h, w = sv["final"]
@@ -1067,11 +1016,11 @@ class BackboneEngine:
             # the block's incoming gradient g is masked by the final ReLU on three paths (bn3, the residual add, the
             # downsample BN).  With the mask as bits every consumer applies it itself and the masked copy `gm` is never
             # written; otherwise bn3's backward writes it once.
-            m3 = getattr(s["a3"], "_relu_mask", None) if (self.fuse_bn_reduce and self.drop_gm) else None
+            m3 = getattr(s["a3"], "_relu_mask", None) if (sched.fuse_bn_reduce and sched.drop_gm) else None
             # downsample blocks: bn3's apply pass also sums the columns the downsample branch's BatchNorm backward needs (same
             # masked gradient, one read of it instead of two and one launch less; CREID_DS_REDUCE2=0: separate launches)
             ds_part = None
-            if m3 is not None and b["ds"] is not None and self.ds_reduce2 and not self.fin_with_wred:
+            if m3 is not None and b["ds"] is not None and sched.ds_reduce2 and not sched.fin_with_wred:
                 dx3, ds_part = self._bn_bwd(b["c3"], s["x3"], g, s["a3"], s["m3"], s["i3"], M3, part=part3,
                                             reduce2=(s["xd"], s["md"], s["idd"]))
                 gm = g
@@ -1083,17 +1032,14 @@ class BackboneEngine:
             # then the weight gradient, which is off that chain and carries the finalize of the BatchNorm whose column sums
             # the data gradient just produced (and, via the pending queue, gets its own split reduction carried by the
             # NEXT data gradient)
-            wfirst = self.wgrad_first
-
-            def wg(u, a, dy, h_, w_, fin=None, early=False, first=None):   # the call site that matches the launch order issues it
-                f = wfirst if first is None else first
-                if early == f:
-                    self._wgrad(u, a, dy, B, h_, w_, fin=None if f else fin)
+            def wg(u, a, dy, h_, w_, fin=None, early=False):   # the call site that matches the launch order issues it
+                if early == sched.wgrad_first:
+                    self._wgrad(u, a, dy, B, h_, w_, fin=None if sched.wgrad_first else fin)
 
             wg(b["c3"], s["a2"], dx3, s["h2"], s["w2"], early=True)
             da2, p2 = self._dgrad(b["c3"], dx3, B, s["h2"], s["w2"], bnred=(s["x2"], s["a2"], s["m2"], s["i2"]))
             wg(b["c3"], s["a2"], dx3, s["h2"], s["w2"], fin=(b["c2"], p2, M3, s["m2"], s["i2"]))
-            dx2, _ = self._bn_bwd(b["c2"], s["x2"], da2, s["a2"], s["m2"], s["i2"], M3, part=p2, dry=bool(self._apply_dry & 2))
+            dx2, _ = self._bn_bwd(b["c2"], s["x2"], da2, s["a2"], s["m2"], s["i2"], M3, part=p2)
             ibn1 = b["c1"].ibn is not None
             hw1 = s["h1"] * s["w1"]
             ibn_fused = ibn1 and hw1 % 128 == 0          # per-image statistics: the 128-row tiles must not straddle images
@@ -1106,17 +1052,13 @@ class BackboneEngine:
             if ibn1:
                 dx1, _ = self._ibn_bwd(b["c1"], s["x1"], da1, s["a1"], s["m1"], s["i1"], B, hw1, part=p1)
             else:
-                dx1, _ = self._bn_bwd(b["c1"], s["x1"], da1, s["a1"], s["m1"], s["i1"], M1, part=p1, dry=bool(self._apply_dry & 2))
+                dx1, _ = self._bn_bwd(b["c1"], s["x1"], da1, s["a1"], s["m1"], s["i1"], M1, part=p1)
             nxt = None if prev is None else (prev[1]["x3"], prev[1]["a3"], prev[1]["m3"], prev[1]["i3"])
-            # the c1 data gradient writes the block-input gradient (the widest tensor of the block) that the previous block's
-            # bn3 apply reads next; when it is larger than the carrier threshold the weight gradient goes first (its operand
-            # traffic would push that tensor out of the Infinity Cache) and bn3's finalize keeps its own launch
-            c1_first = wfirst or B * s["hin"] * s["win"] * b["c1"].cin * 2 > self.carrier_max_bytes
-            wg(b["c1"], s["a_in"], dx1, s["hin"], s["win"], early=True, first=c1_first)
+            wg(b["c1"], s["a_in"], dx1, s["hin"], s["win"], early=True)
             if b["ds"] is not None:
                 dxd, _ = self._bn_bwd(b["ds"], s["xd"], gm, None, s["md"], s["idd"], M3, mask=m3, part=ds_part)
                 dsu = b["ds"]
-                if (dsu.stride == 2 and dsu.k == 1 and nxt is not None and self.fuse_bn_reduce
+                if (dsu.stride == 2 and dsu.k == 1 and nxt is not None and sched.fuse_bn_reduce
                         and s["hin"] % 2 == 0 and s["win"] % 2 == 0):
                     # stride-2 1x1 downsample: its data gradient lives on the even pixels only -- compute it as a
                     # plain 1x1 GEMM over the OUTPUT grid and let the c1 dgrad epilogue scatter-add it
@@ -1132,18 +1074,16 @@ class BackboneEngine:
             else:
                 g, part3 = self._dgrad(b["c1"], dx1, B, s["hin"], s["win"], add_src=gm, bnred=nxt, add_mask=m3)
             Min = B * s["hin"] * s["win"]
-            wg(b["c1"], s["a_in"], dx1, s["hin"], s["win"], first=c1_first,
+            wg(b["c1"], s["a_in"], dx1, s["hin"], s["win"],
                fin=None if (prev is None or part3 is None) else (prev[0]["c3"], part3, Min, prev[1]["m3"], prev[1]["i3"]))
             if self.on_group_done is not None and bi in self._group_first:
                 self._flush_wred()                       # the layer's last split reduction: nothing left to carry it
-                if self.wgrad_stream or self.reduce_stream:
-                    self._join_side()                    # side-stream weight gradients of this group must be ordered before the hook
                 self.on_group_done(self._group_first[bi])
         # stem
         xpad, x0, y0, mean0, invstd0, idx0 = sv["stem"]
         H, W = sv["H"], sv["W"]
         H1, W1 = H // 2, W // 2
-        if self.stem_fuse_pool_bwd and not self.net.stem_relu:
+        if sched.stem_fuse_pool_bwd and not self.net.stem_relu:
             # the max-pool gradient is gathered inside the BatchNorm backward passes, the full-resolution dy0 is never written
             bn, M0 = self.stem.bn, B * H1 * W1
             part0 = self._empty(lib.creid_bn2d_bwd_rows(M0) * 2, 64, dtype=torch.float32)
@@ -1159,14 +1099,12 @@ class BackboneEngine:
             L.check(lib.creid_maxpool3x3s2_bwd(L.ptr(g), L.ptr(idx0), B, H1, W1, 64, self.dt, L.ptr(dy0), st), "maxpool_bwd")
             dx0, _ = self._bn_bwd(self.stem, x0, dy0, y0 if self.net.stem_relu else None, mean0, invstd0, B * H1 * W1)
         if self.stem.conv.weight.requires_grad:
-            with (self._fork_side(xpad, dx0) if self.wgrad_stream else contextlib.nullcontext()):
-                nbytes = lib.creid_stem_conv_wgrad_workspace_bytes(B, H, W, self.dt)
-                ws = self._workspace(nbytes)
-                L.check(lib.creid_stem_conv_wgrad(B, H, W, L.ptr(xpad), L.ptr(dx0),
-                                                  L.ptr(self._grad_of(self.stem.conv.weight)), 1, L.ptr(ws), nbytes,
-                                                  self.dt, L.stream()), "stem_conv_wgrad")
+            nbytes = lib.creid_stem_conv_wgrad_workspace_bytes(B, H, W, self.dt)
+            ws = self._workspace(nbytes)
+            L.check(lib.creid_stem_conv_wgrad(B, H, W, L.ptr(xpad), L.ptr(dx0), L.ptr(self._grad_of(self.stem.conv.weight)), 1,
+                                              L.ptr(ws), nbytes, self.dt, st), "stem_conv_wgrad")
         self._flush_wred()
-        self._join_side()
+        self._keep.clear()
         self.saved = None
 
     def _backward_basic(self, blocks, g, B):

@@ -1,6 +1,7 @@
 """GPU parity: stage A (conv fwd / dgrad / wgrad, BN, pool, GAP, whole ResNet50) through the C ABI.
 Layer kernels are checked against plain torch-CPU fp32/fp64 references of the same op; the whole
 backbone against the golden vectors produced by the reference and against the CPU oracle."""
+import dataclasses
 import os
 
 import numpy as np
@@ -471,7 +472,7 @@ def test_piggyback_wgrad_reduce_matches_standalone(arch, dtype):
     grads = []
     for piggy in (True, False):
         net, eng, _ = _build(arch, dtype)
-        eng.wred_piggyback = piggy
+        eng.sched = dataclasses.replace(eng.sched, wred_piggyback=piggy)
         for _ in range(2):                       # twice: gradients accumulate, workspaces rotate
             _, feat = eng.forward(x, training=True)
             eng.backward(coef)
@@ -499,8 +500,8 @@ def test_fused_bn_reduce_matches_separate_pass(arch):
     grads = []
     for fuse in (True, False):
         net, eng, _ = _build(arch, torch.bfloat16)
-        eng.fuse_bn_reduce = fuse
-        eng.c3_axf = set()             # (the operand-path BatchNorm of round 6 runs conv3 on another kernel: its own test below)
+        # (the operand-path BatchNorm of round 6 runs conv3 on another kernel: its own test below)
+        eng.sched = dataclasses.replace(eng.sched, fuse_bn_reduce=fuse, c3_axf=frozenset())
         _, feat = eng.forward(x, training=True)
         eng.backward(coef)
         grads.append({n: p.grad.detach().clone() for n, p in net.named_parameters() if p.grad is not None})
@@ -625,7 +626,7 @@ def test_relu_bitmask_kernels_match_activation_path():
 @pytest.mark.parametrize("arch", ["resnet50", "resnet50_ibn_a"])
 def test_relu_bitmask_schedule_is_bit_identical(arch):
     """Whole backward with the ReLU masks carried as bits (default) against the schedule that re-reads the activations
-    (CREID_RELU_BITMASK=0 / eng.relu_bitmask = False): same masks, same arithmetic -> identical gradients."""
+    (CREID_RELU_BITMASK=0 / eng.sched.relu_bitmask False): same masks, same arithmetic -> identical gradients."""
     from oracle import backbone_oracle as bo
     from centroids_reid_amd import ops
     x = bo.synthetic_images(4, 128, 64, seed=23).cuda()
@@ -633,8 +634,8 @@ def test_relu_bitmask_schedule_is_bit_identical(arch):
     grads = []
     for bits in (True, False):
         net, eng, _ = _build(arch, torch.bfloat16)
-        eng.relu_bitmask = bits
-        eng.c3_axf = set()             # needs the bits; with it conv3 runs on the persistent 1 x 1 kernel (other statistics grouping)
+        # (c3_axf needs the bits; with it conv3 runs on the persistent 1 x 1 kernel: other statistics grouping)
+        eng.sched = dataclasses.replace(eng.sched, relu_bitmask=bits, c3_axf=frozenset())
         _, feat = eng.forward(x, training=True)
         if bits:
             assert any(getattr(s["a3"], "_relu_mask", None) is not None for s in eng.saved["blocks"])
@@ -696,8 +697,8 @@ def test_stem_fusion_schedule_is_bit_identical(dtype):
     res = []
     for fuse in (True, False):
         net, eng, _ = _build("resnet50", dtype)
-        eng.stem_fuse_pool = fuse
-        eng.stem_fuse_pool_bwd = fuse               # the (off by default) pooled BatchNorm backward as well
+        # (the -- off by default -- pooled BatchNorm backward as well)
+        eng.sched = dataclasses.replace(eng.sched, stem_fuse_pool=fuse, stem_fuse_pool_bwd=fuse)
         _, feat = eng.forward(x, training=True)
         assert (eng.saved["stem"][2] is None) == fuse
         eng.backward(coef)
@@ -719,9 +720,10 @@ def test_bn_finalize_carried_by_wgrad_matches_own_launch(arch):
     grads = []
     for mode in ("wgrad", "wred", "none"):
         net, eng, _ = _build(arch, torch.bfloat16)
-        eng.bnfin_piggyback = mode == "wgrad"          # finalize in the first workgroups of a weight-gradient launch
-        eng.fin_with_wred = mode == "wred"             # finalize + pending split reduction as one launch
-        eng.wgrad_first = mode != "wgrad"
+        eng.sched = dataclasses.replace(
+            eng.sched, bnfin_piggyback=mode == "wgrad",      # finalize in the first workgroups of a weight-gradient launch
+            fin_with_wred=mode == "wred",                    # finalize + pending split reduction as one launch
+            wgrad_first=mode != "wgrad")
         for _ in range(2):
             _, feat = eng.forward(x, training=True)
             eng.backward(coef)
@@ -746,7 +748,7 @@ def test_dual_apply_equals_separate_downsample_bn_fp32(arch, H, W, monkeypatch):
     for dual in ("1", "0"):
         monkeypatch.setenv("CREID_DUAL_APPLY", dual)
         net, eng, _ = _build(arch, torch.float32, seed=31)
-        assert eng.dual_apply == (dual == "1")
+        assert eng.sched.dual_apply == (dual == "1")
         _, feat = eng.forward(x, training=True)
         eng.backward(coef)
         torch.cuda.synchronize()
@@ -927,7 +929,7 @@ def test_downsample_bn_column_sums_in_bn3_apply_pass_are_bit_identical(arch, dty
     grads = []
     for fused in (True, False):
         net, eng, _ = _build(arch, dtype, seed=99)
-        eng.ds_reduce2 = fused
+        eng.sched = dataclasses.replace(eng.sched, ds_reduce2=fused)
         eng.loss_scaler = None
         _, f = eng.forward(x, training=True)
         eng.backward(coef)
@@ -953,7 +955,7 @@ def test_bn2_relu_inside_conv3_operand_path_is_bit_identical(arch, dtype, hw, mo
     res = []
     for widths in ({64, 128}, set()):
         net, eng, _ = _build(arch, dtype, seed=98)
-        eng.c3_axf = widths
+        eng.sched = dataclasses.replace(eng.sched, c3_axf=frozenset(widths))
         eng.loss_scaler = None
         _, f = eng.forward(x, training=True)
         saved_masks = [blk["a2"]._relu_mask.clone() for blk in eng.saved["blocks"]]

@@ -54,8 +54,8 @@ def test_engine_mode_and_baseline_argument():
     from centroids_reid_amd.config import get_cfg_defaults
     net = bb.ResNet(last_stride=1)
     eng = bb.BackboneEngine(net, "bf16x3")
-    assert eng.x3 and eng.dtype == torch.float32 and eng.conv_dt == 3 and eng.eval_fold
-    assert not eng.stem_pool_fused or eng.dtype == torch.float32        # the 16-bit-only fused stem is never taken
+    assert eng.x3 and eng.dtype == torch.float32 and eng.conv_dt == 3 and eng.sched.eval_fold
+    assert not eng.sched.stem_pool_fused or eng.dtype == torch.float32        # the 16-bit-only fused stem is never taken
     with pytest.raises(ValueError):
         bb.BackboneEngine(net, "tf32")
     # engines of one network share the weight-change flag

@@ -87,7 +87,7 @@ def test_trainable_engine_selection():
     b = baseline.Baseline(_cfg(), compute_dtype="bf16x3")
     e = b.engine_for(True)
     assert e.x3 and e.x3_train and e.dtype == torch.float32 and e.conv_dt == 3
-    assert not (e.wred_piggyback or e.wgrad_stream or e.reduce_stream or e.fuse_bn_reduce or e.relu_bitmask)
+    assert not (e.sched.wred_piggyback or e.sched.fuse_bn_reduce or e.sched.relu_bitmask)    # (no side-stream forms any more)
     assert b.engine_for(True) is e and b.engine is e            # built once, not on every access
     assert b.engine_for(False) is e                             # its eval-mode forward is the folded bf16x3 one
     b2 = baseline.Baseline(_cfg(), compute_dtype="bf16x3", eval_precision="bf16x3")
@@ -100,7 +100,7 @@ def test_default_x3_engine_stays_eval_only():
     from centroids_reid_amd import _lib, backbone as bb
     net = bb.ResNet(last_stride=1)
     eng = bb.BackboneEngine(net, "bf16x3")
-    assert eng.x3 and not eng.x3_train and eng.eval_fold    # (its training forward still raises: tests/test_bf16x3_train_gpu.py)
+    assert eng.x3 and not eng.x3_train and eng.sched.eval_fold    # (its training forward still raises: tests/test_bf16x3_train_gpu.py)
     with pytest.raises(ValueError):
         bb.BackboneEngine(net, torch.float32, trainable=True)
     # the trainable form refuses the BasicBlock networks with a clear error

@@ -140,13 +140,13 @@ def record_step(cfg, monkeypatch):
         rec.dfeat = None if dfeat is None else dfeat.clone()
         return o_bwd(dfeat, g=g, part3=part3)
 
-    def bn_bwd(u, x, g, act, mean, invstd, M, want_gm=False, part=None, mask=None, dry=False, reduce2=None):
+    def bn_bwd(u, x, g, act, mean, invstd, M, want_gm=False, part=None, mask=None, reduce2=None):
         route = "ready2" if id(u) in eng._bn_sums else ("ready1" if part is not None else "ready0")
-        if route == "ready1" and eng.fin_with_wred and eng._wred_pending:
+        if route == "ready1" and eng.sched.fin_with_wred and eng._wred_pending:
             route = "fin+wred"
         bits = mask if mask is not None else (getattr(act, "_relu_mask", None) if act is not None else None)
         gc = g.clone()
-        out = o_bn(u, x, g, act, mean, invstd, M, want_gm=want_gm, part=part, mask=mask, dry=dry, reduce2=reduce2)
+        out = o_bn(u, x, g, act, mean, invstd, M, want_gm=want_gm, part=part, mask=mask, reduce2=reduce2)
         rec.bn.append(dict(u=u, x=x, g=gc, act=act, bits=bits, mean=mean, invstd=invstd, M=M, route=route,
                            reduce2=reduce2 is not None, dx=out[0].clone(),
                            gm=out[1].clone() if (want_gm and reduce2 is None and out[1] is not None) else None))
@@ -160,18 +160,18 @@ def record_step(cfg, monkeypatch):
         return out
 
     def dgrad(u, dy, B, H_, W_, add_src=None, bnred=None, stat_image_rows=0, add_src_stride=1, add_mask=None):
-        carry = bool(eng._wred_pending) and len(eng._wred_pending) >= (2 if eng.fin_with_wred else 1)
+        carry = bool(eng._wred_pending) and len(eng._wred_pending) >= (2 if eng.sched.fin_with_wred else 1)
         dyc = dy.clone()
         addc = None if add_src is None else add_src.clone()
         out = o_dg(u, dy, B, H_, W_, add_src=add_src, bnred=bnred, stat_image_rows=stat_image_rows,
                    add_src_stride=add_src_stride, add_mask=add_mask)
         rec.dgrad.append(dict(u=u, dy=dyc, B=B, H=H_, W=W_, add=addc, stride=add_src_stride, add_mask=add_mask,
-                              bnred=bnred is not None and eng.fuse_bn_reduce, carry=carry, dx=out[0].clone()))
+                              bnred=bnred is not None and eng.sched.fuse_bn_reduce, carry=carry, dx=out[0].clone()))
         return out
 
     def wgrad(u, a_in, dy, B, H_, W_, fin=None):
         rec.wgrad.append(dict(u=u, a_in=a_in, dy=dy.clone(), B=B, H=H_, W=W_,
-                              bnfin=fin is not None and fin[1] is not None and eng.bnfin_piggyback and eng.wred_piggyback))
+                              bnfin=fin is not None and fin[1] is not None and eng.sched.bnfin_piggyback and eng.sched.wred_piggyback))
         return o_wg(u, a_in, dy, B, H_, W_, fin=fin)
 
     for n, f in (("forward", forward), ("backward", backward), ("_bn_bwd", bn_bwd), ("_ibn_bwd", ibn_bwd), ("_dgrad", dgrad),
@@ -418,7 +418,7 @@ def audit_forward(au, rec):
             refd, ed, td = _conv_check(au, rec, nd, b_u["ds"], s["a_in"], B, hin, win, s["xd"])
             m_ref, var_ref, dm, dvar = _stats_check(au, rec, nd, b_u["ds"].bn, refd, ed, s["md"], s["idd"], td)
             _running_check(au, rec, nd, b_u["ds"], m_ref, var_ref, dm, dvar, refd.shape[0])
-            assert eng.dual_apply
+            assert eng.sched.dual_apply
             r, scd, shd, mscd = _apply_ref(s["xd"], s["md"], s["idd"], b_u["ds"].bn.weight, b_u["ds"].bn.bias)   # dual: fp32, unrounded
             res_terms = [s["xd"].double() * scd, shd, mscd]
         else:
@@ -592,7 +592,7 @@ def expected_routes(rec):
     eng = rec.eng
     need = {"creid_stem_conv_fwd", "creid_stem_conv_wgrad", "creid_maxpool3x3s2_bwd"}
     need.add("creid_bn2d_apply_dual_mask")                                      # dual apply (CREID_DUAL_APPLY=1)
-    if -(-rec.B * (rec.H // 16) * (rec.W // 16) // 128) <= eng.fin_apply_rows:
+    if -(-rec.B * (rec.H // 16) * (rec.W // 16) // 128) <= eng.sched.fin_apply_rows:
         need.add("creid_bn2d_finalize_apply_mask")                              # finalize + apply (CREID_FIN_APPLY=64 rows)
     need.add("creid_bn2d_apply_maxpool3x3s2" if not eng.net.stem_relu else "creid_maxpool3x3s2_fwd")
     if rec.fused:

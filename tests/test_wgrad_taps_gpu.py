@@ -204,14 +204,14 @@ def test_backward_pass_differs_only_in_the_covered_weight_gradients(monkeypatch)
         net = net.cuda()
         eng = bb.BackboneEngine(net, torch.bfloat16)
         seen = {}
-        inner = eng._wgrad_launch
+        inner = eng._wgrad
 
         def record(u, a_in, dy, B, H, W, fin=None, inner=inner, seen=seen):
             if u.k == 3 and u.stride == 1 and tc.covers(u.cin, u.cout, 3, 1, 1, H, W, H, W, B * H * W):
                 seen[id(u.conv.weight)] = (a_in.detach().clone().view(B, H, W, u.cin), dy.detach().clone().view(B, H, W, u.cout))
             return inner(u, a_in, dy, B, H, W, fin)
 
-        eng._wgrad_launch = record
+        eng._wgrad = record
         n0 = _launches()
         eng.forward(x, training=True)
         eng.backward(coef)

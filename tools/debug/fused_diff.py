@@ -1,4 +1,4 @@
-import sys, numpy as np, torch
+import dataclasses, sys, numpy as np, torch
 sys.path.insert(0, '.')
 from oracle import backbone_oracle as bo
 from centroids_reid_amd import backbone as bb
@@ -8,7 +8,7 @@ grads = []
 for fuse in (True, False):
     sd = bo.make_state_dict('resnet50', 1, seed=1234)
     net = bb.ResNet(last_stride=1); net.load_state_dict(sd); net = net.cuda()
-    eng = bb.BackboneEngine(net, torch.bfloat16); eng.fuse_bn_reduce = fuse
+    eng = bb.BackboneEngine(net, torch.bfloat16); eng.sched = dataclasses.replace(eng.sched, fuse_bn_reduce=fuse)
     eng.forward(x, training=True); eng.backward(coef)
     grads.append({n: p.grad.detach().clone() for n, p in net.named_parameters() if p.grad is not None})
 names = list(grads[0])

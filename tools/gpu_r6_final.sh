@@ -9,7 +9,7 @@ python -c "import __graft_entry__ as g; g.smoke()" > $o/smoke.log 2>&1; tail -2 
 ( time python bench.py --full > $o/bench.json 2> $o/bench.err ) 2> $o/bench.time; echo "bench rc $?"; tail -3 $o/bench.time
 # what each round-6 schedule change is worth on THIS box (same process environment, two interleaved repeats)
 bash tools/ab.sh "CREID_HEADS_ONE_CALL=0 CREID_DS_REDUCE2=0 CREID_C3_AXF= CREID_HEADS_BNRED=0" "CREID_DS_REDUCE2=0 CREID_C3_AXF= CREID_HEADS_BNRED=0" \
-  "CREID_C3_AXF= CREID_HEADS_BNRED=0" "CREID_C3_AXF=" "CREID_X=default" "CREID_WPREP_SIDE=1" > $o/switches_ab.txt 2>&1; cat $o/switches_ab.txt
+  "CREID_C3_AXF= CREID_HEADS_BNRED=0" "CREID_C3_AXF=" "CREID_X=default" > $o/switches_ab.txt 2>&1; cat $o/switches_ab.txt
 bash tools/prof_train.sh r6f > $o/train_step_anatomy.md 2>&1; head -22 $o/train_step_anatomy.md
 db=$(find gpurun_out/prof_r6f -name "*.db" | head -1)
 python tools/train_layers.py $db > $o/train_layers.md 2>&1; tail -16 $o/train_layers.md
