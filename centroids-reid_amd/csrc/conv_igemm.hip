@@ -1133,7 +1133,14 @@ __global__ __launch_bounds__(256) void igemm_f32_kernel(IGemmGeom g, const float
         if (rr < g.M) {
           float v = acc[i][j][r];
           if (g.epi_scale) v = fmaf(v, esc, esh);                   // folded eval-mode BatchNorm: bn2d_apply_kernel's arithmetic
-          if (add_src) v += add_src[(int64_t)rr * g.N + c];
+          if (add_src && !g.add_compact) {
+            v += add_src[(int64_t)rr * g.N + c];
+          } else if (add_src) {                                    // the stride-2 compact tensor: even (y, x) only (igemm_tile_epilogue)
+            int ab, arem, ay, ax;
+            fast_divmod(rr, g.OH * g.OW, g.inv_ohow, ab, arem);
+            fast_divmod(arem, g.OW, g.inv_ow, ay, ax);
+            if (((ay | ax) & 1) == 0) v += add_src[(int64_t)((ab * (g.OH >> 1) + (ay >> 1)) * (g.OW >> 1) + (ax >> 1)) * g.N + c];
+          }
           if (g.epi_relu) v = fmaxf(v, 0.f);
           s1 += v; s2 = fmaf(v, v, s2);
           out[(int64_t)rr * g.N + c] = v;

@@ -762,7 +762,8 @@ int creid_conv2d_dgrad_bnred_nhwc(const creid_conv_desc* d, const void* dy, cons
                                   const float* bn_mean, const float* bn_invstd, float* bn_partial,
                                   int64_t bn_stat_image_rows, int add_src_stride, int dtype, void* stream);
 
-/* The data gradient with everything that can ride in the same launch: "+ add_src" (add_src_stride as above), the
+/* The data gradient with everything that can ride in the same launch: "+ add_src" (add_src_stride as above; the compact
+ * form exists in the 16-bit LDS-DMA kernels and in the fp32 kernel), the
  * NEXT BatchNorm-backward's column reduction (bn_x != NULL, arguments as creid_conv2d_dgrad_bnred_nhwc), and the
  * split reduction of the PREVIOUS weight-gradient launch: wred_desc != NULL names the convolution whose
  * creid_conv2d_wgrad_partials call filled wred_ws; the first workgroups of this launch sum those partials into
