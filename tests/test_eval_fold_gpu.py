@@ -58,6 +58,15 @@ def test_conv_affine_layer(case, dtype):
     np.testing.assert_allclose(yg.float().cpu().permute(0, 3, 1, 2).numpy(), y.float().numpy(), rtol=rt, atol=at)
     if relu:
         assert float(yg.float().min()) >= 0.0
+    # the bounds derived from the kernels' arithmetic (tests/eval_audit.py), on the operands as stored: the tolerances above cannot
+    # see a dropped rounding, a wrong eps or a truncated accumulator; these can (tests/test_eval_audit_cpu.py)
+    import eval_audit as ea
+    import layer_audit as la
+    au = la.Audit("layer")
+    ea.check_fold(au, "bn", ss, gamma.cuda(), beta.cuda(), rm.cuda(), rv.cuda(), 1e-5)
+    ea.check_folded_conv(au, "conv", "folded conv", yg.view(-1, cout), xg, krsc.permute(0, 3, 1, 2).double(), stride, pad, ss, relu, rg,
+                         dtype)
+    assert not au.failures, au.failures
 
 
 def _eval_feat(arch, dtype, fold, x, sd):
