@@ -181,6 +181,9 @@ SIGNATURES = {
     "creid_gap_fwd": (C.c_int, [_p, _i64, _i64, _i64, C.c_int, _p, _p]),
     "creid_gap_fwd_count": (C.c_int, [_p, _i64, _i64, _i64, C.c_int, _p, _p, _p]),
     "creid_gap_bwd": (C.c_int, [_p, _i64, _i64, _i64, C.c_int, _p, _p]),
+    "creid_gem_bwd_partials": (_i64, [_i64, _i64, C.c_int]),
+    "creid_gem_fwd": (C.c_int, [_p, _i64, _i64, _i64, C.c_int, _p, _f32, _p, _p, _p, _p]),
+    "creid_gem_bwd": (C.c_int, [_p, _p, _p, _i64, _i64, _i64, C.c_int, _p, _f32, _p, _p, _p, _p]),
     "creid_nhwc_to_nchw_f32": (C.c_int, [_p, _i64, _i64, _i64, C.c_int, _p, _p]),
     "creid_gemm_f32": (C.c_int, [_p, _i64, _i64, _p, _i64, _i64, _p, _i64, _i64, _i64, _i64, _f32, _f32, _i32, _p]),
 }

@@ -334,6 +334,9 @@ def resolve_schedule(dtype, mode=None, trainable=False, env=os.environ):
         heads_bnred=on("CREID_HEADS_BNRED"))
 
 
+POOLINGS = ("avg", "gem")
+
+
 class BackboneEngine:
     """Explicit forward / backward schedule for one backbone instance.
 
@@ -343,8 +346,16 @@ class BackboneEngine:
     engine's training schedule with the forward, data-gradient and weight-gradient launches of the 52 non-stem convolutions
     on the bf16x3 entry points (every activation, BatchNorm, IBN and the stem stay exact fp32)."""
 
-    def __init__(self, net: ResNet, dtype=torch.bfloat16, trainable=False):
+    def __init__(self, net: ResNet, dtype=torch.bfloat16, trainable=False, pooling="avg", gem=None):
+        """pooling: "avg" (the reference's global average pool) or "gem" -- generalized-mean pooling (csrc/gem_pool.hip) in
+        every forward of this engine and its backward; `gem` is then the module that owns the exponent (`gem.p`, a [1] fp32
+        parameter read on the device at every launch) and `gem.eps`."""
         self.net = net
+        if pooling not in POOLINGS:
+            raise ValueError(f"pooling must be one of {POOLINGS}, got {pooling!r}")
+        if (pooling == "gem") != (gem is not None):
+            raise ValueError("pooling='gem' needs the module that owns the exponent (gem=...), pooling='avg' takes none")
+        self.pooling, self.gem = pooling, gem
         self.mode = dtype if isinstance(dtype, str) else None
         if self.mode is not None and self.mode not in L.EVAL_PRECISIONS:
             raise ValueError(f"unknown compute mode {dtype!r} (a torch dtype or one of {L.EVAL_PRECISIONS})")
@@ -605,7 +616,10 @@ class BackboneEngine:
             else:
                 a, h, w = self._conv_fold(b["c3"], a2, B, h2, w2, True, residual=r)
         feat = self._empty(B, self.cout, dtype=torch.float32)
-        L.check(lib.creid_gap_fwd(L.ptr(a), B, h * w, self.cout, self.dt, L.ptr(feat), st), "gap_fwd")
+        if self.gem is not None:
+            self._gem_fwd(a, B, h * w, feat, False)
+        else:
+            L.check(lib.creid_gap_fwd(L.ptr(a), B, h * w, self.cout, self.dt, L.ptr(feat), st), "gap_fwd")
         self.saved = None
         base_out = None
         if want_base_out:
@@ -731,6 +745,17 @@ class BackboneEngine:
             a._relu_mask = mask            # travels with the saved activation to _bn_bwd / _dgrad
         return a, mean, invstd
 
+    def _gem_fwd(self, a, B, hw, feat, training):
+        """Generalized-mean pool of the final map a [B hw, C] into feat; training: also the step counter (as creid_gap_fwd_count)
+        and the saved per-(b, c) quantities, which are returned."""
+        p = self.gem.p
+        if not (p.is_cuda and p.dtype == torch.float32 and p.numel() == 1):
+            raise L.CreidError("the GeM exponent must be one fp32 value on the GPU (move the model with .cuda())")
+        stats = self._empty(3, B, self.cout, dtype=torch.float32) if training else None
+        L.check(L.lib().creid_gem_fwd(L.ptr(a), B, hw, self.cout, self.dt, L.ptr(p), self.gem.eps, L.ptr(feat), L.ptr(stats),
+                                      L.ptr(self._pending_steps) if training else None, L.stream()), "gem_fwd")
+        return stats
+
     # ---- forward
     def forward(self, x_nchw, training: bool, want_base_out: bool = False):
         """x_nchw: fp32 [B, 3, H, W] on the GPU, or a transforms.StemOperand (same batch, already in the stem's layout)."""
@@ -831,7 +856,11 @@ class BackboneEngine:
                                          x3=x3, a3=a3, m3=m3, i3=i3))
             a, h, w = a3, h3, w3
         feat = self._empty(B, self.cout, dtype=torch.float32)
-        if training:
+        if self.gem is not None:
+            # the final map itself is kept for the backward (with the average pool nothing reads it after this launch when the
+            # ReLU masks travel as bits), next to the per-(b, c) quantities the forward saves
+            sv["gem"] = (a, self._gem_fwd(a, B, h * w, feat, training))
+        elif training:
             L.check(lib.creid_gap_fwd_count(L.ptr(a), B, h * w, self.cout, self.dt, L.ptr(feat), L.ptr(self._pending_steps), st), "gap_fwd")
         else:
             L.check(lib.creid_gap_fwd(L.ptr(a), B, h * w, self.cout, self.dt, L.ptr(feat), st), "gap_fwd")
@@ -1000,7 +1029,22 @@ class BackboneEngine:
             if self.loss_scaler is not None and self.dtype == torch.float16:
                 dfeat = self.loss_scaler.scale_(dfeat)        # every f16 gradient tensor / backbone parameter gradient below is scaled
             g = self._empty(B * h * w, self.cout)
-            L.check(lib.creid_gap_bwd(L.ptr(dfeat), B, h * w, self.cout, self.dt, L.ptr(g), st), "gap_bwd")
+            if self.gem is not None:
+                a_fin, stats = sv["gem"]
+                p = self.gem.p
+                # p.grad is final after this call, before any gradient of layer 4: the data-parallel bucket that closes with
+                # layer 4 (it runs to the end of the flat buffer, `gap.p` sits behind layer 4 in it) carries it
+                dp = self._grad_of(p) if p.requires_grad else None
+                parts = None
+                if dp is not None:
+                    parts = self._empty(lib.creid_gem_bwd_partials(B, self.cout, self.dt), dtype=torch.float32)
+                L.check(lib.creid_gem_bwd(L.ptr(a_fin), L.ptr(dfeat), L.ptr(stats), B, h * w, self.cout, self.dt, L.ptr(p),
+                                          self.gem.eps, L.ptr(g), L.ptr(dp), L.ptr(parts), st), "gem_bwd")
+            else:
+                L.check(lib.creid_gap_bwd(L.ptr(dfeat), B, h * w, self.cout, self.dt, L.ptr(g), st), "gap_bwd")
+        elif self.gem is not None:
+            raise L.CreidError("a pooled-back gradient g comes from creid_ctl_heads_fused, which applies the average pool's "
+                               "backward: with pooling='gem' hand backward() the feature gradient dfeat")
         else:
             assert g.dtype == self.dtype and tuple(g.shape) == (B * h * w, self.cout) and g.is_contiguous()
         blocks = list(zip(self.blocks, sv["blocks"]))

@@ -7,7 +7,10 @@ cfg.USE_MIXED_PRECISION) or torch.float32 (parity mode, exact-f32 MFMA).  `eval_
 (validation, inference) on a second engine over the same fp32 master weights: fp32 activations, convolutions as three bf16
 MFMAs per product on split operands -- fp32-grade embeddings at several times the fp32 mode's rate; training keeps
 `compute_dtype`.  `compute_dtype="bf16x3"` trains in that mode too: the fp32 mode's schedule with every non-stem convolution
-(forward, data gradient, weight gradient) on the split-operand bf16 path; its eval-mode forward is the bf16x3 one."""
+(forward, data gradient, weight gradient) on the split-operand bf16 path; its eval-mode forward is the bf16x3 one.
+`pooling="gem"` replaces the global average pool between the final map and the embedding by generalized-mean pooling with one
+trainable exponent (`gap.p`, start value `gem_p`; Radenovic et al., TPAMI 2019) in every forward and in the backward; the default
+`pooling="avg"` is the reference's mean and adds nothing to the state dict."""
 from __future__ import annotations
 
 import torch
@@ -17,11 +20,42 @@ from . import _lib as L
 from . import backbone as bb
 
 
+GEM_P_RANGE = (1.0, 8.0)
+
+
+class GemPool(nn.Module):
+    """Owner of the generalized-mean pool's exponent: y = (mean_hw max(x, eps)^p)^(1/p).  The arithmetic lives in the backbone
+    engine (creid_gem_fwd / creid_gem_bwd); this module is the parameter's home in the state dict (`gap.p`, shape [1], fp32)."""
+
+    def __init__(self, p=3.0, eps=1e-6):
+        super().__init__()
+        if not GEM_P_RANGE[0] <= float(p) <= GEM_P_RANGE[1]:
+            raise ValueError(f"gem_p must lie in [{GEM_P_RANGE[0]:g}, {GEM_P_RANGE[1]:g}], got {p!r}")
+        if not float(eps) > 0:
+            raise ValueError(f"gem_eps must be positive, got {eps!r}")
+        self.p = nn.Parameter(torch.full((1,), float(p), dtype=torch.float32))
+        self.eps = float(eps)
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        # a reference-layout checkpoint has no exponent: it loads (strict too) and p keeps its start value
+        n = len(missing_keys)
+        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
+        if prefix + "p" not in state_dict:
+            del missing_keys[n:]
+
+    def extra_repr(self):
+        return f"eps={self.eps:g}"
+
+
 class Baseline(nn.Module):
     in_planes = 2048
 
-    def __init__(self, cfg, compute_dtype=None, eval_precision=None):
+    def __init__(self, cfg, compute_dtype=None, eval_precision=None, pooling="avg", gem_p=3.0, gem_eps=1e-6):
         super().__init__()
+        if pooling not in bb.POOLINGS:
+            raise ValueError(f"pooling must be one of {bb.POOLINGS}, got {pooling!r}")
+        self.pooling = pooling
+        gap = GemPool(gem_p, gem_eps) if pooling == "gem" else None       # (refused before any weight is built or loaded)
         last_stride = cfg.MODEL.LAST_STRIDE
         model_name = cfg.MODEL.NAME
         self.use_mixed_precision = cfg.USE_MIXED_PRECISION
@@ -29,6 +63,8 @@ class Baseline(nn.Module):
         # 2048); resnet18 / resnet34 (BasicBlock, in_planes 512; round 6)
         self.base = bb.build_backbone(model_name, last_stride)
         self.in_planes = self.base.out_channels
+        if gap is not None:
+            self.gap = gap                 # `gap.p`, behind `base.*` in named_parameters(): the reference's name for its pooling
         self.model_name = model_name
         if cfg.MODEL.PRETRAINED and not cfg.MODEL.RESUME_TRAINING and not cfg.TEST.ONLY_TEST:
             self.base.load_param(cfg.MODEL.PRETRAIN_PATH)      # modelling/baseline.py:84-87
@@ -54,13 +90,16 @@ class Baseline(nn.Module):
             return eng.mode == cd and eng.x3_train
         return eng.mode is None and eng.dtype == cd
 
+    def _pool_args(self):
+        return dict(pooling=self.pooling, gem=getattr(self, "gap", None))
+
     @property
     def engine(self):
         if self._engine is None or not self._engine_matches(self._engine):
             if isinstance(self.compute_dtype, str):
-                self._engine = bb.BackboneEngine(self.base, self.compute_dtype, trainable=True)
+                self._engine = bb.BackboneEngine(self.base, self.compute_dtype, trainable=True, **self._pool_args())
             else:
-                self._engine = bb.BackboneEngine(self.base, self.compute_dtype)
+                self._engine = bb.BackboneEngine(self.base, self.compute_dtype, **self._pool_args())
         self._engine.loss_scaler = self.loss_scaler
         return self._engine
 
@@ -69,7 +108,7 @@ class Baseline(nn.Module):
         if training or self.eval_precision is None or self.eval_precision == self.compute_dtype:
             return self.engine
         if self._eval_engine is None or self._eval_engine.mode != self.eval_precision:
-            self._eval_engine = bb.BackboneEngine(self.base, self.eval_precision)
+            self._eval_engine = bb.BackboneEngine(self.base, self.eval_precision, **self._pool_args())
         return self._eval_engine
 
     def state_dict(self, *args, **kwargs):

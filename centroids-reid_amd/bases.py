@@ -147,8 +147,10 @@ def load_checkpoint_file(path, map_location="cpu"):
 
 class ModelBase(_Base):
     def __init__(self, cfg=None, test_dataloader=None, compute_dtype=None, eval_precision=None, eval_prefilter=None,
-                 eval_query_expansion=None, eval_roc=None, **kwargs):
-        """eval_prefilter=torch.bfloat16 | torch.float16: get_val_metrics runs its streamed evaluation with the counting
+                 eval_query_expansion=None, eval_roc=None, pooling="avg", gem_p=3.0, gem_eps=1e-6, **kwargs):
+        """pooling="gem" (with gem_p, gem_eps): the backbone pools its final map with a trainable generalized mean instead of the
+        average (Baseline; the exponent is `backbone.gap.p`, in the Adam group).  Keywords, not config keys.
+        eval_prefilter=torch.bfloat16 | torch.float16: get_val_metrics runs its streamed evaluation with the counting
         contraction on the 16-bit MFMA and the fp32 results (R1_mAP(prefilter=...)); not with camera-aware centroids.
         eval_query_expansion=True | a dict of k / alpha / rounds / scope: get_val_metrics expands the normalised rows by their
         nearest neighbours before ranking (R1_mAP(query_expansion=...); needs TEST.FEAT_NORM).
@@ -175,7 +177,8 @@ class ModelBase(_Base):
         if test_dataloader is not None:
             self.test_dataloader = test_dataloader
 
-        self.backbone = Baseline(self.hparams, compute_dtype=compute_dtype, eval_precision=eval_precision)
+        self.backbone = Baseline(self.hparams, compute_dtype=compute_dtype, eval_precision=eval_precision, pooling=pooling,
+                                 gem_p=gem_p, gem_eps=gem_eps)
         self.backbone.return_base_out = False            # this module only reads global_feat (modelling/bases.py:171)
         self.contrastive_loss = TripletLoss(self.hparams.SOLVER.MARGIN, self.hparams.SOLVER.DISTANCE_FUNC)
         d_model = self.hparams.MODEL.BACKBONE_EMB_SIZE
@@ -295,6 +298,8 @@ class ModelBase(_Base):
         ckpt = load_checkpoint_file(checkpoint_path, map_location)
         hp = _to_attr({**_plain_dict(ckpt["hyper_parameters"]), **overrides})
         hp["MODEL"]["PRETRAINED"] = False            # weights come from the checkpoint, not from ImageNet
+        if "backbone.gap.p" in ckpt["state_dict"]:   # written by a GeM model: the pooling mode is no hyper-parameter key
+            hp.setdefault("pooling", "gem")
         model = cls(cfg=None, **hp)
         model.load_state_dict(ckpt["state_dict"], strict=strict)
         return model

@@ -227,7 +227,10 @@ class CTLModel(ModelBase):
         dev = feat.device
         labels = class_labels.to(torch.int64).contiguous()
         margin = float(self.contrastive_loss.margin)
-        if self.heads_one_call and B <= 256 and D % 8 == 0 and getattr(eng, "saved", None) is not None:
+        # (the last of the six launches pools the gradient back with the average pool's expression: a GeM backbone takes the
+        # separate launches below, which end at dfeat, and pools back in eng.backward)
+        if (self.heads_one_call and B <= 256 and D % 8 == 0 and getattr(eng, "saved", None) is not None
+                and getattr(eng, "pooling", "avg") == "avg"):
             return self._heads_one_call(eng, feat, labels, P, K, real)
         f32 = dict(dtype=torch.float32, device=dev)
         i32 = dict(dtype=torch.int32, device=dev)

@@ -1029,6 +1029,25 @@ int creid_gap_fwd(const void* x, int64_t B, int64_t HW, int64_t C, int dtype, fl
 int creid_gap_fwd_count(const void* x, int64_t B, int64_t HW, int64_t C, int dtype, float* feat, int64_t* forward_counter,
                         void* stream);
 int creid_gap_bwd(const float* dfeat, int64_t B, int64_t HW, int64_t C, int dtype, void* dx, void* stream);
+/* Generalized-mean pooling with a trainable exponent, the opt-in replacement of the average pool (csrc/gem_pool.hip):
+ *   u = max(x, eps), m = mean_hw u^p, feat = m^(1/p)        x [B, HW, C] in `dtype` (post-ReLU), feat fp32 [B, C].
+ * p: ONE float on the device, read by the kernels (a captured training step sees the optimiser's updates); 1 <= p <= 8 is the
+ * supported range, eps > 0.  The sums are formed relative to the per-(b, c) maximum, so every output is finite for every finite
+ * input in that range.  C % 4 == 0 for CREID_F32 and C % 8 == 0 for the 16-bit types, any HW >= 1, B <= 65535; NULL x / p /
+ * feat, a C off the vector width or eps <= 0 return CREID_E_ARG and any other dtype CREID_E_DTYPE before anything is launched.
+ * creid_gem_fwd: stats (optional, fp32 [3][B][C]) receives what the backward needs per (b, c): the maximum, the coefficient
+ * of dx and dfeat's coefficient in dp; NULL (eval) skips them.  forward_counter (optional, int64 on the device): += 1, as
+ * creid_gap_fwd_count.
+ * creid_gem_bwd: one pass over the saved map x: dx [B, HW, C] in `dtype` = dfeat * (1/HW) * m^(1/p - 1) * u^(p - 1) where
+ * x >= eps and a true zero below (the gradient of clamp(min = eps)); a loss scale carried by dfeat is carried by dx and dp.
+ * p_grad (optional, ONE float): += dp, summed deterministically -- one partial per workgroup into partials
+ * (creid_gem_bwd_partials(B, C, dtype) floats, required with p_grad), then a fixed-order sum in a second, one-workgroup launch;
+ * no floating-point atomics, two calls give the same bits. */
+int64_t creid_gem_bwd_partials(int64_t B, int64_t C, int dtype);
+int creid_gem_fwd(const void* x, int64_t B, int64_t HW, int64_t C, int dtype, const float* p, float eps, float* feat,
+                  float* stats, int64_t* forward_counter, void* stream);
+int creid_gem_bwd(const void* x, const float* dfeat, const float* stats, int64_t B, int64_t HW, int64_t C, int dtype,
+                  const float* p, float eps, void* dx, float* p_grad, float* partials, void* stream);
 /* NHWC compute dtype -> NCHW fp32 (to return `base_out` in the reference's layout). */
 int creid_nhwc_to_nchw_f32(const void* x, int64_t B, int64_t HW, int64_t C, int dtype, float* y, void* stream);
 
