@@ -245,6 +245,66 @@ class _ConvUnit:
         self.fold = None               # eval mode: BatchNorm as a per-channel affine, float [2][cout] (view of one flat buffer)
 
 
+@dataclasses.dataclass(slots=True)
+class SavedLayer:
+    """One convolution + normalisation of a forward, as its helper returns it and as the backward reads it (no temporaries).
+    `act`: the normalised output, or None where the layer kept statistics only and its apply rides in another launch (`ss`,
+    scale / shift, is set until that launch has read it).  `bits`: the ReLU mask, one bit per element -- it lives nowhere else.
+    `relu` = False: no ReLU follows the normalisation, the backward masks by neither `act` nor `bits`."""
+    unit: _ConvUnit
+    x: torch.Tensor                # raw convolution output [M, cout]
+    mean: torch.Tensor
+    invstd: torch.Tensor
+    h: int
+    w: int
+    relu: bool
+    act: torch.Tensor = None
+    bits: torch.Tensor = None
+    ss: torch.Tensor = None
+
+    @property
+    def hw(self):
+        return self.h * self.w
+
+
+@dataclasses.dataclass(slots=True)
+class SavedBlock:
+    a_in: torch.Tensor             # the block's input [B hin win, cin]
+    hin: int
+    win: int
+    c1: SavedLayer
+    c2: SavedLayer
+    c3: SavedLayer = None          # None: BasicBlock
+    ds: SavedLayer = None          # None: identity shortcut
+
+
+@dataclasses.dataclass(slots=True)
+class SavedStem:
+    xpad: torch.Tensor
+    bn: SavedLayer                 # x = conv1's output (x0); act = the full-resolution bn1 output (y0), None when bn1 + max-pool ran fused
+    idx: torch.Tensor              # the max-pool's taps
+
+
+@dataclasses.dataclass(slots=True)
+class SavedStep:
+    B: int
+    H: int
+    W: int
+    stem: SavedStem
+    blocks: list
+    final: tuple                   # (h, w) of the last feature map
+    gem: tuple = None              # pooling="gem": (the last feature map, what creid_gem_fwd saved)
+
+
+@dataclasses.dataclass(slots=True)
+class WredJob:
+    """A weight gradient's split reduction that waits for a launch to ride in."""
+    desc: L.ConvDesc
+    grad: torch.Tensor
+    ws: torch.Tensor
+    nbytes: int
+
+
 @dataclasses.dataclass(frozen=True)
 class Schedule:
     """Which launches the engine issues and in which order, decided once per engine by resolve_schedule()."""
@@ -399,7 +459,7 @@ class BackboneEngine:
         self._keep = []                # replaced workspaces, kept until backward() ends
         self.loss_scaler = None        # f16 training: solver.LossScaler; backward() multiplies the incoming head gradient by its scale
         self._bn_sums = {}             # id(unit) -> coefficient tensor whose finalize has already been issued
-        self._wred_pending = []        # FIFO of (desc, grad tensor, workspace, nbytes)
+        self._wred_pending = []        # FIFO of WredJob
         self._wred_ws = [None, None, None]
         self._wred_flip = 0
         self.on_group_done = None
@@ -407,7 +467,7 @@ class BackboneEngine:
         for k, layer in enumerate((net.layer1, net.layer2, net.layer3, net.layer4), start=1):
             self._group_first[o] = k
             o += len(layer)
-        self.saved = None
+        self.saved = None              # SavedStep: what a training forward leaves for backward(), which drops it (so does an eval forward)
         self._pending_steps = None     # device counter of training forwards not yet folded into num_batches_tracked
         self._fold_key = None
 
@@ -429,6 +489,9 @@ class BackboneEngine:
 
     def _empty(self, *shape, dtype=None):
         return torch.empty(shape, dtype=dtype or self.dtype, device=self.device)
+
+    def _relu_bits(self, a):           # the buffer for the ReLU mask of `a`, one bit per element; None where the schedule keeps no bits
+        return torch.empty(a.numel() // 8, dtype=torch.uint8, device=self.device) if self.sched.relu_bitmask else None
 
     def _workspace(self, nbytes):
         if self._ws is None or self._ws.numel() < nbytes:
@@ -584,7 +647,8 @@ class BackboneEngine:
             if a1_next is not None:
                 a1, h1, w1, a1_next = a1_next, hin, win, None
             elif b["c1"].ibn is not None:
-                _, a1, _, _, h1, w1 = self._conv_bn(b["c1"], a_in, B, hin, win, False, True)
+                c1 = self._conv_bn(b["c1"], a_in, B, hin, win, False, True)
+                a1, h1, w1 = c1.act, c1.h, c1.w
             else:
                 a1, h1, w1 = self._conv_fold(b["c1"], a_in, B, hin, win, True)
             a2, h2, w2 = self._conv_fold(b["c2"], a1, B, h1, w1, True)
@@ -611,7 +675,7 @@ class BackboneEngine:
                     L.check(lib.creid_bottleneck_c3_c1_fwd_stats(M3, 64, 256, 64, L.ptr(a2), L.ptr(b["c3"].w_krsc), L.ptr(b["c3"].fold),
                                                                  L.ptr(r), L.ptr(a), L.ptr(nb["c1"].w_krsc), L.ptr(x1), L.ptr(part),
                                                                  self.dt, st), "bottleneck_c3_c1_fwd_stats")
-                    a1_next = self._ibn_tail(nb["c1"], x1, B, h2 * w2, False, True, part)[0]
+                    a1_next = self._ibn_tail(nb["c1"], x1, B, h2, w2, False, True, part).act
                 h, w = h2, w2
             else:
                 a, h, w = self._conv_fold(b["c3"], a2, B, h2, w2, True, residual=r)
@@ -628,47 +692,43 @@ class BackboneEngine:
         return base_out, feat
 
     def _conv_bn(self, u, a_in, B, H, W, training, relu, residual=None, residual_ss=None, apply=True):
-        """conv -> BN(batch or running stats) -> (+residual) -> (ReLU).  Returns (x_raw, a_out, mean, invstd, oh, ow).
-        apply=False: statistics only, a_out is the (scale, shift) pair instead (the downsample branch: its normalisation
+        """conv -> BN(batch or running stats) -> (+residual) -> (ReLU).  Returns the SavedLayer.
+        apply=False: statistics only, the layer has `ss` and no `act` (the downsample branch: its normalisation
         happens inside the block's bn3 pass, which takes the raw tensor as `residual` and that pair as `residual_ss`)."""
         lib, st = L.lib(), L.stream()
         d, oh, ow = _desc(B, H, W, u.cin, u.cout, u.k, u.stride, u.pad)
-        M = B * oh * ow
-        x = self._empty(M, u.cout)
-        if u.ibn is not None:
-            # the conv epilogue's per-128-row (sum, sumsq) partials are per-image row blocks when HW % 128 == 0:
-            # IBN then needs no statistics pass of its own (InstanceNorm uses instance statistics in eval too)
-            part = None
-            if (oh * ow) % 128 == 0:
-                part = self._empty(lib.creid_conv2d_bn_partial_rows(C.byref(d)) * 2, u.cout, dtype=torch.float32)
-            L.check(lib.creid_conv2d_fwd_nhwc(C.byref(d), L.ptr(a_in), L.ptr(u.w_krsc), L.ptr(x), L.ptr(part), self.conv_dt, st),
-                    "conv2d_fwd")
-            return (x,) + self._ibn_tail(u, x, B, oh * ow, training, relu, part) + (oh, ow)
-        rows = lib.creid_conv2d_bn_partial_rows(C.byref(d)) if training else 0
-        part = self._empty(rows * 2, u.cout, dtype=torch.float32) if training else None
+        x = self._empty(B * oh * ow, u.cout)
+        # the conv epilogue's per-128-row (sum, sumsq) partials are per-image row blocks when HW % 128 == 0:
+        # IBN then needs no statistics pass of its own (InstanceNorm uses instance statistics in eval too)
+        stats = training if u.ibn is None else (oh * ow) % 128 == 0
+        rows = lib.creid_conv2d_bn_partial_rows(C.byref(d)) if stats else 0
+        part = self._empty(rows * 2, u.cout, dtype=torch.float32) if stats else None
         L.check(lib.creid_conv2d_fwd_nhwc(C.byref(d), L.ptr(a_in), L.ptr(u.w_krsc), L.ptr(x), L.ptr(part), self.conv_dt, st),
                 "conv2d_fwd")
-        return (x,) + self._bn_tail(u, x, part, rows, M, training, relu, residual, residual_ss, apply) + (oh, ow)
+        if u.ibn is not None:
+            return self._ibn_tail(u, x, B, oh, ow, training, relu, part)
+        return self._bn_tail(u, x, part, rows, oh, ow, training, relu, residual, residual_ss, apply)
 
-    def _conv3_axf(self, u, x_raw, ss, B, H, W, residual, residual_ss):
-        """conv3 of a bottleneck on conv2's RAW output: bn2 + ReLU on the operand path, the normalised tensor and its ReLU bits as
-        side outputs (what the backward reads), then bn3 as usual.  Returns (x3, a2, a3, mean3, invstd3, oh, ow)."""
+    def _conv3_axf(self, u, c2, B, residual, residual_ss):
+        """conv3 of a bottleneck on conv2's RAW output (c2: its statistics-only layer): bn2 + ReLU on the operand path, the
+        normalised tensor and its ReLU bits as side outputs (what the backward reads: they complete c2), then bn3 as usual."""
         lib, st = L.lib(), L.stream()
-        d, oh, ow = _desc(B, H, W, u.cin, u.cout, 1, 1, 0)
+        d, oh, ow = _desc(B, c2.h, c2.w, u.cin, u.cout, 1, 1, 0)
         M = B * oh * ow
         x = self._empty(M, u.cout)
         rows = lib.creid_conv2d_bn_partial_rows(C.byref(d))
         part = self._empty(rows * 2, u.cout, dtype=torch.float32)
         a_in = self._empty(M, u.cin)
         mask = torch.empty(M * u.cin // 8, dtype=torch.uint8, device=self.device)
-        L.check(lib.creid_conv1x1_bnrelu_fwd(L.ptr(x_raw), L.ptr(ss), L.ptr(u.w_krsc), M, u.cin, u.cout, L.ptr(x), L.ptr(part),
+        L.check(lib.creid_conv1x1_bnrelu_fwd(L.ptr(c2.x), L.ptr(c2.ss), L.ptr(u.w_krsc), M, u.cin, u.cout, L.ptr(x), L.ptr(part),
                                              L.ptr(a_in), L.ptr(mask), self.dt, st), "conv1x1_bnrelu_fwd")
-        a_in._relu_mask = mask
-        return (x, a_in) + self._bn_tail(u, x, part, rows, M, True, True, residual, residual_ss, True) + (oh, ow)
+        c2.act, c2.bits, c2.ss = a_in, mask, None
+        return self._bn_tail(u, x, part, rows, oh, ow, True, True, residual, residual_ss, True)
 
-    def _ibn_tail(self, u, x, B, HW, training, relu, part=None):
+    def _ibn_tail(self, u, x, B, h, w, training, relu, part=None):
         lib, st = L.lib(), L.stream()
         ibn, bn = u.ibn, u.bn
+        HW = h * w
         rpi = lib.creid_ibn_rows_per_image(HW)
         ready = 1 if part is not None else 0
         if part is None:
@@ -677,20 +737,16 @@ class BackboneEngine:
         invstd = self._empty(B, u.cout, dtype=torch.float32)
         ss = self._empty(B * 2, u.cout, dtype=torch.float32)
         a = self._empty(B * HW, u.cout)
-        mask = None
-        if training and relu and self.sched.relu_bitmask:
-            mask = torch.empty(B * HW * u.cout // 8, dtype=torch.uint8, device=self.device)
+        mask = self._relu_bits(a) if training and relu else None
         L.check(lib.creid_ibn_fwd_mask(L.ptr(x), B, HW, u.cout, ibn.half, L.ptr(ibn.IN.weight), L.ptr(ibn.IN.bias),
                                        L.ptr(bn.weight), L.ptr(bn.bias), L.ptr(bn.running_mean), L.ptr(bn.running_var),
                                        1 if training else 0, bn.momentum, bn.eps, 1 if relu else 0, self.dt, L.ptr(part), ready,
                                        L.ptr(mean), L.ptr(invstd), L.ptr(ss), L.ptr(a), L.ptr(mask), st), "ibn_fwd")
-        if mask is not None:
-            a._relu_mask = mask
-        return a, mean, invstd
+        return SavedLayer(u, x, mean, invstd, h, w, relu, act=a, bits=mask)
 
-    def _ibn_bwd(self, u, x, g, act, mean, invstd, B, HW, part=None):
+    def _ibn_bwd(self, layer, g, B, part=None):
         lib, st = L.lib(), L.stream()
-        ibn, bn = u.ibn, u.bn
+        u, ibn, bn, HW = layer.unit, layer.unit.ibn, layer.unit.bn, layer.hw
         rpi = lib.creid_ibn_rows_per_image(HW)
         ready = 1 if part is not None else 0
         if part is None:
@@ -698,16 +754,16 @@ class BackboneEngine:
         coef = self._empty(B * 3, u.cout, dtype=torch.float32)
         per_img = self._empty(B * 2, ibn.half, dtype=torch.float32)
         dx = self._empty(B * HW, u.cout)
-        mask = getattr(act, "_relu_mask", None) if act is not None else None
-        L.check(lib.creid_ibn_bwd_mask(L.ptr(x), L.ptr(g), L.ptr(act), L.ptr(mask), L.ptr(mean), L.ptr(invstd), B, HW, u.cout, ibn.half,
-                                  L.ptr(ibn.IN.weight), L.ptr(bn.weight), self.dt, L.ptr(part), ready, L.ptr(coef), L.ptr(per_img),
-                                  L.ptr(self._grad_of(ibn.IN.weight)), L.ptr(self._grad_of(ibn.IN.bias)),
-                                  L.ptr(self._grad_of(bn.weight)), L.ptr(self._grad_of(bn.bias)), L.ptr(dx), st), "ibn_bwd")
-        return dx, None
+        L.check(lib.creid_ibn_bwd_mask(L.ptr(layer.x), L.ptr(g), L.ptr(layer.act), L.ptr(layer.bits), L.ptr(layer.mean),
+                                       L.ptr(layer.invstd), B, HW, u.cout, ibn.half, L.ptr(ibn.IN.weight), L.ptr(bn.weight), self.dt,
+                                       L.ptr(part), ready, L.ptr(coef), L.ptr(per_img), L.ptr(self._grad_of(ibn.IN.weight)),
+                                       L.ptr(self._grad_of(ibn.IN.bias)), L.ptr(self._grad_of(bn.weight)),
+                                       L.ptr(self._grad_of(bn.bias)), L.ptr(dx), st), "ibn_bwd")
+        return dx
 
-    def _bn_tail(self, u, x, part, rows, M, training, relu, residual, residual_ss=None, apply=True):
+    def _bn_tail(self, u, x, part, rows, h, w, training, relu, residual, residual_ss=None, apply=True):
         lib, st = L.lib(), L.stream()
-        bn = u.bn
+        bn, M = u.bn, x.shape[0]
         mean = self._empty(u.cout, dtype=torch.float32)
         invstd = self._empty(u.cout, dtype=torch.float32)
         ss = self._empty(2, u.cout, dtype=torch.float32)
@@ -716,34 +772,26 @@ class BackboneEngine:
                 and u.cout % (32 if self.dtype == torch.float32 else 64) == 0):
             # finalize + apply in ONE launch (CREID_FIN_APPLY=<max statistic rows>; profiles/r05_fin_apply.md)
             a = self._empty(M, u.cout)
-            mask = None
-            if relu and sched.relu_bitmask:
-                mask = torch.empty(M * u.cout // 8, dtype=torch.uint8, device=self.device)
+            mask = self._relu_bits(a) if relu else None
             L.check(lib.creid_bn2d_finalize_apply_mask(L.ptr(part), rows, u.cout, M, L.ptr(bn.running_mean), L.ptr(bn.running_var),
                                                        bn.momentum, bn.eps, L.ptr(bn.weight), L.ptr(bn.bias), L.ptr(mean), L.ptr(invstd),
                                                        L.ptr(ss), L.ptr(x), L.ptr(residual), 1 if relu else 0, self.dt, L.ptr(a),
                                                        L.ptr(mask), sched.fin_apply_rb, st), "bn2d_finalize_apply")
-            if mask is not None:
-                a._relu_mask = mask
-            return a, mean, invstd
+            return SavedLayer(u, x, mean, invstd, h, w, relu, act=a, bits=mask)
         L.check(lib.creid_bn2d_finalize(L.ptr(part), rows, u.cout, M, L.ptr(bn.running_mean), L.ptr(bn.running_var),
                                         1 if training else 0, bn.momentum, bn.eps, L.ptr(bn.weight), L.ptr(bn.bias),
                                         L.ptr(mean), L.ptr(invstd), L.ptr(ss), st), "bn2d_finalize")
         if not apply:
-            return ss, mean, invstd
+            return SavedLayer(u, x, mean, invstd, h, w, relu, ss=ss)
         a = self._empty(M, u.cout)
-        mask = None
-        if training and relu and sched.relu_bitmask:
-            mask = torch.empty(M * u.cout // 8, dtype=torch.uint8, device=self.device)
+        mask = self._relu_bits(a) if training and relu else None
         if residual_ss is not None:
             L.check(lib.creid_bn2d_apply_dual_mask(L.ptr(x), L.ptr(ss), L.ptr(residual), L.ptr(residual_ss), 1 if relu else 0, M,
                                                    u.cout, self.dt, L.ptr(a), L.ptr(mask), st), "bn2d_apply_dual")
         else:
             L.check(lib.creid_bn2d_apply_mask(L.ptr(x), L.ptr(ss), L.ptr(residual), 1 if relu else 0, M, u.cout, self.dt,
                                               L.ptr(a), L.ptr(mask), st), "bn2d_apply")
-        if mask is not None:
-            a._relu_mask = mask            # travels with the saved activation to _bn_bwd / _dgrad
-        return a, mean, invstd
+        return SavedLayer(u, x, mean, invstd, h, w, relu, act=a, bits=mask)      # the bits travel to _bn_bwd / _dgrad with it
 
     def _gem_fwd(self, a, B, hw, feat, training):
         """Generalized-mean pool of the final map a [B hw, C] into feat; training: also the step counter (as creid_gap_fwd_count)
@@ -778,10 +826,10 @@ class BackboneEngine:
             return self._forward_eval_folded(x_nchw, want_base_out)
         # (f16 -- the reference's precision=16, utils/misc.py:111 -- trains like bf16; its gradients need the dynamic loss scale
         # that ModelBase.configure_optimizers attaches as `loss_scaler`: solver.LossScaler)
-        sv = {"B": B, "H": H, "W": W, "training": training}
-        if training:      # ONE device counter per step instead of 53 per-layer `num_batches_tracked += 1`; the increment itself
-            if self._pending_steps is None:          # rides in the forward's last launch (creid_gap_fwd_count)
-                self._pending_steps = torch.zeros((), dtype=torch.long, device=self.device)
+        if training and self._pending_steps is None:
+            # ONE device counter per step instead of 53 per-layer `num_batches_tracked += 1`; the increment itself rides in the
+            # forward's last launch (creid_gap_fwd_count)
+            self._pending_steps = torch.zeros((), dtype=torch.long, device=self.device)
         # stem
         xpad = self._stem_operand(x_nchw, B, H, W)
         H1, W1 = H // 2, W // 2
@@ -797,75 +845,51 @@ class BackboneEngine:
         if sched.stem_fuse_pool and not self.net.stem_relu:
             # bn1 + maxpool in one pass over the raw conv output: the normalised 64-channel full-resolution tensor is read
             # by nothing else (no stem ReLU -> the backward needs no mask of it either) and is never written
-            bn = self.stem.bn
-            mean0 = self._empty(64, dtype=torch.float32); invstd0 = self._empty(64, dtype=torch.float32)
-            ss = self._empty(2, 64, dtype=torch.float32)
-            L.check(lib.creid_bn2d_finalize(L.ptr(part), rows, 64, M0, L.ptr(bn.running_mean), L.ptr(bn.running_var),
-                                            1 if training else 0, bn.momentum, bn.eps, L.ptr(bn.weight), L.ptr(bn.bias),
-                                            L.ptr(mean0), L.ptr(invstd0), L.ptr(ss), st), "bn2d_finalize")
-            L.check(lib.creid_bn2d_apply_maxpool3x3s2(L.ptr(x0), L.ptr(ss), 0, B, H1, W1, 64, self.dt, L.ptr(p0), L.ptr(idx0),
+            bn0 = self._bn_tail(self.stem, x0, part, rows, H1, W1, training, False, None, apply=False)
+            L.check(lib.creid_bn2d_apply_maxpool3x3s2(L.ptr(x0), L.ptr(bn0.ss), 0, B, H1, W1, 64, self.dt, L.ptr(p0), L.ptr(idx0),
                                                       st), "bn2d_apply_maxpool")
-            y0 = None
+            bn0.ss = None
         else:
-            y0, mean0, invstd0 = self._bn_tail(self.stem, x0, part, rows, M0, training, self.net.stem_relu, None)
-            L.check(lib.creid_maxpool3x3s2_fwd(L.ptr(y0), B, H1, W1, 64, self.dt, L.ptr(p0), L.ptr(idx0), st), "maxpool_fwd")
-        sv["stem"] = (xpad, x0, y0, mean0, invstd0, idx0)
+            bn0 = self._bn_tail(self.stem, x0, part, rows, H1, W1, training, self.net.stem_relu, None)
+            L.check(lib.creid_maxpool3x3s2_fwd(L.ptr(bn0.act), B, H1, W1, 64, self.dt, L.ptr(p0), L.ptr(idx0), st), "maxpool_fwd")
         a, h, w = p0, H2, W2
-        sv["blocks"] = []
+        blocks, gem = [], None
         for b in self.blocks:
-            a_in, hin, win = a, h, w
+            # BasicBlock (resnet.py:33-48): conv1 - bn1 - relu - conv2 - bn2 (+ residual) - relu; a bottleneck has conv3 - bn3 behind
+            # conv2 - bn2 - relu and adds the residual there.  `last`: the convolution whose normalisation takes the residual
+            s = SavedBlock(a, h, w, c1=self._conv_bn(b["c1"], a, B, h, w, training, True), c2=None)
+            last = b["c2"] if self.basic else b["c3"]
+            axf = (not self.basic and training and self.dtype != torch.float32 and sched.relu_bitmask and last.k == 1
+                   and last.stride == 1 and last.cin in sched.c3_axf and last.cin in (64, 128) and b["c2"].ibn is None)
+            if not self.basic:   # axf: conv2 + statistics only, bn2's (scale, shift) go to conv3, which normalises its operand itself
+                s.c2 = self._conv_bn(b["c2"], s.c1.act, B, s.c1.h, s.c1.w, training, True, apply=not axf)
+            r, rss = s.a_in, None
+            if b["ds"] is not None:
+                # downsample branch, dual apply: conv + statistics only; its normalisation rides in the apply pass of `last` (one
+                # launch and the write + read of the normalised branch tensor less per downsample block)
+                s.ds = self._conv_bn(b["ds"], s.a_in, B, s.hin, s.win, training, False, apply=not (self.basic or sched.dual_apply))
+                r, rss = (s.ds.x if s.ds.act is None else s.ds.act), s.ds.ss
+                s.ds.act = s.ds.ss = None        # the backward reads neither: they live as long as this block's forward
             if self.basic:
-                # BasicBlock (resnet.py:33-48): conv1 -> bn1 -> relu -> conv2 -> bn2 (+ residual, through the downsample branch's
-                # BatchNorm where there is one: applied inside bn2's pass like the bottleneck's bn3) -> relu
-                x1, a1, m1, i1, h1, w1 = self._conv_bn(b["c1"], a_in, B, hin, win, training, True)
-                xd = md = idd = rss = None
-                r = a_in
-                if b["ds"] is not None:
-                    xd, rss, md, idd, _, _ = self._conv_bn(b["ds"], a_in, B, hin, win, training, False, apply=False)
-                    r = xd
-                x2, a2, m2, i2, h2, w2 = self._conv_bn(b["c2"], a1, B, h1, w1, training, True, residual=r, residual_ss=rss)
-                if training:
-                    sv["blocks"].append(dict(a_in=a_in, hin=hin, win=win, x1=x1, a1=a1, m1=m1, i1=i1, h1=h1, w1=w1,
-                                             x2=x2, a2=a2, m2=m2, i2=i2, h2=h2, w2=w2, xd=xd, md=md, idd=idd))
-                a, h, w = a2, h2, w2
-                continue
-            x1, a1, m1, i1, h1, w1 = self._conv_bn(b["c1"], a_in, B, hin, win, training, True)
-            axf = (training and self.dtype != torch.float32 and sched.relu_bitmask and b["c3"].k == 1
-                   and b["c3"].stride == 1 and b["c3"].cin in sched.c3_axf and b["c3"].cin in (64, 128) and b["c2"].ibn is None)
-            if axf:      # conv2 + statistics only: bn2's (scale, shift) go to conv3, which normalises its operand itself
-                x2, ss2, m2, i2, h2, w2 = self._conv_bn(b["c2"], a1, B, h1, w1, training, True, apply=False)
+                out = s.c2 = self._conv_bn(last, s.c1.act, B, s.c1.h, s.c1.w, training, True, residual=r, residual_ss=rss)
+            elif axf:
+                out = s.c3 = self._conv3_axf(last, s.c2, B, r, rss)
             else:
-                x2, a2, m2, i2, h2, w2 = self._conv_bn(b["c2"], a1, B, h1, w1, training, True)
-            rss = None
-            if b["ds"] is not None and sched.dual_apply:
-                # downsample branch: conv + statistics only; its normalisation rides in bn3's apply pass (one launch and
-                # the write + read of the normalised branch tensor less per downsample block)
-                xd, rss, md, idd, _, _ = self._conv_bn(b["ds"], a_in, B, hin, win, training, False, apply=False)
-                r = xd
-            elif b["ds"] is not None:
-                xd, r, md, idd, _, _ = self._conv_bn(b["ds"], a_in, B, hin, win, training, False)
-            else:
-                xd, r, md, idd = None, a_in, None, None
-            if axf:
-                x3, a2, a3, m3, i3, h3, w3 = self._conv3_axf(b["c3"], x2, ss2, B, h2, w2, r, rss)
-            else:
-                x3, a3, m3, i3, h3, w3 = self._conv_bn(b["c3"], a2, B, h2, w2, training, True, residual=r, residual_ss=rss)
+                out = s.c3 = self._conv_bn(last, s.c2.act, B, s.c2.h, s.c2.w, training, True, residual=r, residual_ss=rss)
+            a, h, w = out.act, out.h, out.w
             if training:
-                sv["blocks"].append(dict(a_in=a_in, hin=hin, win=win, x1=x1, a1=a1, m1=m1, i1=i1, h1=h1, w1=w1,
-                                         x2=x2, a2=a2, m2=m2, i2=i2, h2=h2, w2=w2, xd=xd, md=md, idd=idd,
-                                         x3=x3, a3=a3, m3=m3, i3=i3))
-            a, h, w = a3, h3, w3
+                blocks.append(s)
+            del s                                # (an eval forward keeps no block alive into the next one's launches)
         feat = self._empty(B, self.cout, dtype=torch.float32)
         if self.gem is not None:
             # the final map itself is kept for the backward (with the average pool nothing reads it after this launch when the
             # ReLU masks travel as bits), next to the per-(b, c) quantities the forward saves
-            sv["gem"] = (a, self._gem_fwd(a, B, h * w, feat, training))
+            gem = (a, self._gem_fwd(a, B, h * w, feat, training))
         elif training:
             L.check(lib.creid_gap_fwd_count(L.ptr(a), B, h * w, self.cout, self.dt, L.ptr(feat), L.ptr(self._pending_steps), st), "gap_fwd")
         else:
             L.check(lib.creid_gap_fwd(L.ptr(a), B, h * w, self.cout, self.dt, L.ptr(feat), st), "gap_fwd")
-        sv["final"] = (h, w)
-        self.saved = sv if training else None
+        self.saved = SavedStep(B, H, W, SavedStem(xpad, bn0, idx0), blocks, (h, w), gem) if training else None
         base_out = None
         if want_base_out:
             base_out = self._empty(B, self.cout, h, w, dtype=torch.float32)
@@ -878,50 +902,48 @@ class BackboneEngine:
             p.grad = torch.zeros_like(p)
         return p.grad
 
-    def _bn_bwd(self, u, x, g, act, mean, invstd, M, want_gm=False, part=None, mask=None, reduce2=None):
-        """BN backward; `part` = column-reduction partials already produced by a fused dgrad epilogue; `mask` = ReLU bits
-        to apply to g (default: the ones that travel with `act`).  reduce2 = (x2, mean2, invstd2): the apply pass also produces
-        the column sums of a second BatchNorm backward over the same masked gradient (the downsample branch's); returned in
-        place of gm."""
+    def _bn_bwd(self, layer, g, *, want_gm=False, part=None, mask=None, reduce2=None):
+        """BN backward of `layer`; `part` = column-reduction partials already produced by a fused dgrad epilogue; `mask` = ReLU
+        bits to apply to g (default: the layer's own).  reduce2 = the SavedLayer of a second BatchNorm backward over the same
+        masked gradient (the downsample branch's): the apply pass also produces its column sums.  Returns (dx, gm, part2): gm the
+        masked copy of g with want_gm, part2 those column sums with reduce2, None otherwise."""
         lib, st = L.lib(), L.stream()
+        u, bn, x, mean, invstd, M = layer.unit, layer.unit.bn, layer.x, layer.mean, layer.invstd, layer.x.shape[0]
+        act, bits = (layer.act, layer.bits) if layer.relu else (None, None)
         rows = lib.creid_bn2d_bwd_rows(M)
         ready = 1 if part is not None else 0
         sums = self._bn_sums.pop(id(u), None)
         if sums is not None:
             ready = 2                      # finalize already issued (it rode in a weight-gradient launch): apply only
-        elif part is None:
-            part = self._empty(rows * 2, u.cout, dtype=torch.float32)
-        if sums is None:
+        else:
+            part = part if part is not None else self._empty(rows * 2, u.cout, dtype=torch.float32)
             sums = self._empty(3, u.cout, dtype=torch.float32)
         dx = self._empty(M, u.cout)
         gm = self._empty(M, u.cout) if want_gm else None
-        bn = u.bn
         dgam = self._grad_of(bn.weight) if bn.weight.requires_grad else None
         dbet = self._grad_of(bn.bias) if bn.bias.requires_grad else None
         if ready == 1 and self.sched.fin_with_wred and self._wred_pending:
             # the finalize and the oldest pending split reduction in ONE launch, then apply only
-            rd, rgw, rws, rbytes = self._wred_pending.pop(0)
+            job = self._wred_pending.pop(0)
             L.check(lib.creid_bn2d_bwd_finalize_wred(L.ptr(part), rows, u.cout, M, L.ptr(mean), L.ptr(invstd), L.ptr(bn.weight),
-                                                     L.ptr(sums), L.ptr(dgam), L.ptr(dbet), C.byref(rd), L.ptr(rgw), 1, L.ptr(rws),
-                                                     rbytes, self.dt, st), "bn2d_bwd_finalize_wred")
+                                                     L.ptr(sums), L.ptr(dgam), L.ptr(dbet), C.byref(job.desc), L.ptr(job.grad), 1,
+                                                     L.ptr(job.ws), job.nbytes, self.dt, st), "bn2d_bwd_finalize_wred")
             ready = 2
-        if mask is None and act is not None:
-            mask = getattr(act, "_relu_mask", None)
+        mask = bits if mask is None else mask
         if reduce2 is not None:
-            x2, mean2, invstd2 = reduce2
             part2 = self._empty(rows * 2, u.cout, dtype=torch.float32)
             L.check(lib.creid_bn2d_bwd_mask_reduce2(L.ptr(x), L.ptr(g), L.ptr(mask), L.ptr(mean), L.ptr(invstd), L.ptr(bn.weight), M,
                                                     u.cout, self.dt, L.ptr(part), ready, L.ptr(sums), L.ptr(dgam), L.ptr(dbet),
-                                                    L.ptr(dx), L.ptr(x2), L.ptr(mean2), L.ptr(invstd2), L.ptr(part2), st),
-                    "bn2d_bwd_reduce2")
-            return dx, part2
+                                                    L.ptr(dx), L.ptr(reduce2.x), L.ptr(reduce2.mean), L.ptr(reduce2.invstd),
+                                                    L.ptr(part2), st), "bn2d_bwd_reduce2")
+            return dx, None, part2
         L.check(lib.creid_bn2d_bwd_mask(L.ptr(x), L.ptr(g), L.ptr(act), L.ptr(mask), L.ptr(mean), L.ptr(invstd),
                                         L.ptr(bn.weight), M, u.cout, self.dt, L.ptr(part), ready, L.ptr(sums), L.ptr(dgam),
                                         L.ptr(dbet), L.ptr(dx), L.ptr(gm), st), "bn2d_bwd")
-        return dx, gm
+        return dx, gm, None
 
-    def _wgrad(self, u, a_in, dy, B, H, W, fin=None):
-        """Weight gradient.  fin = (unit, partials, M) of a BatchNorm whose backward finalize should ride in this launch
+    def _wgrad(self, u, a_in, dy, B, H, W, *, fin=None):
+        """Weight gradient.  fin = (SavedLayer, partials) of a BatchNorm whose backward finalize should ride in this launch
         (ignored -- the BatchNorm backward then runs its own finalize -- where the carrier does not apply)."""
         if not u.conv.weight.requires_grad:
             return
@@ -944,32 +966,33 @@ class BackboneEngine:
                 self._wred_ws[k] = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=self.device)
             ws = self._wred_ws[k]
             if fin is not None and self.sched.bnfin_piggyback and fin[1] is not None:
-                fu, fpart, fM, mean, invstd = fin
-                fbn = fu.bn
+                fl, fpart = fin
+                fu, fbn, fM = fl.unit, fl.unit.bn, fl.x.shape[0]
                 sums = self._empty(3, fu.cout, dtype=torch.float32)
                 dgam = self._grad_of(fbn.weight) if fbn.weight.requires_grad else None
                 dbet = self._grad_of(fbn.bias) if fbn.bias.requires_grad else None
                 L.check(lib.creid_conv2d_wgrad_partials_bnfin(C.byref(d), L.ptr(a_in), L.ptr(dy), L.ptr(ws), nbytes, self.dt,
                                                               L.ptr(fpart), lib.creid_bn2d_bwd_rows(fM), fu.cout, fM,
-                                                              L.ptr(mean), L.ptr(invstd), L.ptr(fbn.weight), L.ptr(sums),
+                                                              L.ptr(fl.mean), L.ptr(fl.invstd), L.ptr(fbn.weight), L.ptr(sums),
                                                               L.ptr(dgam), L.ptr(dbet), st), "conv2d_wgrad_partials_bnfin")
                 self._bn_sums[id(fu)] = sums
             else:
                 L.check(lib.creid_conv2d_wgrad_partials(C.byref(d), L.ptr(a_in), L.ptr(dy), L.ptr(ws), nbytes, self.dt, st),
                         "conv2d_wgrad_partials")
-            self._wred_pending.append((d, gw, ws, nbytes))
+            self._wred_pending.append(WredJob(d, gw, ws, nbytes))
             assert len(self._wred_pending) <= 3
             return
         ws = self._workspace(nbytes)
         L.check(lib.creid_conv2d_wgrad_nhwc(C.byref(d), L.ptr(a_in), L.ptr(dy), L.ptr(gw), 1, L.ptr(ws), nbytes, self.dt, st),
                 "conv2d_wgrad")
 
-    def _dgrad(self, u, dy, B, H, W, add_src=None, bnred=None, stat_image_rows=0, add_src_stride=1, add_mask=None):
-        """Data gradient.  bnred = (x, act, mean, invstd) of the BN layer that consumes the result: its column
-        reduction is fused into the epilogue (bf16) and the partials are returned.  stat_image_rows = H*W when
-        mean / invstd are per-(image, channel) (IBN), 0 for BatchNorm."""
+    def _dgrad(self, u, dy, B, H, W, *, add_src=None, consumer=None, add_src_stride=1, add_mask=None, on_output_grid=False):
+        """Data gradient, returns (dx, part).  consumer = the SavedLayer of the normalisation that consumes the result: its
+        backward column reduction is fused into the epilogue (16-bit) and the partials are returned as `part` (else None); IBN has
+        per-(image, channel) statistics and is fused only where the 128-row tiles do not straddle images.  on_output_grid (a
+        stride-2 1 x 1 convolution): the gradient on the even input pixels only, as the plain 1 x 1 GEMM over the output grid H x W."""
         lib, st = L.lib(), L.stream()
-        d, _, _ = _desc(B, H, W, u.cin, u.cout, u.k, u.stride, u.pad)
+        d, _, _ = _desc(B, H, W, u.cin, u.cout, 1, 1, 0) if on_output_grid else _desc(B, H, W, u.cin, u.cout, u.k, u.stride, u.pad)
         M = B * H * W
         dx = self._empty(M, u.cin)
         if self.x3_train:                  # (the fp32 schedule: no fused BatchNorm reduction, no mask, stride-1 add_src)
@@ -977,18 +1000,20 @@ class BackboneEngine:
             L.check(lib.creid_conv2d_dgrad_x3_nhwc(C.byref(d), L.ptr(dy), L.ptr(u.w_crsk), L.ptr(dx), L.ptr(add_src), st),
                     "conv2d_dgrad_x3")
             return dx, None
-        fuse_bn = bnred is not None and self.sched.fuse_bn_reduce
+        per_image = consumer is not None and consumer.unit.ibn is not None
+        fuse_bn = consumer is not None and self.sched.fuse_bn_reduce and not (per_image and consumer.hw % 128 != 0)
         carry = len(self._wred_pending) >= (2 if self.sched.fin_with_wred else 1)   # "wred" mode keeps one job for the finalize launch
         if carry or fuse_bn or add_mask is not None:
-            rd, rgw, rws, rbytes = self._wred_pending.pop(0) if carry else (None, None, None, 0)
-            x, act, mean, invstd = bnred if fuse_bn else (None, None, None, None)
-            mask = getattr(act, "_relu_mask", None) if act is not None else None
-            part = self._empty(lib.creid_bn2d_bwd_rows(M) * 2, u.cin, dtype=torch.float32) if fuse_bn else None
+            job = self._wred_pending.pop(0) if carry else WredJob(None, None, None, 0)
+            x = act = bits = mean = invstd = part = None
+            if fuse_bn:
+                x, act, bits, mean, invstd = consumer.x, consumer.act, consumer.bits, consumer.mean, consumer.invstd
+                part = self._empty(lib.creid_bn2d_bwd_rows(M) * 2, u.cin, dtype=torch.float32)
             L.check(lib.creid_conv2d_dgrad_fused_nhwc(C.byref(d), L.ptr(dy), L.ptr(u.w_crsk), L.ptr(dx), L.ptr(add_src),
-                                                      add_src_stride, L.ptr(add_mask), L.ptr(x), L.ptr(act), L.ptr(mask), L.ptr(mean),
-                                                      L.ptr(invstd), L.ptr(part), stat_image_rows if fuse_bn else 0,
-                                                      C.byref(rd) if rd is not None else None, L.ptr(rgw), 1,
-                                                      L.ptr(rws), rbytes, self.dt, st), "conv2d_dgrad_fused")
+                                                      add_src_stride, L.ptr(add_mask), L.ptr(x), L.ptr(act), L.ptr(bits),
+                                                      L.ptr(mean), L.ptr(invstd), L.ptr(part), consumer.hw if per_image and fuse_bn else 0,
+                                                      C.byref(job.desc) if carry else None, L.ptr(job.grad), 1,
+                                                      L.ptr(job.ws), job.nbytes, self.dt, st), "conv2d_dgrad_fused")
             return dx, part
         L.check(lib.creid_conv2d_dgrad_nhwc(C.byref(d), L.ptr(dy), L.ptr(u.w_crsk), L.ptr(dx), L.ptr(add_src), self.dt, st),
                 "conv2d_dgrad")
@@ -999,17 +1024,13 @@ class BackboneEngine:
         while it writes g: (x3, ReLU bits of the block output, mean, invstd, partial-rows buffer), or None when that reduction
         keeps its own launch (fp32 engine, no mask bits, 128-row tiles that straddle images in the general case are fine)."""
         sv, sched = self.saved, self.sched
-        if self.basic or sv is None or not sv.get("training"):
+        if self.basic or sv is None or not (sched.heads_bnred and sched.fuse_bn_reduce and sched.drop_gm and sched.relu_bitmask):
             return None
-        if not (sched.heads_bnred and sched.fuse_bn_reduce and sched.drop_gm and sched.relu_bitmask):
+        c3 = sv.blocks[-1].c3
+        if c3.bits is None or c3.unit.cout % 256 != 0:
             return None
-        s = sv["blocks"][-1]
-        mask = getattr(s["a3"], "_relu_mask", None)
-        if mask is None or s["x3"].shape[1] % 256 != 0:
-            return None
-        M = s["x3"].shape[0]
-        part = self._empty(L.lib().creid_bn2d_bwd_rows(M) * 2, s["x3"].shape[1], dtype=torch.float32)
-        return s["x3"], mask, s["m3"], s["i3"], part
+        part = self._empty(L.lib().creid_bn2d_bwd_rows(c3.x.shape[0]) * 2, c3.unit.cout, dtype=torch.float32)
+        return c3.x, c3.bits, c3.mean, c3.invstd, part
 
     def backward(self, dfeat: torch.Tensor, g: torch.Tensor = None, part3: torch.Tensor = None):
         """Accumulates parameter gradients into `.grad` (fp32, reference layouts).  `self.on_group_done(k)`, if set,
@@ -1019,18 +1040,17 @@ class BackboneEngine:
         loss-scaled -- the last launch of creid_ctl_heads_fused writes it; `dfeat` is ignored then.  part3 (optional): the column
         sums of the deepest bn3 backward, produced by that same launch."""
         sv = self.saved
-        assert sv is not None and sv["training"], "backward() needs a training-mode forward first"
+        assert sv is not None, "backward() needs a training-mode forward first"
         lib, st, sched = L.lib(), L.stream(), self.sched
         self._bn_sums.clear()
-        B = sv["B"]
-        h, w = sv["final"]
+        B, (h, w) = sv.B, sv.final
         if g is None:
             dfeat = dfeat.contiguous().float()
             if self.loss_scaler is not None and self.dtype == torch.float16:
                 dfeat = self.loss_scaler.scale_(dfeat)        # every f16 gradient tensor / backbone parameter gradient below is scaled
             g = self._empty(B * h * w, self.cout)
             if self.gem is not None:
-                a_fin, stats = sv["gem"]
+                a_fin, stats = sv.gem
                 p = self.gem.p
                 # p.grad is final after this call, before any gradient of layer 4: the data-parallel bucket that closes with
                 # layer 4 (it runs to the end of the flat buffer, `gap.p` sits behind layer 4 in it) carries it
@@ -1047,86 +1067,10 @@ class BackboneEngine:
                                "backward: with pooling='gem' hand backward() the feature gradient dfeat")
         else:
             assert g.dtype == self.dtype and tuple(g.shape) == (B * h * w, self.cout) and g.is_contiguous()
-        blocks = list(zip(self.blocks, sv["blocks"]))
-        if self.basic:
-            g = self._backward_basic(blocks, g, B)
-            blocks = []
-        # part3: bn3 partials of the CURRENT block, produced by the previous (deeper) block -- for the deepest block by the heads'
-        # last launch when the caller hands them in (first_bn_bwd_operands)
-        for bi in range(len(blocks) - 1, -1, -1):
-            b, s = blocks[bi]
-            prev = blocks[bi - 1] if bi > 0 else None          # the block whose output gradient we produce
-            M3 = B * s["h2"] * s["w2"]
-            # the block's incoming gradient g is masked by the final ReLU on three paths (bn3, the residual add, the
-            # downsample BN).  With the mask as bits every consumer applies it itself and the masked copy `gm` is never
-            # written; otherwise bn3's backward writes it once.
-            m3 = getattr(s["a3"], "_relu_mask", None) if (sched.fuse_bn_reduce and sched.drop_gm) else None
-            # downsample blocks: bn3's apply pass also sums the columns the downsample branch's BatchNorm backward needs (same
-            # masked gradient, one read of it instead of two and one launch less; CREID_DS_REDUCE2=0: separate launches)
-            ds_part = None
-            if m3 is not None and b["ds"] is not None and sched.ds_reduce2 and not sched.fin_with_wred:
-                dx3, ds_part = self._bn_bwd(b["c3"], s["x3"], g, s["a3"], s["m3"], s["i3"], M3, part=part3,
-                                            reduce2=(s["xd"], s["md"], s["idd"]))
-                gm = g
-            else:
-                dx3, gm = self._bn_bwd(b["c3"], s["x3"], g, s["a3"], s["m3"], s["i3"], M3, want_gm=m3 is None, part=part3)
-                if m3 is not None:
-                    gm = g
-            # per convolution: data gradient first (it feeds the dependent chain dgrad -> BN finalize -> BN apply -> dgrad),
-            # then the weight gradient, which is off that chain and carries the finalize of the BatchNorm whose column sums
-            # the data gradient just produced (and, via the pending queue, gets its own split reduction carried by the
-            # NEXT data gradient)
-            def wg(u, a, dy, h_, w_, fin=None, early=False):   # the call site that matches the launch order issues it
-                if early == sched.wgrad_first:
-                    self._wgrad(u, a, dy, B, h_, w_, fin=None if sched.wgrad_first else fin)
-
-            wg(b["c3"], s["a2"], dx3, s["h2"], s["w2"], early=True)
-            da2, p2 = self._dgrad(b["c3"], dx3, B, s["h2"], s["w2"], bnred=(s["x2"], s["a2"], s["m2"], s["i2"]))
-            wg(b["c3"], s["a2"], dx3, s["h2"], s["w2"], fin=(b["c2"], p2, M3, s["m2"], s["i2"]))
-            dx2, _ = self._bn_bwd(b["c2"], s["x2"], da2, s["a2"], s["m2"], s["i2"], M3, part=p2)
-            ibn1 = b["c1"].ibn is not None
-            hw1 = s["h1"] * s["w1"]
-            ibn_fused = ibn1 and hw1 % 128 == 0          # per-image statistics: the 128-row tiles must not straddle images
-            wg(b["c2"], s["a1"], dx2, s["h1"], s["w1"], early=True)
-            da1, p1 = self._dgrad(b["c2"], dx2, B, s["h1"], s["w1"],
-                                  bnred=None if (ibn1 and not ibn_fused) else (s["x1"], s["a1"], s["m1"], s["i1"]),
-                                  stat_image_rows=hw1 if ibn_fused else 0)
-            M1 = B * s["h1"] * s["w1"]
-            wg(b["c2"], s["a1"], dx2, s["h1"], s["w1"], fin=None if ibn1 else (b["c1"], p1, M1, s["m1"], s["i1"]))
-            if ibn1:
-                dx1, _ = self._ibn_bwd(b["c1"], s["x1"], da1, s["a1"], s["m1"], s["i1"], B, hw1, part=p1)
-            else:
-                dx1, _ = self._bn_bwd(b["c1"], s["x1"], da1, s["a1"], s["m1"], s["i1"], M1, part=p1)
-            nxt = None if prev is None else (prev[1]["x3"], prev[1]["a3"], prev[1]["m3"], prev[1]["i3"])
-            wg(b["c1"], s["a_in"], dx1, s["hin"], s["win"], early=True)
-            if b["ds"] is not None:
-                dxd, _ = self._bn_bwd(b["ds"], s["xd"], gm, None, s["md"], s["idd"], M3, mask=m3, part=ds_part)
-                dsu = b["ds"]
-                if (dsu.stride == 2 and dsu.k == 1 and nxt is not None and sched.fuse_bn_reduce
-                        and s["hin"] % 2 == 0 and s["win"] % 2 == 0):
-                    # stride-2 1x1 downsample: its data gradient lives on the even pixels only -- compute it as a
-                    # plain 1x1 GEMM over the OUTPUT grid and let the c1 dgrad epilogue scatter-add it
-                    from types import SimpleNamespace
-                    shim = SimpleNamespace(cin=dsu.cin, cout=dsu.cout, k=1, stride=1, pad=0, w_crsk=dsu.w_crsk)
-                    tmp, _ = self._dgrad(shim, dxd, B, s["h2"], s["w2"])        # (also carries a pending split reduction)
-                    self._wgrad(b["ds"], s["a_in"], dxd, B, s["hin"], s["win"])
-                    g, part3 = self._dgrad(b["c1"], dx1, B, s["hin"], s["win"], add_src=tmp, bnred=nxt, add_src_stride=2)
-                else:
-                    tmp, _ = self._dgrad(dsu, dxd, B, s["hin"], s["win"])
-                    self._wgrad(b["ds"], s["a_in"], dxd, B, s["hin"], s["win"])
-                    g, part3 = self._dgrad(b["c1"], dx1, B, s["hin"], s["win"], add_src=tmp, bnred=nxt)
-            else:
-                g, part3 = self._dgrad(b["c1"], dx1, B, s["hin"], s["win"], add_src=gm, bnred=nxt, add_mask=m3)
-            Min = B * s["hin"] * s["win"]
-            wg(b["c1"], s["a_in"], dx1, s["hin"], s["win"],
-               fin=None if (prev is None or part3 is None) else (prev[0]["c3"], part3, Min, prev[1]["m3"], prev[1]["i3"]))
-            if self.on_group_done is not None and bi in self._group_first:
-                self._flush_wred()                       # the layer's last split reduction: nothing left to carry it
-                self.on_group_done(self._group_first[bi])
+        g = self._backward_basic(sv.blocks, g, B) if self.basic else self._backward_bottleneck(sv.blocks, g, part3, B)
         # stem
-        xpad, x0, y0, mean0, invstd0, idx0 = sv["stem"]
-        H, W = sv["H"], sv["W"]
-        H1, W1 = H // 2, W // 2
+        H, W, xpad, bn0, idx0 = sv.H, sv.W, sv.stem.xpad, sv.stem.bn, sv.stem.idx
+        H1, W1 = bn0.h, bn0.w
         if sched.stem_fuse_pool_bwd and not self.net.stem_relu:
             # the max-pool gradient is gathered inside the BatchNorm backward passes, the full-resolution dy0 is never written
             bn, M0 = self.stem.bn, B * H1 * W1
@@ -1135,13 +1079,13 @@ class BackboneEngine:
             dx0 = self._empty(M0, 64)
             dgam = self._grad_of(bn.weight) if bn.weight.requires_grad else None
             dbet = self._grad_of(bn.bias) if bn.bias.requires_grad else None
-            L.check(lib.creid_bn2d_bwd_pooled(L.ptr(x0), L.ptr(g), L.ptr(idx0), B, H1, W1, None, L.ptr(mean0), L.ptr(invstd0),
+            L.check(lib.creid_bn2d_bwd_pooled(L.ptr(bn0.x), L.ptr(g), L.ptr(idx0), B, H1, W1, None, L.ptr(bn0.mean), L.ptr(bn0.invstd),
                                               L.ptr(bn.weight), 64, self.dt, L.ptr(part0), L.ptr(sums0), L.ptr(dgam), L.ptr(dbet),
                                               L.ptr(dx0), st), "bn2d_bwd_pooled")
         else:
             dy0 = self._empty(B * H1 * W1, 64)
             L.check(lib.creid_maxpool3x3s2_bwd(L.ptr(g), L.ptr(idx0), B, H1, W1, 64, self.dt, L.ptr(dy0), st), "maxpool_bwd")
-            dx0, _ = self._bn_bwd(self.stem, x0, dy0, y0 if self.net.stem_relu else None, mean0, invstd0, B * H1 * W1)
+            dx0, _, _ = self._bn_bwd(bn0, dy0)
         if self.stem.conv.weight.requires_grad:
             nbytes = lib.creid_stem_conv_wgrad_workspace_bytes(B, H, W, self.dt)
             ws = self._workspace(nbytes)
@@ -1151,6 +1095,62 @@ class BackboneEngine:
         self._keep.clear()
         self.saved = None
 
+    def _backward_bottleneck(self, blocks, g, part3, B):
+        """Backward of the Bottleneck networks, block by block in reverse.  part3: bn3 partials of the CURRENT block, produced by
+        the previous (deeper) block -- for the deepest block by the heads' last launch when the caller hands them in
+        (first_bn_bwd_operands).  Returns the gradient w.r.t. the max-pool output."""
+        sched = self.sched
+        for bi in range(len(blocks) - 1, -1, -1):
+            s = blocks[bi]
+            c1, c2, c3, ds = s.c1, s.c2, s.c3, s.ds
+            nxt = blocks[bi - 1].c3 if bi > 0 else None     # bn3 of the block whose output gradient we produce
+            # the block's incoming gradient g is masked by the final ReLU on three paths (bn3, the residual add, the
+            # downsample BN).  With the mask as bits every consumer applies it itself and the masked copy `gm` is never
+            # written; otherwise bn3's backward writes it once.
+            m3 = c3.bits if (sched.fuse_bn_reduce and sched.drop_gm) else None
+            # downsample blocks: bn3's apply pass also sums the columns the downsample branch's BatchNorm backward needs (same
+            # masked gradient, one read of it instead of two and one launch less; CREID_DS_REDUCE2=0: separate launches)
+            reduce2 = ds if (m3 is not None and ds is not None and sched.ds_reduce2 and not sched.fin_with_wred) else None
+            dx3, gm, ds_part = self._bn_bwd(c3, g, want_gm=m3 is None, part=part3, reduce2=reduce2)
+            gm = g if m3 is not None else gm
+            da2, p2 = self._conv_bwd(c3.unit, c2.act, dx3, B, c2.h, c2.w, consumer=c2)
+            dx2, _, _ = self._bn_bwd(c2, da2, part=p2)
+            da1, p1 = self._conv_bwd(c2.unit, c1.act, dx2, B, c1.h, c1.w, consumer=c1)
+            dx1 = self._ibn_bwd(c1, da1, B, part=p1) if c1.unit.ibn is not None else self._bn_bwd(c1, da1, part=p1)[0]
+            # conv1: the downsample branch's launches lie between its weight gradient (where that comes first) and its data
+            # gradient, which adds the shortcut's gradient in its epilogue
+            if sched.wgrad_first:
+                self._wgrad(c1.unit, s.a_in, dx1, B, s.hin, s.win)
+            if ds is not None:
+                dxd, _, _ = self._bn_bwd(ds, gm, mask=m3, part=ds_part)
+                # stride-2 1x1 downsample: its data gradient lives on the even pixels only -- compute it as a plain 1x1 GEMM
+                # over the OUTPUT grid and let the c1 dgrad epilogue scatter-add it
+                even = (ds.unit.stride == 2 and ds.unit.k == 1 and nxt is not None and sched.fuse_bn_reduce
+                        and s.hin % 2 == 0 and s.win % 2 == 0)
+                gh, gw = (ds.h, ds.w) if even else (s.hin, s.win)
+                tmp, _ = self._dgrad(ds.unit, dxd, B, gh, gw, on_output_grid=even)       # (also carries a pending split reduction)
+                self._wgrad(ds.unit, s.a_in, dxd, B, s.hin, s.win)
+                g, part3 = self._dgrad(c1.unit, dx1, B, s.hin, s.win, add_src=tmp, consumer=nxt, add_src_stride=2 if even else 1)
+            else:
+                g, part3 = self._dgrad(c1.unit, dx1, B, s.hin, s.win, add_src=gm, consumer=nxt, add_mask=m3)
+            if not sched.wgrad_first:
+                self._wgrad(c1.unit, s.a_in, dx1, B, s.hin, s.win, fin=None if nxt is None else (nxt, part3))
+            if self.on_group_done is not None and bi in self._group_first:
+                self._flush_wred()                       # the layer's last split reduction: nothing left to carry it
+                self.on_group_done(self._group_first[bi])
+        return g
+
+    def _conv_bwd(self, u, a_in, dy, B, H, W, *, consumer):
+        """Both gradients of one convolution in the schedule's order, returns the data gradient's (dx, part).  Data gradient first:
+        it feeds the dependent chain dgrad -> BN finalize -> BN apply -> dgrad; the weight gradient is off that chain and carries
+        the finalize of `consumer`'s BatchNorm backward (and gets its own split reduction carried by the NEXT data gradient)."""
+        if self.sched.wgrad_first:
+            self._wgrad(u, a_in, dy, B, H, W)
+        dx, part = self._dgrad(u, dy, B, H, W, consumer=consumer)
+        if not self.sched.wgrad_first:
+            self._wgrad(u, a_in, dy, B, H, W, fin=None if consumer.unit.ibn is not None else (consumer, part))
+        return dx, part
+
     def _backward_basic(self, blocks, g, B):
         """Backward of the BasicBlock networks (resnet18 / resnet34), block by block in reverse: bn2 backward (it also writes the
         ReLU-masked gradient the shortcut needs), conv2's weight and data gradient, bn1 backward, conv1's weight gradient, the
@@ -1158,20 +1158,20 @@ class BackboneEngine:
         gradient added in its epilogue.  Plain launches of the same kernels as the bottleneck schedule; split reductions of the
         weight gradients ride in the following data gradients as there.  Returns the gradient w.r.t. the max-pool output."""
         for bi in range(len(blocks) - 1, -1, -1):
-            b, s = blocks[bi]
-            M2 = B * s["h2"] * s["w2"]
-            dx2, gm = self._bn_bwd(b["c2"], s["x2"], g, s["a2"], s["m2"], s["i2"], M2, want_gm=True)
-            self._wgrad(b["c2"], s["a1"], dx2, B, s["h1"], s["w1"])
-            da1, _ = self._dgrad(b["c2"], dx2, B, s["h1"], s["w1"])
-            dx1, _ = self._bn_bwd(b["c1"], s["x1"], da1, s["a1"], s["m1"], s["i1"], B * s["h1"] * s["w1"])
-            self._wgrad(b["c1"], s["a_in"], dx1, B, s["hin"], s["win"])
-            if b["ds"] is not None:
-                dxd, _ = self._bn_bwd(b["ds"], s["xd"], gm, None, s["md"], s["idd"], M2)
-                self._wgrad(b["ds"], s["a_in"], dxd, B, s["hin"], s["win"])
-                short, _ = self._dgrad(b["ds"], dxd, B, s["hin"], s["win"])
+            s = blocks[bi]
+            c1, c2, ds = s.c1, s.c2, s.ds
+            dx2, gm, _ = self._bn_bwd(c2, g, want_gm=True)
+            self._wgrad(c2.unit, c1.act, dx2, B, c1.h, c1.w)
+            da1, _ = self._dgrad(c2.unit, dx2, B, c1.h, c1.w)
+            dx1, _, _ = self._bn_bwd(c1, da1)
+            self._wgrad(c1.unit, s.a_in, dx1, B, s.hin, s.win)
+            if ds is not None:
+                dxd, _, _ = self._bn_bwd(ds, gm)
+                self._wgrad(ds.unit, s.a_in, dxd, B, s.hin, s.win)
+                short, _ = self._dgrad(ds.unit, dxd, B, s.hin, s.win)
             else:
                 short = gm
-            g, _ = self._dgrad(b["c1"], dx1, B, s["hin"], s["win"], add_src=short)
+            g, _ = self._dgrad(c1.unit, dx1, B, s.hin, s.win, add_src=short)
             if self.on_group_done is not None and bi in self._group_first:
                 self._flush_wred()
                 self.on_group_done(self._group_first[bi])
@@ -1182,8 +1182,8 @@ class BackboneEngine:
         group hook, of every layer group): the same job as the carried form, as its own launch."""
         lib, st = L.lib(), L.stream()
         while self._wred_pending:
-            rd, rgw, rws, rbytes = self._wred_pending.pop(0)
-            L.check(lib.creid_conv2d_wgrad_reduce_job(C.byref(rd), L.ptr(rgw), 1, L.ptr(rws), rbytes, self.dt, st),
+            job = self._wred_pending.pop(0)
+            L.check(lib.creid_conv2d_wgrad_reduce_job(C.byref(job.desc), L.ptr(job.grad), 1, L.ptr(job.ws), job.nbytes, self.dt, st),
                     "conv2d_wgrad_reduce_job")
 
 

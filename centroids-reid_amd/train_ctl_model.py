@@ -381,7 +381,7 @@ class CTLModel(ModelBase):
         masked = real is not None
         bn, W, centers = self.bn, self.fc_query.weight, self.center_loss.centers
         C_cls = W.shape[0]
-        h, w = eng.saved["final"]
+        h, w = eng.saved.final
 
         def grad_of(p):
             if not p.requires_grad:

@@ -638,7 +638,7 @@ def test_relu_bitmask_schedule_is_bit_identical(arch):
         eng.sched = dataclasses.replace(eng.sched, relu_bitmask=bits, c3_axf=frozenset())
         _, feat = eng.forward(x, training=True)
         if bits:
-            assert any(getattr(s["a3"], "_relu_mask", None) is not None for s in eng.saved["blocks"])
+            assert any(s.c3.bits is not None for s in eng.saved.blocks)
         eng.backward(coef)
         grads.append({n: p.grad.detach().clone() for n, p in net.named_parameters() if p.grad is not None})
     for n in grads[0]:
@@ -700,7 +700,7 @@ def test_stem_fusion_schedule_is_bit_identical(dtype):
         # (the -- off by default -- pooled BatchNorm backward as well)
         eng.sched = dataclasses.replace(eng.sched, stem_fuse_pool=fuse, stem_fuse_pool_bwd=fuse)
         _, feat = eng.forward(x, training=True)
-        assert (eng.saved["stem"][2] is None) == fuse
+        assert (eng.saved.stem.bn.act is None) == fuse
         eng.backward(coef)
         res.append((feat.clone(), {n: p.grad.detach().clone() for n, p in net.named_parameters() if p.grad is not None}))
     assert torch.equal(res[0][0], res[1][0])
@@ -727,7 +727,7 @@ def test_bn_finalize_carried_by_wgrad_matches_own_launch(arch):
         for _ in range(2):
             _, feat = eng.forward(x, training=True)
             eng.backward(coef)
-        assert not eng._wred_pending and not eng._bn_sums
+        assert not eng._wred_pending and not eng._bn_sums     # (_bn_sums: the carried finalizes issued and not yet consumed)
         grads.append({n: p.grad.detach().clone() for n, p in net.named_parameters() if p.grad is not None})
     for other in grads[:2]:
         for n in other:
@@ -958,8 +958,8 @@ def test_bn2_relu_inside_conv3_operand_path_is_bit_identical(arch, dtype, hw, mo
         eng.sched = dataclasses.replace(eng.sched, c3_axf=frozenset(widths))
         eng.loss_scaler = None
         _, f = eng.forward(x, training=True)
-        saved_masks = [blk["a2"]._relu_mask.clone() for blk in eng.saved["blocks"]]
-        saved_a2 = [blk["a2"].clone() for blk in eng.saved["blocks"]]
+        saved_masks = [blk.c2.bits.clone() for blk in eng.saved.blocks]
+        saved_a2 = [blk.c2.act.clone() for blk in eng.saved.blocks]
         eng.backward(coef)
         res.append((f.clone(), saved_a2, saved_masks, {n: p.grad.clone() for n, p in net.named_parameters() if p.grad is not None},
                     net.layer2[1].bn3.running_var.clone()))

@@ -1,5 +1,7 @@
 """GPU parity: CTLModel.training_step (train_ctl_model.py:38-179) -- heads against the golden vectors
 recorded from the reference's own training_step, and the full fp32 model against the CPU oracle."""
+from types import SimpleNamespace
+
 import numpy as np
 import pytest
 import torch
@@ -25,7 +27,7 @@ class EngineStub:
         self.weights_dirty = False
         # what creid_ctl_heads_fused needs to know about the backbone: a 1 x 1 final map (the pooled-back gradient IS the feature
         # gradient), fp32, no loss scale
-        self.saved = {"final": (1, 1)}
+        self.saved = SimpleNamespace(final=(1, 1))
         self.dtype, self.dt, self.loss_scaler = torch.float32, 0, None
 
     def forward(self, x, training, want_base_out=False):

@@ -177,13 +177,13 @@ def record_forward(cfg, monkeypatch):
 
     def conv_bn(u, a_in, B_, H_, W_, training, relu, residual=None, residual_ss=None, apply=True):
         out = o_cb(u, a_in, B_, H_, W_, training, relu, residual, residual_ss, apply)
-        rec.raw[id(u)] = dict(u=u, a_in=a_in, B=B_, H=H_, W=W_, x=out[0].clone())
+        rec.raw[id(u)] = dict(u=u, a_in=a_in, B=B_, H=H_, W=W_, x=out.x.clone())
         return out
 
-    def ibn_tail(u, x, B_, HW, training, relu, part=None):
-        out = o_it(u, x, B_, HW, training, relu, part)
-        rec.ibn.append(dict(u=u, x=x, B=B_, HW=HW, training=training, relu=relu, ready=part is not None, a=out[0].clone(),
-                            mean=out[1].clone(), invstd=out[2].clone()))
+    def ibn_tail(u, x, B_, h_, w_, training, relu, part=None):
+        out = o_it(u, x, B_, h_, w_, training, relu, part)           # (the SavedLayer of the IBN layer)
+        rec.ibn.append(dict(u=u, x=x, B=B_, HW=h_ * w_, training=training, relu=relu, ready=part is not None, a=out.act.clone(),
+                            mean=out.mean.clone(), invstd=out.invstd.clone()))
         return out
 
     def stem_operand(x, B_, H_, W_):

@@ -3,7 +3,7 @@
 One real step runs through CTLModel.forward_backward (creid_ctl_heads_fused writes the backbone's incoming gradient `g` and the
 deepest bn3 column sums `part3`, exactly as in bench.py; config F drives the engine with a given feature gradient, which takes the
 gap_bwd route).  The engine's methods are wrapped on the instance: `forward` (the pooled features), `backward` (a snapshot of
-`saved`, `g`, `part3`), `_bn_bwd`, `_ibn_bwd`, `_dgrad` (inputs and results cloned right after each call: stream order makes the
+`saved` -- the engine's SavedStep records --, `g`, `part3`), `_bn_bwd`, `_ibn_bwd`, `_dgrad` (inputs and results cloned right after each call: stream order makes the
 clone see exactly what the launch wrote) and `_wgrad` (its operands; weight and BatchNorm-parameter gradients are compared at the
 end, when the carried split reductions and finalizes have all run).  The C entry points called during the step are counted
 through a proxy of the library handle, so the routes the default knobs select are asserted, not assumed.  Knobs stay at their
@@ -48,6 +48,7 @@ Bias and relative-L2 bars: Audit.check's docstring.  Measured: |bias| <= 0.0064 
 Runtime: the seven configurations take 33 s on one MI355X.
 """
 import ctypes as C
+import dataclasses
 import math
 from collections import Counter
 from types import SimpleNamespace
@@ -134,42 +135,46 @@ def record_step(cfg, monkeypatch):
 
     def backward(dfeat, g=None, part3=None):
         sv = eng.saved
-        rec.saved = dict(sv, stem=tuple(sv["stem"]), blocks=[dict(b) for b in sv["blocks"]])
+        rec.saved = dataclasses.replace(sv, blocks=[dataclasses.replace(b) for b in sv.blocks])
         rec.g = None if g is None else g.clone()
         rec.part3 = part3 is not None
         rec.dfeat = None if dfeat is None else dfeat.clone()
         return o_bwd(dfeat, g=g, part3=part3)
 
-    def bn_bwd(u, x, g, act, mean, invstd, M, want_gm=False, part=None, mask=None, reduce2=None):
+    def bn_bwd(layer, g, *, want_gm=False, part=None, mask=None, reduce2=None):
+        u = layer.unit
         route = "ready2" if id(u) in eng._bn_sums else ("ready1" if part is not None else "ready0")
         if route == "ready1" and eng.sched.fin_with_wred and eng._wred_pending:
             route = "fin+wred"
-        bits = mask if mask is not None else (getattr(act, "_relu_mask", None) if act is not None else None)
+        act, own = (layer.act, layer.bits) if layer.relu else (None, None)      # (no ReLU behind the layer: nothing masks g)
         gc = g.clone()
-        out = o_bn(u, x, g, act, mean, invstd, M, want_gm=want_gm, part=part, mask=mask, reduce2=reduce2)
-        rec.bn.append(dict(u=u, x=x, g=gc, act=act, bits=bits, mean=mean, invstd=invstd, M=M, route=route,
-                           reduce2=reduce2 is not None, dx=out[0].clone(),
-                           gm=out[1].clone() if (want_gm and reduce2 is None and out[1] is not None) else None))
+        dx, gm, part2 = out = o_bn(layer, g, want_gm=want_gm, part=part, mask=mask, reduce2=reduce2)
+        assert (gm is not None) == (want_gm and reduce2 is None) and (part2 is not None) == (reduce2 is not None)
+        rec.bn.append(dict(u=u, x=layer.x, g=gc, act=act, bits=mask if mask is not None else own, mean=layer.mean,
+                           invstd=layer.invstd, M=layer.x.shape[0], route=route, reduce2=reduce2 is not None, dx=dx.clone(),
+                           gm=None if gm is None else gm.clone()))
         return out
 
-    def ibn_bwd(u, x, g, act, mean, invstd, B, HW, part=None):
+    def ibn_bwd(layer, g, B, part=None):
         gc = g.clone()
-        out = o_ibn(u, x, g, act, mean, invstd, B, HW, part=part)
-        rec.ibn.append(dict(u=u, x=x, g=gc, act=act, mean=mean, invstd=invstd, B=B, HW=HW, ready=part is not None,
-                            dx=out[0].clone()))
-        return out
+        dx = o_ibn(layer, g, B, part=part)
+        rec.ibn.append(dict(u=layer.unit, x=layer.x, g=gc, act=layer.act, bits=layer.bits, mean=layer.mean, invstd=layer.invstd,
+                            B=B, HW=layer.hw, ready=part is not None, dx=dx.clone()))
+        return dx
 
-    def dgrad(u, dy, B, H_, W_, add_src=None, bnred=None, stat_image_rows=0, add_src_stride=1, add_mask=None):
+    def dgrad(u, dy, B, H_, W_, *, add_src=None, consumer=None, add_src_stride=1, add_mask=None, on_output_grid=False):
         carry = bool(eng._wred_pending) and len(eng._wred_pending) >= (2 if eng.sched.fin_with_wred else 1)
         dyc = dy.clone()
         addc = None if add_src is None else add_src.clone()
-        out = o_dg(u, dy, B, H_, W_, add_src=add_src, bnred=bnred, stat_image_rows=stat_image_rows,
-                   add_src_stride=add_src_stride, add_mask=add_mask)
+        out = o_dg(u, dy, B, H_, W_, add_src=add_src, consumer=consumer, add_src_stride=add_src_stride, add_mask=add_mask,
+                   on_output_grid=on_output_grid)
+        # bnred: the launch also returned the column sums of the consumer's BatchNorm backward (never without a consumer)
+        assert out[1] is None or (consumer is not None and eng.sched.fuse_bn_reduce)
         rec.dgrad.append(dict(u=u, dy=dyc, B=B, H=H_, W=W_, add=addc, stride=add_src_stride, add_mask=add_mask,
-                              bnred=bnred is not None and eng.sched.fuse_bn_reduce, carry=carry, dx=out[0].clone()))
+                              bnred=out[1] is not None, carry=carry, on_output_grid=on_output_grid, dx=out[0].clone()))
         return out
 
-    def wgrad(u, a_in, dy, B, H_, W_, fin=None):
+    def wgrad(u, a_in, dy, B, H_, W_, *, fin=None):
         rec.wgrad.append(dict(u=u, a_in=a_in, dy=dy.clone(), B=B, H=H_, W=W_,
                               bnfin=fin is not None and fin[1] is not None and eng.sched.bnfin_piggyback and eng.sched.wred_piggyback))
         return o_wg(u, a_in, dy, B, H_, W_, fin=fin)
@@ -261,7 +266,8 @@ def _apply_ref(x, mean, invstd, gamma, beta):
     return x.double() * sc + sh, sc, sh, mean.double() * sc     # (|mean sc|: the rounding of shift = beta - mean sc)
 
 
-def _apply_check(au, rec, name, a_out, x, mean, invstd, bn, relu, residual=None, res_terms=()):
+def _apply_check(au, rec, name, layer, relu, residual=None, res_terms=()):
+    a_out, x, mean, invstd, bn = layer.act, layer.x, layer.mean, layer.invstd, layer.unit.bn
     M, Cc = x.shape
     y, sc, sh, msc = _apply_ref(x, mean, invstd, bn.weight, bn.bias)
     terms = list(res_terms) + [msc]
@@ -271,14 +277,14 @@ def _apply_check(au, rec, name, a_out, x, mean, invstd, bn, relu, residual=None,
     b = la.affine_bound(x.double(), sc, sh, terms)
     ref = y.clamp_min(0.0) if relu else y
     au.check(name, "apply", a_out, ref, b, _dt_out(rec), sigma=b)
-    bits = getattr(a_out, "_relu_mask", None)
-    if bits is not None:
-        au.relu_bits(name, bits, a_out.view(M, Cc), ref.view(M, Cc), rec.eng.dtype)
+    if layer.bits is not None:
+        au.relu_bits(name, layer.bits, a_out.view(M, Cc), ref.view(M, Cc), rec.eng.dtype)
     return ref
 
 
-def _ibn_fwd_check(au, rec, name, u, ref, e, x_raw, a_out, mean, invstd, B, HW):
+def _ibn_fwd_check(au, rec, name, layer, ref, e, B):
     """IBN-a bn1: InstanceNorm (per image) on the first `half` channels, BatchNorm on the rest; mean / invstd are [B, C]"""
+    u, x_raw, a_out, mean, invstd, HW = layer.unit, layer.x, layer.act, layer.mean, layer.invstd, layer.hw
     ibn, bn = u.ibn, u.bn
     h = ibn.half
     Cc = ref.shape[1]
@@ -309,9 +315,8 @@ def _ibn_fwd_check(au, rec, name, u, ref, e, x_raw, a_out, mean, invstd, B, HW):
     b = la.affine_bound(x, sc.unsqueeze(1), sh.unsqueeze(1), [(mean.double() * sc).unsqueeze(1)])
     ref_a = y.clamp_min(0.0)
     au.check(name, "IBN apply", a_out, ref_a, b, _dt_out(rec), sigma=b)
-    bits = getattr(a_out, "_relu_mask", None)
-    if bits is not None:
-        au.relu_bits(name, bits, a_out.view(B * HW, Cc), ref_a.view(B * HW, Cc), rec.eng.dtype)
+    if layer.bits is not None:
+        au.relu_bits(name, layer.bits, a_out.view(B * HW, Cc), ref_a.view(B * HW, Cc), rec.eng.dtype)
 
 
 def _pool_tie_check(au, rec, x0, mean0, invstd0, bn, idx0, p0, B, H1, W1, dt):
@@ -367,7 +372,8 @@ def audit_forward(au, rec):
     dt = eng.dtype
     _weight_copies_check(au, rec)
     # stem: layout pass, 7 x 7 conv, bn1 statistics, apply (+ ReLU) and the 3 x 3 s2 max-pool with its taps
-    xpad, x0, y0, mean0, invstd0, idx0 = sv["stem"]
+    xpad, bn0, idx0 = sv.stem.xpad, sv.stem.bn, sv.stem.idx
+    x0, y0, mean0, invstd0 = bn0.x, bn0.act, bn0.mean, bn0.invstd
     img = xpad[:, 3:3 + H, 3:3 + W, :3]
     au.exact("stem", "image layout", torch.equal(img, rec.x.permute(0, 2, 3, 1).to(dt)))
     st = eng.stem
@@ -379,11 +385,11 @@ def audit_forward(au, rec):
     m_ref, var_ref, dm, dvar = _stats_check(au, rec, "stem", st.bn, ref0, e0, mean0, invstd0)
     _running_check(au, rec, "stem", st, m_ref, var_ref, dm, dvar, ref0.shape[0])
     H1, W1 = H // 2, W // 2
-    p0 = sv["blocks"][0]["a_in"]
+    p0 = sv.blocks[0].a_in
     y, sc, sh, msc = _apply_ref(x0, mean0, invstd0, st.bn.weight, st.bn.bias)
     b = la.affine_bound(x0.double(), sc, sh, [msc])
     if eng.net.stem_relu:
-        _apply_check(au, rec, "stem", y0, x0, mean0, invstd0, st.bn, True)
+        _apply_check(au, rec, "stem", bn0, True)
         pv, pidx, taps = la.maxpool3x3s2(y0.view(B, H1, W1, 64).double())       # pooled values of the stored activation: exact
         au.exact("stem", "max-pool values", torch.equal(p0.view_as(pv).double(), pv))
         au.exact("stem", "max-pool taps (first max)", torch.equal(idx0.view_as(pidx).long(), pidx))
@@ -396,37 +402,38 @@ def audit_forward(au, rec):
         au.exact("stem", "max-pool tap is a window max", bool((sel >= pv - 2 * bb - 2 * la.half_ulp(pv, dt)).all()))
         _pool_tie_check(au, rec, x0, mean0, invstd0, st.bn, idx0, p0, B, H1, W1, dt)
     # bottlenecks
-    for b_u, s in zip(eng.blocks, sv["blocks"]):
-        n1, n2, n3 = (rec.names[id(b_u[k])] for k in ("c1", "c2", "c3"))
-        hin, win, h1, w1, h2, w2 = s["hin"], s["win"], s["h1"], s["w1"], s["h2"], s["w2"]
-        ref1, e1, t1 = _conv_check(au, rec, n1, b_u["c1"], s["a_in"], B, hin, win, s["x1"])
-        if b_u["c1"].ibn is not None:
-            _ibn_fwd_check(au, rec, n1, b_u["c1"], ref1, e1, s["x1"], s["a1"], s["m1"], s["i1"], B, h1 * w1)
+    for b_u, s in zip(eng.blocks, sv.blocks):
+        c1, c2, c3, ds = s.c1, s.c2, s.c3, s.ds
+        assert [l.unit for l in (c1, c2, c3)] == [b_u[k] for k in ("c1", "c2", "c3")] and (ds is None) == (b_u["ds"] is None)
+        n1, n2, n3 = (rec.names[id(l.unit)] for l in (c1, c2, c3))
+        ref1, e1, t1 = _conv_check(au, rec, n1, c1.unit, s.a_in, B, s.hin, s.win, c1.x)
+        if c1.unit.ibn is not None:
+            _ibn_fwd_check(au, rec, n1, c1, ref1, e1, B)
         else:
-            m_ref, var_ref, dm, dvar = _stats_check(au, rec, n1, b_u["c1"].bn, ref1, e1, s["m1"], s["i1"], t1)
-            _running_check(au, rec, n1, b_u["c1"], m_ref, var_ref, dm, dvar, ref1.shape[0])
-            _apply_check(au, rec, n1, s["a1"], s["x1"], s["m1"], s["i1"], b_u["c1"].bn, True)
-        ref2, e2, t2 = _conv_check(au, rec, n2, b_u["c2"], s["a1"], B, h1, w1, s["x2"])
-        m_ref, var_ref, dm, dvar = _stats_check(au, rec, n2, b_u["c2"].bn, ref2, e2, s["m2"], s["i2"], t2)
-        _running_check(au, rec, n2, b_u["c2"], m_ref, var_ref, dm, dvar, ref2.shape[0])
-        _apply_check(au, rec, n2, s["a2"], s["x2"], s["m2"], s["i2"], b_u["c2"].bn, True)
-        ref3, e3, t3 = _conv_check(au, rec, n3, b_u["c3"], s["a2"], B, h2, w2, s["x3"])
-        m_ref, var_ref, dm, dvar = _stats_check(au, rec, n3, b_u["c3"].bn, ref3, e3, s["m3"], s["i3"], t3)
-        _running_check(au, rec, n3, b_u["c3"], m_ref, var_ref, dm, dvar, ref3.shape[0])
-        if b_u["ds"] is not None:
-            nd = rec.names[id(b_u["ds"])]
-            refd, ed, td = _conv_check(au, rec, nd, b_u["ds"], s["a_in"], B, hin, win, s["xd"])
-            m_ref, var_ref, dm, dvar = _stats_check(au, rec, nd, b_u["ds"].bn, refd, ed, s["md"], s["idd"], td)
-            _running_check(au, rec, nd, b_u["ds"], m_ref, var_ref, dm, dvar, refd.shape[0])
-            assert eng.sched.dual_apply
-            r, scd, shd, mscd = _apply_ref(s["xd"], s["md"], s["idd"], b_u["ds"].bn.weight, b_u["ds"].bn.bias)   # dual: fp32, unrounded
-            res_terms = [s["xd"].double() * scd, shd, mscd]
+            m_ref, var_ref, dm, dvar = _stats_check(au, rec, n1, c1.unit.bn, ref1, e1, c1.mean, c1.invstd, t1)
+            _running_check(au, rec, n1, c1.unit, m_ref, var_ref, dm, dvar, ref1.shape[0])
+            _apply_check(au, rec, n1, c1, True)
+        ref2, e2, t2 = _conv_check(au, rec, n2, c2.unit, c1.act, B, c1.h, c1.w, c2.x)
+        m_ref, var_ref, dm, dvar = _stats_check(au, rec, n2, c2.unit.bn, ref2, e2, c2.mean, c2.invstd, t2)
+        _running_check(au, rec, n2, c2.unit, m_ref, var_ref, dm, dvar, ref2.shape[0])
+        _apply_check(au, rec, n2, c2, True)
+        ref3, e3, t3 = _conv_check(au, rec, n3, c3.unit, c2.act, B, c2.h, c2.w, c3.x)
+        m_ref, var_ref, dm, dvar = _stats_check(au, rec, n3, c3.unit.bn, ref3, e3, c3.mean, c3.invstd, t3)
+        _running_check(au, rec, n3, c3.unit, m_ref, var_ref, dm, dvar, ref3.shape[0])
+        if ds is not None:
+            nd = rec.names[id(ds.unit)]
+            refd, ed, td = _conv_check(au, rec, nd, ds.unit, s.a_in, B, s.hin, s.win, ds.x)
+            m_ref, var_ref, dm, dvar = _stats_check(au, rec, nd, ds.unit.bn, refd, ed, ds.mean, ds.invstd, td)
+            _running_check(au, rec, nd, ds.unit, m_ref, var_ref, dm, dvar, refd.shape[0])
+            assert eng.sched.dual_apply and ds.act is None and not ds.relu
+            r, scd, shd, mscd = _apply_ref(ds.x, ds.mean, ds.invstd, ds.unit.bn.weight, ds.unit.bn.bias)   # dual: fp32, unrounded
+            res_terms = [ds.x.double() * scd, shd, mscd]
         else:
-            r, res_terms = s["a_in"].double(), []
-        _apply_check(au, rec, n3, s["a3"], s["x3"], s["m3"], s["i3"], b_u["c3"].bn, True, residual=r, res_terms=res_terms)
+            r, res_terms = s.a_in.double(), []
+        _apply_check(au, rec, n3, c3, True, residual=r, res_terms=res_terms)
     # GAP
-    h, w = sv["final"]
-    a = sv["blocks"][-1]["a3"].view(B, h * w, -1).double()
+    h, w = sv.final
+    a = sv.blocks[-1].c3.act.view(B, h * w, -1).double()
     ref = a.mean(1)
     au.check("gap", "gap fwd", rec.feat, ref, h * w * la.U * a.abs().mean(1) + la.U * ref.abs(), F32, bias=False,
              sigma=math.sqrt(h * w) * la.U * a.abs().mean(1))
@@ -437,7 +444,7 @@ def audit_backward(au, rec):
     B = rec.B
     dt = eng.dtype
     x3 = eng.x3
-    h, w = sv["final"]
+    h, w = sv.final
     grads = {}                   # parameter -> (ref, bound): the BatchNorm / InstanceNorm gamma and beta gradients
     if rec.g is not None:
         gv = rec.g.view(B, h * w, -1)
@@ -464,7 +471,7 @@ def audit_backward(au, rec):
             # max-pool backward: the stem BatchNorm's incoming gradient is the last data gradient scattered through idx0
             H1, W1 = rec.H // 2, rec.W // 2
             gp = rec.dgrad[-1]["dx"].view(B, H1 // 2, W1 // 2, 64)
-            idx0 = sv["stem"][5].view(B, H1 // 2, W1 // 2, 64)
+            idx0 = sv.stem.idx.view(B, H1 // 2, W1 // 2, 64)
             refp = la.maxpool3x3s2_bwd(gp, idx0, H1, W1)
             bp = 3 * la.U * la.maxpool3x3s2_bwd(gp.abs(), idx0, H1, W1)
             au.check("stem", "max-pool bwd", r["g"], refp.reshape(r["g"].shape), bp, dt, sigma=bp)
@@ -476,7 +483,7 @@ def audit_backward(au, rec):
         hh = ibn.half
         B_, HW = r["B"], r["HW"]
         M, Cc = r["x"].shape
-        mask = _mask_of(getattr(r["act"], "_relu_mask", None), r["act"], M, Cc)
+        mask = _mask_of(r["bits"], r["act"], M, Cc)
         dy = r["g"].double() if mask is None else r["g"].double() * mask
         rpi = rec.lib.creid_ibn_rows_per_image(HW)
         tile = -(-HW // rpi)
@@ -492,18 +499,18 @@ def audit_backward(au, rec):
         grads[ibn.IN.weight] = (s2i.sum(0), d2i.sum(0))
         grads[bn.bias] = (s1b.view(-1), d1b.view(-1))
         grads[bn.weight] = (s2b.view(-1), d2b.view(-1))
-    wptr = {u.w_crsk.data_ptr(): u for u in eng.all_units() if u.w_crsk is not None}
     for r in rec.dgrad:
         u = r["u"]
-        shim = id(u) not in rec.names
-        base = wptr[u.w_crsk.data_ptr()] if shim else u
-        name = rec.names[id(base)]
-        wt = _bwd_w(rec, base)
+        name = rec.names[id(u)]
+        wt = _bwd_w(rec, u)
         B_, H_, W_ = r["B"], r["H"], r["W"]
-        oh, ow = (H_ + 2 * u.pad - u.k) // u.stride + 1, (W_ + 2 * u.pad - u.k) // u.stride + 1
+        # on_output_grid (the stride-2 1 x 1 downsample): the same weights as a stride-1 1 x 1 convolution over the output grid
+        k, stride, pad = (1, 1, 0) if r["on_output_grid"] else (u.k, u.stride, u.pad)
+        assert not r["on_output_grid"] or (u.k, u.stride, u.pad) == (1, 2, 0)
+        oh, ow = (H_ + 2 * pad - k) // stride + 1, (W_ + 2 * pad - k) // stride + 1
         dy = r["dy"].view(B_, oh, ow, u.cout)
-        ref = la.conv_dgrad(dy, wt, u.stride, u.pad, H_, W_)
-        mag = la.conv_dgrad(dy.double().abs(), wt.abs(), u.stride, u.pad, H_, W_)
+        ref = la.conv_dgrad(dy, wt, stride, pad, H_, W_)
+        mag = la.conv_dgrad(dy.double().abs(), wt.abs(), stride, pad, H_, W_)
         add = torch.zeros((), dtype=torch.float64, device=ref.device)
         tags = []
         if r["add"] is not None:
@@ -523,9 +530,9 @@ def audit_backward(au, rec):
             tags.append("bnred")
         if r["carry"]:
             tags.append("carry")
-        if shim:
+        if r["on_output_grid"]:
             tags.append("s2 shim")
-        K = u.cout * u.k * u.k
+        K = u.cout * k * k
         e = K * la.U * mag + (la.SPLIT * mag if x3 else 0.0)
         sig = math.sqrt(K) * la.U * mag + (la.SPLIT * mag if x3 else 0.0)
         if r["add"] is not None:
@@ -563,7 +570,7 @@ def audit_backward(au, rec):
                  report_max_rms=x3)
     st = eng.stem
     H, W = rec.H, rec.W
-    img = sv["stem"][0][:, 3:3 + H, 3:3 + W, :3]
+    img = sv.stem.xpad[:, 3:3 + H, 3:3 + W, :3]
     dy0 = rec.stem_dx.view(B, H // 2, W // 2, 64)
     ref = la.conv_wgrad(img, dy0, 7, 2, 3)
     mag = la.conv_wgrad(img.double().abs(), dy0.double().abs(), 7, 2, 3)
@@ -660,7 +667,7 @@ def test_layer_audit(cfg, monkeypatch):
     if cfg == "F-bf16":
         # the audit can fail: one channel of one recorded conv output x (1 + 2^-7) is named, and nothing else is
         target = "layer1.0.conv1"
-        x1 = rec.saved["blocks"][0]["x1"]
+        x1 = rec.saved.blocks[0].c1.x
         x1.view(-1, x1.shape[1])[:, 5] *= (1.0 + 2.0 ** -7)
         bad = run_audit(rec, cfg + "-perturbed")
         assert bad.failing_layers() == {target}, bad.failures[:20]

@@ -206,17 +206,17 @@ def test_backward_pass_differs_only_in_the_covered_weight_gradients(monkeypatch)
         seen = {}
         inner = eng._wgrad
 
-        def record(u, a_in, dy, B, H, W, fin=None, inner=inner, seen=seen):
+        def record(u, a_in, dy, B, H, W, *, fin=None, inner=inner, seen=seen):
             if u.k == 3 and u.stride == 1 and tc.covers(u.cin, u.cout, 3, 1, 1, H, W, H, W, B * H * W):
                 seen[id(u.conv.weight)] = (a_in.detach().clone().view(B, H, W, u.cin), dy.detach().clone().view(B, H, W, u.cout))
-            return inner(u, a_in, dy, B, H, W, fin)
+            return inner(u, a_in, dy, B, H, W, fin=fin)
 
         eng._wgrad = record
         n0 = _launches()
         eng.forward(x, training=True)
         eng.backward(coef)
         torch.cuda.synchronize()
-        assert not eng._wred_pending and not eng._bn_sums
+        assert not eng._wred_pending and not eng._bn_sums     # (_bn_sums: the carried finalizes issued and not yet consumed)
         names = {id(p): n for n, p in net.named_parameters()}
         runs.append((_launches() - n0, {n: p.grad.detach().clone() for n, p in net.named_parameters() if p.grad is not None},
                      {names[k]: v for k, v in seen.items()}))

@@ -5,6 +5,8 @@
     python tools/backbone_schedule_dump.py resolve --write    # ... or write tests/golden/backbone_schedule.json
     python tools/backbone_schedule_dump.py trace              # compare the C-level launch order with the golden (one GPU)
     python tools/backbone_schedule_dump.py trace --write      # ... or write tests/golden/backbone_launch_trace.json
+    python tools/backbone_schedule_dump.py trace --args       # compare every call's arguments and the results' checksums (one GPU)
+    python tools/backbone_schedule_dump.py trace --args --write   # ... or write tests/golden/backbone_launch_args.json
 
 The tool sets switches through environment variables only, before it constructs a BackboneEngine, and reads only the engine's
 schedule attributes (`eng.sched.<field>` where the engine keeps a Schedule value, `eng.<field>` where it keeps loose
@@ -17,8 +19,17 @@ on CPU parameter holders.  A combination the constructor rejects is recorded wit
 trace: one training forward + backward (twice, so the rotating workspaces wrap) or one eval forward at B = 4, 128 x 64 per
 TRAIN_CASES / EVAL_CASES x SETTINGS, through a proxy of the library handle that keeps the ordered entry-point names (host-side
 size queries included).  The library reads CREID_IGEMM_DMA once per process, so the settings that carry it run in a child
-process of their own (`--group dma0`).  Distinct name sequences are stored once, as indices into one name table."""
+process of their own (`--group dma0`).  Distinct name sequences are stored once, as indices into one name table.
+
+trace --args: the same runs, and per call through the proxy every scalar argument by value (floats by repr), every ConvDesc
+passed by reference as its field tuple, every pointer as null / non-null ("p"); per case an integer checksum, computed on the
+device, of `feat`, every parameter gradient and every BatchNorm running statistic after the two rounds: the tensor viewed as int32,
+widened to int64, summed plainly and weighted by 1-based index (wrap-around integer sums: independent of the reduction order).
+The `default` rows are stored in full (distinct calls once, as indices into one call table); every other row as one SHA-256 of
+its canonical call list and checksums."""
 import argparse
+import ctypes
+import hashlib
 import json
 import os
 import subprocess
@@ -29,6 +40,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 GOLDEN_RESOLVE = os.path.join(ROOT, "tests", "golden", "backbone_schedule.json")
 GOLDEN_TRACE = os.path.join(ROOT, "tests", "golden", "backbone_launch_trace.json")
+GOLDEN_ARGS = os.path.join(ROOT, "tests", "golden", "backbone_launch_args.json")
 
 # every schedule switch the engine keeps: name -> (default, the non-default values the tables cover)
 SWITCHES = {
@@ -135,13 +147,37 @@ def expand_rows(doc):
 
 
 # ------------------------------------------------------------------------------------------ trace
+def _arg(v):
+    """one argument of a library call as a JSON value: None = null pointer, "p" = non-null pointer, int, repr(float), or the
+    field list of a ConvDesc passed by reference"""
+    if v is None:
+        return None
+    if isinstance(v, ctypes.c_void_p):
+        return "p" if v.value else None
+    if isinstance(v, (bool, int)):
+        return int(v)
+    if isinstance(v, float):
+        return repr(v)
+    obj = getattr(v, "_obj", None)                      # ctypes.byref(...)
+    if type(obj).__name__ == "ConvDesc":
+        return [int(getattr(obj, f)) for f, _ in obj._fields_]
+    raise TypeError(f"argument {v!r}: neither a scalar, a pointer nor a ConvDesc by reference")
+
+
 class _LibProxy:
-    def __init__(self, lib, names):
-        self._lib, self._names = lib, names
+    def __init__(self, lib, names, calls=None):
+        self._lib, self._names, self._calls = lib, names, calls
 
     def __getattr__(self, name):
         self._names.append(name)
-        return getattr(self._lib, name)
+        fn = getattr(self._lib, name)
+        if self._calls is None:
+            return fn
+
+        def call(*a):
+            self._calls.append([name] + [_arg(v) for v in a])
+            return fn(*a)
+        return call
 
 
 _NETS = {}
@@ -158,12 +194,25 @@ def _net(arch):
     return copy.deepcopy(_NETS[arch])
 
 
-def trace_case(kind, arch, dtype):
+def _checksums(named):
+    """{name: [plain sum, index-weighted sum]} of fp32 device tensors, as wrap-around int64 sums of their int32 bit patterns; one
+    copy back"""
+    import torch
+    rows = []
+    for _, t in named:
+        v = t.detach().contiguous().view(torch.int32).reshape(-1).to(torch.int64)
+        rows.append(torch.stack((v.sum(), (v * torch.arange(1, v.numel() + 1, dtype=torch.int64, device=v.device)).sum())))
+    host = torch.stack(rows).cpu().tolist()
+    return {n: r for (n, _), r in zip(named, host)}
+
+
+def trace_case(kind, arch, dtype, args=False):
     """the ordered entry-point names of one case under the current environment: {"names": [...]} (training cases also say whether
-    the engine offers the heads the operands of the first BatchNorm backward), or {"error": text}"""
+    the engine offers the heads the operands of the first BatchNorm backward), or {"error": text}.  args: also "calls" (every
+    call with its arguments, _arg) and "sums" (_checksums of the results)"""
     import torch
     from centroids_reid_amd import _lib as L
-    real, names = L.lib(), []
+    real, names, calls = L.lib(), [], ([] if args else None)
     try:
         eng = engine(_net(arch), dtype)
     except Exception as e:
@@ -173,21 +222,26 @@ def trace_case(kind, arch, dtype):
     coef = torch.randn((B, eng.cout), generator=g).cuda()
     out = {}
     orig = L.lib
-    L.lib = lambda: _LibProxy(real, names)
+    L.lib = lambda: _LibProxy(real, names, calls)
     try:
         if kind == "eval":
             with torch.no_grad():
-                eng.forward(x, training=False)
+                _, feat = eng.forward(x, training=False)
         else:
             for rnd in range(2):
-                eng.forward(x, training=True)
+                _, feat = eng.forward(x, training=True)
                 if rnd == 0:
                     L.lib = orig                      # (not part of forward / backward: the heads ask for it in a full step)
                     out["heads_bnred_operands"] = eng.first_bn_bwd_operands() is not None
-                    L.lib = lambda: _LibProxy(real, names)
+                    L.lib = lambda: _LibProxy(real, names, calls)
                 eng.backward(coef)
     finally:
         L.lib = orig
+    if args:
+        out["calls"] = calls
+        out["sums"] = _checksums([("feat", feat)] +
+                                 [("grad " + n, p.grad) for n, p in eng.net.named_parameters() if p.grad is not None] +
+                                 [(n, b) for n, b in eng.net.named_buffers() if n.endswith(("running_mean", "running_var"))])
     torch.cuda.synchronize()
     for p in eng.net.parameters():
         p.grad = None
@@ -195,31 +249,46 @@ def trace_case(kind, arch, dtype):
     return out
 
 
-def trace_setting(s):
-    """{case key: trace_case(...)} for every case under the setting `s`"""
+def digest_case(key, t):
+    """what the argument record keeps of one traced case: calls and checksums in full for a `default` row, their SHA-256 otherwise"""
+    t = dict(t)
+    t.pop("names", None)
+    if "calls" in t and not key.endswith("| default"):
+        canon = json.dumps({"calls": t.pop("calls"), "sums": t.pop("sums")}, sort_keys=True, separators=(",", ":"))
+        t["sha256"] = hashlib.sha256(canon.encode()).hexdigest()
+    return t
+
+
+def trace_setting(s, args=False):
+    """{case key: trace_case(...)} for every case under the setting `s`.  args: each case carries its names and, under "args",
+    its digest_case"""
     out = {}
     with _Env(s):
         for kind, cases in (("train", TRAIN_CASES), ("eval", EVAL_CASES)):
             for arch, dtype in cases:
-                out[f"{kind} {arch} {dtype} | {setting_name(s)}"] = trace_case(kind, arch, dtype)
+                key = f"{kind} {arch} {dtype} | {setting_name(s)}"
+                t = trace_case(kind, arch, dtype, args)
+                if args:
+                    t = {k: v for k, v in t.items() if k not in ("calls", "sums")} | {"args": digest_case(key, t)}
+                out[key] = t
     return out
 
 
-def trace_group(group):
+def trace_group(group, args=False):
     out = {}
     for s in SETTINGS:
         if group_of(s) == group:
-            out.update(trace_setting(s))
+            out.update(trace_setting(s, args))
     return out
 
 
-def trace_all():
+def trace_all(args=False):
     """both groups, each in a child process of its own (the parent never opens the GPU)"""
     out = {}
     for group in ("dma1", "dma0"):
         env = {k: v for k, v in os.environ.items() if k not in SWITCHES}
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "trace", "--group", group], env=env, cwd=ROOT,
-                           stdout=subprocess.PIPE, text=True, timeout=900)
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "trace", "--group", group] + (["--args"] if args else []),
+                           env=env, cwd=ROOT, stdout=subprocess.PIPE, text=True, timeout=900)
         if r.returncode != 0:
             raise SystemExit(f"trace group {group} failed with exit status {r.returncode}")
         out.update(json.loads(r.stdout.splitlines()[-1]))
@@ -252,6 +321,58 @@ def expand_traces(doc):
     return out
 
 
+def condense_args(digests):
+    """{case key: digest_case(...)} -> the stored form: distinct calls once, a default row's calls as indices into that table"""
+    table, index, seqs, cases = [], {}, [], {}
+    for key, t in digests.items():
+        t = dict(t)
+        if "calls" in t:
+            seq = []
+            for c in t.pop("calls"):
+                k = json.dumps(c)
+                if k not in index:
+                    index[k] = len(table)
+                    table.append(c)
+                seq.append(index[k])
+            if seq not in seqs:
+                seqs.append(seq)
+            t["seq"] = seqs.index(seq)
+        cases[key] = t
+    return {"shape": [B, H, W], "calls": table, "seqs": seqs, "cases": cases}
+
+
+def expand_args(doc):
+    out = {}
+    for key, t in doc["cases"].items():
+        t = dict(t)
+        if "seq" in t:
+            t["calls"] = [doc["calls"][i] for i in doc["seqs"][t.pop("seq")]]
+        out[key] = t
+    return out
+
+
+def args_difference(key, got, ref):
+    """None if the digest `got` of case `key` equals the recorded `ref`, else one line that says where it differs: in a default
+    row the first differing call and argument slot, or the first differing tensor checksum"""
+    if got == ref:
+        return None
+    if "calls" in got and "calls" in ref:
+        for i, (a, b) in enumerate(zip(got["calls"], ref["calls"])):
+            if a != b:
+                if a[0] != b[0] or len(a) != len(b):
+                    return f"{key}: call {i} is {a}, recorded {b}"
+                j = next(j for j in range(1, len(a)) if a[j] != b[j])
+                return f"{key}: call {i} {a[0]}, argument {j - 1} is {a[j]!r}, recorded {b[j]!r}"
+        if len(got["calls"]) != len(ref["calls"]):
+            return f"{key}: {len(got['calls'])} calls, recorded {len(ref['calls'])}"
+        for n in sorted(set(got["sums"]) | set(ref["sums"])):
+            if got["sums"].get(n) != ref["sums"].get(n):
+                return f"{key}: same calls, checksum of {n} is {got['sums'].get(n)}, recorded {ref['sums'].get(n)}"
+    def short(t):                                       # (a non-default row: the hash; any row: the flags, or the refusal)
+        return {k: v for k, v in t.items() if k not in ("calls", "sums")}
+    return f"{key}: {short(got)}, recorded {short(ref)}"
+
+
 def _dump(doc, path):
     """one top-level key per line; the long tables one entry per line (diffs stay readable)"""
     def js(v):
@@ -272,10 +393,23 @@ def main():
     ap.add_argument("mode", choices=("resolve", "trace"))
     ap.add_argument("--write", nargs="?", const="", default=None, help="write the table (to PATH, default: the golden file)")
     ap.add_argument("--group", choices=("dma1", "dma0"), help="trace: run one group of settings in this process, print JSON")
+    ap.add_argument("--args", action="store_true", help="trace: the argument-level record (backbone_launch_args.json)")
     a = ap.parse_args()
     if a.mode == "trace" and a.group:
-        print(json.dumps(trace_group(a.group), separators=(",", ":")))
+        print(json.dumps(trace_group(a.group, a.args), separators=(",", ":")))
         return 0
+    if a.mode == "trace" and a.args:
+        got = {k: t["args"] for k, t in trace_all(True).items()}
+        if a.write is not None:
+            _dump(condense_args(got), a.write or GOLDEN_ARGS)
+            print(f"wrote {a.write or GOLDEN_ARGS}: {len(got)} cases")
+            return 0
+        ref = expand_args(json.load(open(GOLDEN_ARGS)))
+        bad = [d for d in (args_difference(k, got.get(k, {}), ref.get(k, {})) for k in sorted(set(ref) | set(got))) if d]
+        for b in bad[:20]:
+            print("DIFFERS:", b)
+        print(f"{len(got)} cases, {len(bad)} differ from {os.path.relpath(GOLDEN_ARGS, ROOT)}")
+        return 1 if bad else 0
     got = resolve_rows() if a.mode == "resolve" else trace_all()
     golden = GOLDEN_RESOLVE if a.mode == "resolve" else GOLDEN_TRACE
     if a.write is not None:
